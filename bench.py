@@ -8,10 +8,18 @@ A step = one pass of the fused sweep+DPV entry point (pdepth_sweep_dpv_f32, NCHW
 over one batch of synthetic inputs already resident in HBM.  Workload = BASELINE.json configs[1]: mono eval, B=4
 volumes per GPU, V=1, C=67, D=64, sweep resolution 256x512.  With N GPUs every rank owns its own B=4 batch (weak
 scaling, no data-path collective); per-rank metrics are all-gathered once at the end (RCCL).  Prints ONE JSON line on
-rank 0.  Next to the headline it reports the same step through the packed-source entry
-(pdepth_sweep_dpv_packed_f32: features already in the kernels' staging layout) as `packed_entry`, and SURVEY 8(d)'s
-secondary figures: `model_real` (the shape the reference's model sweeps a 256x512 frame at, 64x128, B = 1 and 4, both entries)
-and `peaked` (the headline workload on the correlated feature variant).
+rank 0.  A plain run does only what the headline needs: it sets up, warms up (an untimed preheat of the headline step, then
+W warm-up steps), times the K steps, writes their outputs if --dump-outputs is given and prints the line.
+
+--full adds everything else the line used to carry, around the headline: `cold_start`, the gather-kernel cross-check
+(`preflight`), the same step through the packed-source entry (pdepth_sweep_dpv_packed_f32: features already in the kernels'
+staging layout) as `packed_entry`, SURVEY 8(d)'s secondary figures -- `model_real` (the shape the reference's model sweeps a
+256x512 frame at, 64x128, B = 1 and 4, both entries) and `peaked` (the headline workload on the correlated feature
+variant) --, the `workloads` object and the `cpu_baseline`.  The --no-* options below drop pieces of a --full run.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32):
+depth.npy [B,H,W] whole and logp.npy, the log-DPV [B,D,H,W] at a fixed sample of pixels (see dump_outputs).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -21,6 +29,8 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
@@ -29,6 +39,8 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s
 # fp32 peak = this rate x 64 lanes x 2 flop x 2 packed components).  Rounds 1-3 divided by 2 clocks and under-reported valu_frac by 2x:
 # SQ_ACTIVE_INST_VALU of the same runs (one quad-cycle per VALU instruction) says 4.
 VALU_ISSUE_PEAK = 1024 * 2.4e9 / 4
+DUMP_LOGP_BYTES = 40 << 20   # --dump-outputs: the log-DPV sample stays under this, the whole dump under 64 MB
+DUMP_DEPTH_BYTES = 16 << 20  # the depth map is written whole up to this size, else at the log-DPV's sample of pixels
 
 
 def algorithmic_bytes_per_volume(C, V, D, H, W):
@@ -70,6 +82,24 @@ def cpu_baseline(cfg, budget_s=45.0, gpu_depth0=None):
                       f"{t_used:.0f} s of CPU work in total"}
 
 
+def dump_outputs(path, logp, depth):
+    """The outputs of the last timed step as path/<name>.npy, float32: logp.npy (log-DPV [B,D,H,W]) and depth.npy ([B,H,W]).
+    An array larger than its budget (DUMP_LOGP_BYTES, DUMP_DEPTH_BYTES) is written at P pixels of every map instead, [B,D,P]
+    or [B,P]: drawn without replacement by numpy's default_rng(0) from the H*W of a map, sorted, the same pixels in every
+    item and plane.  The sample depends on the shape only."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B, D, H, W = logp.shape
+    P = min(H * W, DUMP_LOGP_BYTES // (4 * B * D), DUMP_DEPTH_BYTES // (4 * B))
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(H * W, P, replace=False))).to(logp.device)
+    if 4 * logp.numel() > DUMP_LOGP_BYTES:
+        logp = logp.reshape(B, D, H * W)[:, :, idx]
+    if 4 * depth.numel() > DUMP_DEPTH_BYTES:
+        depth = depth.reshape(B, H * W)[:, idx]
+    np.save(os.path.join(path, "logp.npy"), logp.float().cpu().numpy())
+    np.save(os.path.join(path, "depth.npy"), depth.float().cpu().numpy())
+
+
 def self_launch(a):
     """--gpus N without a launcher: start N fresh ranks (one per GPU) BEFORE this process touches the GPU."""
     s = socket.socket()
@@ -95,15 +125,21 @@ def main():
     ap.add_argument("--algo", default="auto", choices=["auto", "direct", "dist", "corr", "tiled1", "tiled2", "cells", "mfma"],
                     help="corr / cells / mfma: lab builds of the library only (make LAB=1)")
     ap.add_argument("--peaked", action="store_true", help="SURVEY 8(d)'s correlated feature variant (src = 0.7 shift(ref) + 0.3 noise: a peaked DPV)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold-start measurement in front of the headline")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything besides the headline (cold start, gather-kernel "
+                    "cross-check, model_real, peaked, packed entry, workloads, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy "
+                    "(float32, under 64 MB: the log-DPV at a fixed sample of pixels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-cold", action="store_true", help="--full: skip the cold-start measurement in front of the headline")
     ap.add_argument("--preheat-ms", type=float, default=60.0, help="untimed headline steps in front of the W warm-up steps (clock ramp), ms of wall time")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the model_real / peaked measurements in front of the headline")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` object (BASELINE configs[2] and [4] at their per-GPU shard, behind the headline)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the model_real / peaked measurements in front of the headline")
+    ap.add_argument("--no-workloads", action="store_true", help="--full: skip the `workloads` object (BASELINE configs[2] and [4] at their per-GPU shard, behind the headline)")
     ap.add_argument("--config", default=None, help="an experiment file in the reference's JSON schema (configs/*.json): "
                     "planes, depth range, sigma, channels and the pose family come from it; the sweep resolution stays "
                     "--height x --width (BASELINE quotes the metric at 256x512)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))   # non-zero if any rank fails
@@ -166,7 +202,8 @@ def main():
             print("per-step ms: " + " ".join("%.4f" % ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps)), file=sys.stderr)
         return out, wall, kern_ms
 
-    # Order of the GPU work of this process, all of it reported in the line:
+    # Order of the GPU work of this process, all of it reported in the line (a plain run: the preheat and the headline of 4 only;
+    # --full: all of it):
     #   1. `cold_start`: the headline protocol -- W warm-up steps, K timed steps -- as the FIRST GPU work of the process.  From idle
     #      the GPU's clocks take ~20 ms of work to come up, more than the driver's 5 warm-up steps: these K steps run on rising clocks
     #      (PDEPTH_BENCH_TRACE=1 prints them: 0.59 ms falling to 0.47 in round 3).
@@ -179,21 +216,22 @@ def main():
     #      `peaked`: the headline call on SURVEY 8(d)'s correlated features (W + K steps).
     t_pre0 = time.perf_counter()
     cold = None
-    if not a.no_cold:
+    if a.full and not a.no_cold:
         _, _, cold_ms = timed(d["src"])
         cold = {"ms_per_step": cold_ms, "what": "the same W warm-up + K timed steps as the first GPU work of the process (clocks still rising)"}
     depth_gather = None
-    try:
-        depth_gather = ops.sweep_dpv(d["ref"], d["src"], d["K"], d["R"], d["t"], d["rays"], d["cxcy"], dc, sigma,
-                                     algo="direct", want_cost=False, want_logp=False, want_depth=True)[2]
-    except RuntimeError:
-        pass
+    if a.full:
+        try:
+            depth_gather = ops.sweep_dpv(d["ref"], d["src"], d["K"], d["R"], d["t"], d["rays"], d["cxcy"], dc, sigma,
+                                         algo="direct", want_cost=False, want_logp=False, want_depth=True)[2]
+        except RuntimeError:
+            pass
     # SURVEY 8(d), "Ambiguity resolved": the 64x128 model-real number is always reported next to the 256x512 one, and both the
     # N(0,1) and the peaked feature variants.  GPU time per call from HIP events over 50 back-to-back calls (the launch gaps of
     # the call are inside); launches per call: NCHW entry = statistics + pack + sweep + the gather kernel for routed items (its
     # blocks leave at once when none is), packed entry = the sweep.
     secondary = {}
-    if not a.no_secondary and a.algo in ("auto", "dist", "corr") and rank == 0 and not a.config:
+    if a.full and not a.no_secondary and a.algo in ("auto", "dist", "corr") and rank == 0 and not a.config:
         def small(Bs, entry):
             bs = synth.make_batch(2, Bs, C=cfg["C"], D=cfg["D"], H=64, W=128, V=cfg["V"], pose=a.pose)
             ds = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in bs.items()}
@@ -235,6 +273,9 @@ def main():
     # settle (PDEPTH_BENCH_TRACE=1 shows the steps falling by 10 %; profiles/r05_ab/bench_clock_ramp.txt); the headline's own W warm-up
     # steps are 2.5 ms.  60 ms of the headline step, untimed, declared in the line (`preheat`); `cold_start` is the number without it.
     pdist.barrier()   # (N > 1: rank 0 ran the secondary measurements above; every rank starts its preheat now, not a second before)
+    if cold is None:   # the first call loads the kernels and allocates the workspace: not part of the preheat's wall time
+        step(d["src"])
+        torch.cuda.synchronize(dev)
     t_h0 = time.perf_counter()
     while (time.perf_counter() - t_h0) * 1e3 < a.preheat_ms:
         for _ in range(8):
@@ -243,8 +284,10 @@ def main():
     preheat_ms = (time.perf_counter() - t_pre0) * 1e3
 
     out, wall, kern_ms = timed(d["src"])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out[1], out[2])
     packed_entry, out_p, kern_p = None, None, None
-    if a.algo in ("auto", "dist", "corr"):   # secondary: the same step on features already in the kernels' staging layout, right behind
+    if a.full and a.algo in ("auto", "dist", "corr"):   # secondary: the same step on features already in the kernels' staging layout, right behind
         try:
             ps = ops.pack_source(d["src"], cfg["D"], a.algo)
             out_p, _, kern_p = timed(ps)
@@ -274,7 +317,7 @@ def main():
     # entry (statistics + pack + sweep), HIP events around W + K calls; each checked against the gather kernel (the
     # reference's op order) on the same batch.
     workloads = {}
-    if not a.no_workloads and not a.no_secondary and a.algo in ("auto", "dist") and rank == 0 and not a.config:
+    if a.full and not a.no_workloads and not a.no_secondary and a.algo in ("auto", "dist") and rank == 0 and not a.config:
         def shard(name, Bs, D, H, W, V, pose, steps, offset=0.0, smooth=0):
             bs = synth.make_batch(2, Bs, C=cfg["C"], D=D, H=H, W=W, V=V, pose=pose)
             if smooth:   # spatially smooth features (box filter, unit variance again): what the trend guard looks at
@@ -378,7 +421,10 @@ def main():
             roof["valu_frac"] = prof["valu_wave_instr_per_launch"] / (kern_ms * 1e-3) / VALU_ISSUE_PEAK
             roof["valu_wave_instr_per_launch"] = prof["valu_wave_instr_per_launch"]
         extras = {"roofline": roof, "gather_fallback_tiles": fallback,
-                  "preheat_ms": preheat_ms, "preheat": "cold_start + preflight + model_real (see those objects) and %.0f ms of the headline step, untimed, ran before the headline's W warm-up steps; packed_entry and peaked right behind the headline" % a.preheat_ms}
+                  "preheat_ms": preheat_ms,
+                  "preheat": ("cold_start + preflight + model_real (see those objects) and %.0f ms of the headline step, untimed, ran before the headline's W warm-up steps; "
+                              "packed_entry and peaked right behind the headline" % a.preheat_ms) if a.full else
+                             ("one call (kernel load, workspace) and %.0f ms of the headline step, untimed, ran before the headline's W warm-up steps" % a.preheat_ms)}
         for k in ("model_real", "peaked"):
             if k in secondary:
                 extras[k] = secondary[k]
@@ -408,7 +454,7 @@ def main():
             # I/O and every sum in fp32; the default kernel forms the channel contraction from fp16 high / low pairs of the
             # centred features on the matrix pipe (22 bits per feature, products exact, fp32 accumulation: DESIGN.md section 1)
             dtype="f32 (fp16-pair products on MFMA, fp32 accumulate)" if impl == "dist" else "f32")
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # (with --config the depth candidates / sigma come from the file, the port's sample keeps the defaults: timing only)
             line["cpu_baseline"] = cpu_baseline(cfg, gpu_depth0=None if a.config else depth[0].cpu())
         print(json.dumps(line), flush=True)

@@ -113,7 +113,7 @@ def test_rccl_path_initialises_on_the_hardware():
     env2["PDEPTH_DIST_FORCE"] = "1"   # (a single rank would not open a process group otherwise)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29733", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-cold"], env=env2, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-cold"], env=env2, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["steps"] == 3 and line["value"] > 0 and line["scaling"] == "weak"

@@ -1,5 +1,5 @@
-"""CPU suite: the committed bench line of round 6 (profiles/r06_bench_line.json, `python bench.py --steps 20 --warmup 5` on a
-gpurun box) carries what VERDICT r5 asked of it: the two multi-GPU configs at one GPU's shard, the model-real figures, the
+"""CPU suite: the committed bench line of round 6 (profiles/r06_bench_line.json, `python bench.py --full --steps 20 --warmup 5` on an
+MI355X) carries what VERDICT r5 asked of it: the two multi-GPU configs at one GPU's shard, the model-real figures, the
 packed entry, a dtype that says what the products are."""
 import json
 import os
