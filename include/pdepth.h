@@ -54,7 +54,9 @@ extern "C" {
 
 #define PDEPTH_ABI_VERSION 6   /* 5: PDEPTH_ALGO_DIST (what AUTO runs), pdepth_sweep_source_layout, layout tag in the workspace;
                                 * 6: the distance-form layout is 320 bytes per texel at C = 67 (336 in v5): a workspace packed by a v5
-                                *    library must be re-packed; PDEPTH_ALGO_CORR answers in lab builds only */
+                                *    library must be re-packed; PDEPTH_ALGO_CORR answers in lab builds only;
+                                *    backward-compatible additions within 6: pdepth_sweep_backward_f32, pdepth_dpv_reduce_backward_f32,
+                                *    pdepth_dpv_expect_backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -374,6 +376,39 @@ int pdepth_inverse_warp_f32(const float *img, const float *depth, const float *K
 int pdepth_inverse_warp_backward_f32(const float *img, const float *depth, const float *Kinv, const float *proj,
                                      const float *grad_out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t mode,
                                      float *grad_img, float *grad_point, void *stream);
+
+/*
+ * Backward of the plane sweep with respect to the feature maps (what autograd does behind est_swp_volume_v4,
+ * warping/homography.py:98-135: F.grid_sample bilinear / zeros / align_corners=False at :170-198, img_dis_L2_pard /
+ * img_dis_L1_pard at :80-86, the division by sigma at :131-134; trained through losses/losses.py:80-88).
+ *   desc, cam, ref, src, d_candi as pdepth_sweep_cost_f32 (desc->metric selects L2 / L1; desc->algo is ignored: the
+ *   backward evaluates every plane directly in fp32 on the NCHW features, positions from the gather kernel's arithmetic);
+ *   grad_cost [B,D,H,W] contiguous;
+ *   grad_ref  [B,C,H,W] contiguous or NULL: a per-pixel gather, no atomics, bitwise reproducible;
+ *   grad_src  [B,V,C,H,W] contiguous or NULL: zeroed on the stream, then scattered with float atomics (summed per workgroup
+ *             in LDS first); the last bits depend on the order in which the adds arrive.
+ * At least one output must be non-NULL.  Taps outside the image receive nothing (ATen's grid_sampler_2d backward).
+ */
+int pdepth_sweep_backward_f32(const pdepth_sweep_desc *desc, const pdepth_camera *cam, const float *ref, const float *src,
+                              const float *d_candi, const float *grad_cost, float *grad_ref, float *grad_src, void *stream);
+
+/*
+ * Backward of pdepth_dpv_reduce_f32 / pdepth_dpv_reduce_ex_f32 (F.log_softmax(dim=1), models/models.py:560,637,694; exp,
+ * :697; dpv_to_depthmap(BV_log=True), utils/img_utils.py:52-61): from the saved logp [B,D,H,W] and any of
+ * g_logp [B,D,H,W], g_prob [B,D,H,W], g_depth [B,H,W] (NULL = zero; not all NULL):
+ *     G = g_logp + p (g_prob + g_depth d),  g_logits = G - p sum_k G_k,  p = exp(logp).
+ * g_logits [B,D,H,W] is also the gradient of the addend of pdepth_dpv_reduce_ex_f32.  g_logits may alias g_logp.
+ */
+int pdepth_dpv_reduce_backward_f32(const float *logp, const float *d_candi, int32_t B, int32_t D, int32_t H, int32_t W,
+                                   const float *g_logp, const float *g_prob, const float *g_depth, float *g_logits,
+                                   void *stream);
+
+/*
+ * Backward of pdepth_dpv_expect_f32 (dpv_to_depthmap, utils/img_utils.py:52-61):
+ *     g_dpv[b,k,y,x] = g_depth[b,y,x] d_k (bv_log ? exp(dpv[b,k,y,x]) : 1).
+ */
+int pdepth_dpv_expect_backward_f32(const float *dpv, const float *d_candi, int32_t B, int32_t D, int32_t H, int32_t W,
+                                   int32_t bv_log, const float *g_depth, float *g_dpv, void *stream);
 
 #ifdef __cplusplus
 }

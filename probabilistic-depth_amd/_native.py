@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "pdepth_ufield_workspace_bytes", "pdepth_ufield_f32",
     "pdepth_correlation_output_size", "pdepth_correlation_forward_f16", "pdepth_correlation_backward_f16",
     "pdepth_pack_views_f32", "pdepth_sweep_centres_source", "pdepth_sweep_source_layout",
+    "pdepth_sweep_backward_f32", "pdepth_dpv_reduce_backward_f32", "pdepth_dpv_expect_backward_f32",
 )
 
 
@@ -141,11 +142,15 @@ def load():
     lib.pdepth_correlation_output_size.argtypes = [c_int32] * 7 + [POINTER(c_int32)] * 3
     lib.pdepth_inverse_warp_f32.argtypes = [c_void_p] * 4 + [c_int32] * 5 + [c_void_p] * 3
     lib.pdepth_inverse_warp_backward_f32.argtypes = [c_void_p] * 5 + [c_int32] * 5 + [c_void_p] * 3
+    lib.pdepth_sweep_backward_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera)] + [c_void_p] * 7
+    lib.pdepth_dpv_reduce_backward_f32.argtypes = [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 5
+    lib.pdepth_dpv_expect_backward_f32.argtypes = [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p] * 3
     for fn in ("pdepth_sweep_cost_f32", "pdepth_sweep_dpv_f32", "pdepth_dpv_reduce_f32",
                "pdepth_dpv_expect_f32", "pdepth_warp_feature_f32", "pdepth_sample_coords_f32",
                "pdepth_dpv_fuse_f32", "pdepth_correlation_forward_f32", "pdepth_inverse_warp_f32",
                "pdepth_dpv_moments_f32", "pdepth_correlation_backward_f32", "pdepth_correlation_output_size",
-               "pdepth_correlation_forward_f16", "pdepth_correlation_backward_f16"):
+               "pdepth_correlation_forward_f16", "pdepth_correlation_backward_f16", "pdepth_sweep_backward_f32",
+               "pdepth_dpv_reduce_backward_f32", "pdepth_dpv_expect_backward_f32"):
         getattr(lib, fn).restype = c_int
     lib.pdepth_sweep_centres_source.restype = c_int
     lib.pdepth_sweep_centres_source.argtypes = [POINTER(SweepDesc)]
@@ -729,3 +734,94 @@ def inverse_warp_backward(img, depth, Kinv, proj, grad_out, mode="bilinear", wan
                                                   g_pt.data_ptr() if want_point else None, _stream(img.device))
     _check(rc, lib)
     return g_img, g_pt
+
+
+# ---- backward passes (ops.py wraps them in torch.autograd.Function) --------------------------------------------------------
+def _shape(t, shape, name, who):
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{who}: {name} must be {list(shape)}, got {list(t.shape)}")
+
+
+def sweep_backward(ref, src, K, R, t, rays, cxcy, d_candi, grad_cost, sigma, metric=METRIC_L2, want_ref=True, want_src=True,
+                   blas_mode=None):
+    """grad_cost [B,D,H,W] -> (grad_ref [B,C,H,W] | None, grad_src [B,V,C,H,W] | None): pdepth_sweep_backward_f32.
+    ref / src / camera as sweep() (NCHW source only).  grad_ref is reproducible bit for bit; grad_src is summed with float
+    atomics (last bits depend on the order of arrival)."""
+    who = "sweep_backward"
+    if not (want_ref or want_src):
+        raise RuntimeError(f"{who}: no output requested")
+    if ref.dim() != 4 or src.dim() != 5:
+        raise RuntimeError(f"{who}: ref must be [B,C,H,W] and src [B,V,C,H,W]")
+    B, C, H, W = ref.shape
+    V = src.shape[1]
+    _shape(src, (B, V, C, H, W), "src", who)
+    D = d_candi.numel()
+    if grad_cost.dim() != 4 or grad_cost.shape[1] != D:
+        raise RuntimeError(f"{who}: grad_cost has {grad_cost.shape[1] if grad_cost.dim() == 4 else '?'} planes, d_candi has {D} entries")
+    _shape(grad_cost, (B, D, H, W), "grad_cost", who)
+    lib = load()
+    _dev(ref, "ref"), _dev(src, "src"), _dev(grad_cost, "grad_cost"), _dev(d_candi, "d_candi")
+    ref, src, d_candi, grad_cost = ref.contiguous(), src.contiguous(), d_candi.contiguous(), grad_cost.contiguous()
+    cam, keep = _camera(K, R, t, rays, cxcy, B, V, H * W)
+    desc = SweepDesc(B, V, C, D, H, W, int(metric), ALGO_DIRECT, _blas(blas_mode), float(sigma), C * H * W, V * C * H * W, C * H * W)
+    g_ref = torch.empty_like(ref) if want_ref else None
+    g_src = torch.empty_like(src) if want_src else None
+    dev = ref.device
+    with _on_device(dev):
+        rc = lib.pdepth_sweep_backward_f32(ctypes.byref(desc), ctypes.byref(cam), ref.data_ptr(), src.data_ptr(), d_candi.data_ptr(),
+                                           grad_cost.data_ptr(), g_ref.data_ptr() if want_ref else None,
+                                           g_src.data_ptr() if want_src else None, _stream(dev))
+    _check(rc, lib)
+    del keep
+    return g_ref, g_src
+
+
+def dpv_reduce_backward(logp, d_candi, g_logp=None, g_prob=None, g_depth=None):
+    """Saved logp [B,D,H,W] + any of g_logp, g_prob [B,D,H,W], g_depth [B,H,W] -> g_logits [B,D,H,W]
+    (pdepth_dpv_reduce_backward_f32)."""
+    who = "dpv_reduce_backward"
+    if g_logp is None and g_prob is None and g_depth is None:
+        raise RuntimeError(f"{who}: no incoming gradient")
+    if logp.dim() != 4:
+        raise RuntimeError(f"{who}: logp must be [B,D,H,W]")
+    B, D, H, W = logp.shape
+    if d_candi.numel() != D:
+        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    for nm, g, shp in (("g_logp", g_logp, (B, D, H, W)), ("g_prob", g_prob, (B, D, H, W)), ("g_depth", g_depth, (B, H, W))):
+        if g is not None:
+            _shape(g, shp, nm, who)
+    lib = load()
+    _dev(logp, "logp"), _dev(d_candi, "d_candi")
+    logp, d_candi = logp.contiguous(), d_candi.contiguous()
+    gs = [None if g is None else g.contiguous().float() for g in (g_logp, g_prob, g_depth)]
+    for nm, g in zip(("g_logp", "g_prob", "g_depth"), gs):
+        if g is not None:
+            _dev(g, nm)
+    out = torch.empty_like(logp)
+    with _on_device(logp.device):
+        rc = lib.pdepth_dpv_reduce_backward_f32(logp.data_ptr(), d_candi.data_ptr(), B, D, H, W,
+                                                *[None if g is None else g.data_ptr() for g in gs], out.data_ptr(),
+                                                _stream(logp.device))
+    _check(rc, lib)
+    return out
+
+
+def dpv_expect_backward(dpv, d_candi, bv_log, g_depth):
+    """dpv [B,D,H,W], g_depth [B,H,W] -> g_dpv [B,D,H,W] (pdepth_dpv_expect_backward_f32)."""
+    who = "dpv_expect_backward"
+    if dpv.dim() != 4:
+        raise RuntimeError(f"{who}: dpv must be [B,D,H,W]")
+    B, D, H, W = dpv.shape
+    if d_candi.numel() != D:
+        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    _shape(g_depth, (B, H, W), "g_depth", who)
+    lib = load()
+    _dev(dpv, "dpv"), _dev(d_candi, "d_candi")
+    dpv, d_candi, g_depth = dpv.contiguous(), d_candi.contiguous(), g_depth.contiguous().float()
+    _dev(g_depth, "g_depth")
+    out = torch.empty_like(dpv)
+    with _on_device(dpv.device):
+        rc = lib.pdepth_dpv_expect_backward_f32(dpv.data_ptr(), d_candi.data_ptr(), B, D, H, W, int(bool(bv_log)), g_depth.data_ptr(),
+                                                out.data_ptr(), _stream(dpv.device))
+    _check(rc, lib)
+    return out

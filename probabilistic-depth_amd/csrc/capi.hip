@@ -492,4 +492,50 @@ int pdepth_inverse_warp_backward_f32(const float* img, const float* depth, const
                                                          grad_point, (hipStream_t)stream), "pdepth_inverse_warp_backward_f32");
 }
 
+// est_swp_volume_v4 backward (warping/homography.py:98-135, :170-198, :80-86), features only
+int pdepth_sweep_backward_f32(const pdepth_sweep_desc* desc, const pdepth_camera* cam, const float* ref, const float* src,
+                              const float* d_candi, const float* grad_cost, float* grad_ref, float* grad_src, void* stream) {
+    const char* who = "pdepth_sweep_backward_f32";
+    if (int rc = check_desc(desc, cam, who)) return rc;
+    if (!ref || !src || !d_candi || !grad_cost) return fail(PDEPTH_E_ARG, "%s: null input pointer", who);
+    if (!grad_ref && !grad_src) return fail(PDEPTH_E_ARG, "%s: no output requested", who);
+    if (desc->metric != PDEPTH_METRIC_L2 && desc->metric != PDEPTH_METRIC_L1)
+        return fail(PDEPTH_E_ARG, "%s: undefined metric for feature distance (%d)", who, desc->metric);
+    if (!(desc->sigma > 0.0f) && !(desc->sigma < 0.0f)) return fail(PDEPTH_E_ARG, "%s: sigma must be non-zero", who);
+    if (desc->D > 512) return fail(PDEPTH_E_ARG, "%s: D=%d exceeds the 512 planes one launch supports", who, desc->D);
+    if ((long long)desc->C * desc->H * desc->W >= (1ll << 31) || desc->B > 65535)
+        return fail(PDEPTH_E_ARG, "%s: C*H*W must be below 2^31 and B at most 65535", who);
+    if ((const void*)grad_ref == (const void*)grad_src || (const float*)grad_ref == ref || (const float*)grad_src == src ||
+        (const float*)grad_ref == grad_cost || (const float*)grad_src == grad_cost)
+        return fail(PDEPTH_E_ARG, "%s: the outputs may not alias each other or an input", who);
+    pdepth::SweepArgs a = make_args(desc, cam, ref, src, d_candi);
+    a.fast_div = 0;
+    return launched(pdepth::launch_sweep_backward(a, grad_cost, grad_ref, grad_src, (hipStream_t)stream), who);
+}
+
+// F.log_softmax(dim=1) + exp + dpv_to_depthmap(BV_log=True) backward (models/models.py:694, :697; utils/img_utils.py:52-61)
+int pdepth_dpv_reduce_backward_f32(const float* logp, const float* d_candi, int32_t B, int32_t D, int32_t H, int32_t W,
+                                   const float* g_logp, const float* g_prob, const float* g_depth, float* g_logits, void* stream) {
+    const char* who = "pdepth_dpv_reduce_backward_f32";
+    if (!logp || !d_candi || !g_logits) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
+    if (!g_logp && !g_prob && !g_depth) return fail(PDEPTH_E_ARG, "%s: no incoming gradient", who);
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+    if ((long long)H * W > (1ll << 30)) return fail(PDEPTH_E_ARG, "%s: H*W too large", who);
+    if ((const float*)g_logits == logp || (g_prob && (const float*)g_logits == g_prob))
+        return fail(PDEPTH_E_ARG, "%s: only g_logp may alias g_logits", who);
+    return launched(pdepth::launch_dpv_reduce_backward(logp, d_candi, B, D, H, W, g_logp, g_prob, g_depth, g_logits,
+                                                       (hipStream_t)stream), who);
+}
+
+// dpv_to_depthmap backward (utils/img_utils.py:52-61)
+int pdepth_dpv_expect_backward_f32(const float* dpv, const float* d_candi, int32_t B, int32_t D, int32_t H, int32_t W,
+                                   int32_t bv_log, const float* g_depth, float* g_dpv, void* stream) {
+    const char* who = "pdepth_dpv_expect_backward_f32";
+    if (!dpv || !d_candi || !g_depth || !g_dpv) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+    if ((long long)H * W > (1ll << 30)) return fail(PDEPTH_E_ARG, "%s: H*W too large", who);
+    if ((const float*)g_dpv == dpv || (const float*)g_dpv == g_depth) return fail(PDEPTH_E_ARG, "%s: g_dpv may not alias an input", who);
+    return launched(pdepth::launch_dpv_expect_backward(dpv, d_candi, B, D, H, W, bv_log, g_depth, g_dpv, (hipStream_t)stream), who);
+}
+
 }  // extern "C"

@@ -162,6 +162,17 @@ hipError_t launch_dpv_reduce_ex(const float* logits, const float* addend, const 
 hipError_t launch_dpv_expect(const float* dpv, const float* d_candi, int B, int D, int H, int W,
                              int bv_log, float* depth, hipStream_t stream);
 
+// dpv_bwd.hip: gradients of the reductions above with respect to their volume input (any of g_logp / g_prob / g_depth may be
+// nullptr, not all)
+hipError_t launch_dpv_reduce_backward(const float* logp, const float* d_candi, int B, int D, int H, int W, const float* g_logp,
+                                      const float* g_prob, const float* g_depth, float* g_logits, hipStream_t stream);
+hipError_t launch_dpv_expect_backward(const float* dpv, const float* d_candi, int B, int D, int H, int W, int bv_log,
+                                      const float* g_depth, float* g_dpv, hipStream_t stream);
+
+// sweep_bwd.hip: gradient of the cost volume with respect to the NCHW features (either output may be nullptr, not both;
+// grad_src [B,V,C,H,W] contiguous, zeroed by the launcher; grad_ref [B,C,H,W] contiguous)
+hipError_t launch_sweep_backward(const SweepArgs& a, const float* grad_cost, float* grad_ref, float* grad_src, hipStream_t stream);
+
 // warp.hip
 hipError_t launch_warp_feature(const SweepArgs& a, float* out, hipStream_t stream);
 hipError_t launch_sample_coords(const SweepArgs& a, float* ix, float* iy, hipStream_t stream);

@@ -236,9 +236,12 @@ class _SweepFeatures:
 
 
 class BaseModel(nn.Module):
-    """Inference-only host model: the sweep / warp / DPV ops are HIP kernels behind ctypes and are invisible to autograd
-    (they raise if an input requires grad while grad mode is on); wrap calls in torch.no_grad() as the reference's
-    evaluation loop does (trainer/default_trainer.py:171)."""
+    """Host model.  nmode "default" trains: with grad mode on, the sweep and the DPV reductions run through their HIP backward
+    passes (ops: gradients with respect to the feature maps and the volumes; the sweep then takes the concatenated NCHW
+    features), so forward + loss.backward() work as in the reference's training loop (trainer/default_trainer.py:87-169).
+    The other nmodes are inference-only: dpv_fuse ("default_upsample") and warp_feature ("default_feedback") have no
+    backward and raise if an input requires grad while grad mode is on; wrap those calls in torch.no_grad() as the
+    reference's evaluation loop does (trainer/default_trainer.py:171)."""
 
     def __init__(self, cfg, id):
         super().__init__()

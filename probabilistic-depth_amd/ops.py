@@ -53,6 +53,11 @@ def sweep_cost(ref, src, K, R, t, rays, cxcy, d_candi, sigma, feat_dist="L2", al
     blas: None = reproduce the rounding of THIS host's CPU BLAS (see _native.host_blas_mode),
     "fma" / "separate" to force one (golden fixtures record the mode of the host that made them).
     """
+    if _sweep_wants_grad("sweep_cost", ref, src, K, R, t, rays, cxcy, d_candi):
+        dc = d_candi_tensor(d_candi, ref.device)
+        cost, _, _ = _SweepFn.apply(ref, src, K, R, t, rays, cxcy, dc, sigma, _metric(feat_dist), ALGOS[algo], BLAS_MODES[blas],
+                                    True, False, False)
+        return cost
     cost, _, _ = _native.sweep(ref, src, K, R, t, rays, cxcy, d_candi_tensor(d_candi, ref.device), sigma,
                                _metric(feat_dist), ALGOS[algo], want_cost=True, blas_mode=BLAS_MODES[blas])
     return cost
@@ -64,6 +69,10 @@ def sweep_dpv(ref, src, K, R, t, rays, cxcy, d_candi, sigma, feat_dist="L2", alg
 
     models/packnet.py:380-394 + utils/img_utils.py:52-61 in one kernel.
     """
+    if _sweep_wants_grad("sweep_dpv", ref, src, K, R, t, rays, cxcy, d_candi):
+        dc = d_candi_tensor(d_candi, ref.device)
+        return _SweepFn.apply(ref, src, K, R, t, rays, cxcy, dc, sigma, _metric(feat_dist), ALGOS[algo], BLAS_MODES[blas],
+                              want_cost, want_logp, want_depth)
     return _native.sweep(ref, src, K, R, t, rays, cxcy, d_candi_tensor(d_candi, ref.device), sigma,
                          _metric(feat_dist), ALGOS[algo], want_cost=want_cost, want_logp=want_logp,
                          want_depth=want_depth, blas_mode=BLAS_MODES[blas])
@@ -98,6 +107,10 @@ def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
         dc = torch.zeros(logits.shape[1], dtype=torch.float32, device=logits.device)
     else:
         dc = d_candi_tensor(d_candi, logits.device)
+    if _wants_grad(logits):
+        _refuse_grad("dpv_reduce", d_candi=d_candi)
+        out = _DpvReduceFn.apply(logits, None, dc, want_logp, False, want_depth, False, False, False)
+        return out[0], out[2]
     return _native.dpv_reduce(logits, dc, want_logp, want_depth, inplace)
 
 
@@ -114,6 +127,10 @@ def dpv_reduce_ex(logits, d_candi=None, addend=None, want_logp=True, want_prob=F
         dc = torch.zeros(logits.shape[1], dtype=torch.float32, device=logits.device)
     else:
         dc = d_candi_tensor(d_candi, logits.device)
+    if _wants_grad(logits, addend):
+        _refuse_grad("dpv_reduce_ex", d_candi=d_candi)
+        out = _DpvReduceFn.apply(logits, addend, dc, want_logp, want_prob, want_depth, want_var, want_quarter, True)
+        return {k: v for k, v in zip(("logp", "prob", "depth", "var", "quarter"), out) if v is not None}
     return _native.dpv_reduce_ex(logits, dc, addend, want_logp, want_prob, want_depth, want_var, want_quarter, inplace)
 
 
@@ -134,6 +151,9 @@ def ufield(dpv, d_candi, intr, mask=None, BV_log=True, unc_ang=5, z_start=0.6, z
 
 def dpv_expect(dpv, d_candi, BV_log=False):
     """depth [B,H,W] from a (log-)DPV [B,D,H,W] (utils/img_utils.py:52-61, batched)."""
+    if _wants_grad(dpv):
+        _refuse_grad("dpv_expect", d_candi=d_candi)
+        return _DpvExpectFn.apply(dpv, d_candi_tensor(d_candi, dpv.device), bool(BV_log))
     return _native.dpv_expect(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
 
 
@@ -166,6 +186,110 @@ def dpv_fuse(logp, dmaps, masks, d_candi, var=0.3, eps=None, want_fused=True, wa
         masks = masks[:, 0]
     return _native.dpv_fuse(logp, dmaps.float(), masks.float(), d_candi_tensor(d_candi, logp.device), var, eps,
                             want_fused, want_log)
+
+
+# ---- autograd ---------------------------------------------------------------------------------------------------------------
+# The public functions above take the autograd path only when grad mode is on and a feature / volume input requires grad;
+# every other call runs the no-grad code unchanged.  The Functions' forwards call the same _native forwards (same algo), so
+# values are bit-identical to the no-grad call; their backwards are the HIP kernels of csrc/sweep_bwd.hip and csrc/dpv_bwd.hip.
+# Differentiable: the feature maps (ref, NCHW src), logits, addend, the DPV of dpv_expect.  Not differentiable: the geometry
+# (K, R, t, rays, cxcy, d_candi -- the reference's training takes them from the data loader), which is refused when it
+# requires grad.
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in tensors)
+
+
+def _refuse_grad(who, **named):
+    for name, x in named.items():
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{who}: {name} requires grad, but the HIP backward differentiates the feature maps / volumes only "
+                               f"(geometry and depth candidates are data); detach {name}")
+
+
+def _sweep_wants_grad(who, ref, src, K, R, t, rays, cxcy, d_candi):
+    """True if this sweep call runs under autograd; raises for inputs the backward cannot differentiate."""
+    if not torch.is_grad_enabled():
+        return False
+    _refuse_grad(who, K=K, R=R, t=t, rays=rays, cxcy=cxcy, d_candi=d_candi)
+    if isinstance(src, _native.PackedSource):
+        if isinstance(ref, torch.Tensor) and ref.requires_grad:
+            raise RuntimeError(f"{who}: ref requires grad, but src is a PackedSource: the staging layout has no fp32 source to "
+                               "differentiate; pass the NCHW features [B,V,C,H,W] as src")
+        return False
+    return _wants_grad(ref, src)
+
+
+class _SweepFn(torch.autograd.Function):
+    """sweep_cost / sweep_dpv under autograd: (cost | None, logp | None, depth | None) of the NCHW features.  logp is kept for
+    the backward whenever logp or depth is returned (computed by the same fused call when the caller did not ask for it)."""
+
+    @staticmethod
+    def forward(ctx, ref, src, K, R, t, rays, cxcy, dc, sigma, metric, algo, blas_mode, want_cost, want_logp, want_depth):
+        ctx.set_materialize_grads(False)
+        keep_logp = want_logp or want_depth
+        cost, logp, depth = _native.sweep(ref, src, K, R, t, rays, cxcy, dc, sigma, metric, algo, want_cost=want_cost,
+                                          want_logp=keep_logp, want_depth=want_depth, blas_mode=blas_mode)
+        ctx.save_for_backward(ref, src, K, R, t, rays, cxcy, dc, logp if keep_logp else None)
+        ctx.cfg = (sigma, metric, blas_mode)
+        return cost, (logp if want_logp else None), depth
+
+    @staticmethod
+    def backward(ctx, g_cost, g_logp, g_depth):
+        ref, src, K, R, t, rays, cxcy, dc, logp = ctx.saved_tensors
+        sigma, metric, blas_mode = ctx.cfg
+        g = None
+        if g_logp is not None or g_depth is not None:
+            g = _native.dpv_reduce_backward(logp, dc, g_logp=g_logp, g_depth=g_depth)
+        if g_cost is not None:
+            g = g_cost.float() if g is None else g + g_cost
+        want_ref, want_src = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g_ref = g_src = None
+        if g is not None and (want_ref or want_src):
+            g_ref, g_src = _native.sweep_backward(ref, src, K, R, t, rays, cxcy, dc, g, sigma, metric, want_ref=want_ref,
+                                                  want_src=want_src, blas_mode=blas_mode)
+        return (g_ref, g_src) + (None,) * 13
+
+
+class _DpvReduceFn(torch.autograd.Function):
+    """dpv_reduce / dpv_reduce_ex under autograd: (logp, prob, depth, var, quarter), each None unless requested; var and
+    quarter (the next frame's prev_output) are not differentiable.  inplace is not honoured: the outputs are new tensors."""
+
+    @staticmethod
+    def forward(ctx, logits, addend, dc, want_logp, want_prob, want_depth, want_var, want_quarter, ex):
+        ctx.set_materialize_grads(False)
+        if ex:   # (the forward of the public function that was called: dpv_reduce_ex or dpv_reduce)
+            out = _native.dpv_reduce_ex(logits, dc, addend, True, want_prob, want_depth, want_var, want_quarter, False)
+        else:
+            lp, dep = _native.dpv_reduce(logits, dc, True, want_depth, False)
+            out = {"logp": lp} if dep is None else {"logp": lp, "depth": dep}
+        logp = out["logp"]
+        ctx.save_for_backward(logp, dc)
+        nd = [out[k] for k in ("var", "quarter") if k in out]
+        if nd:
+            ctx.mark_non_differentiable(*nd)
+        return (logp if want_logp else None, out.get("prob"), out.get("depth"), out.get("var"), out.get("quarter"))
+
+    @staticmethod
+    def backward(ctx, g_logp, g_prob, g_depth, g_var, g_quarter):
+        logp, dc = ctx.saved_tensors
+        g = None
+        if g_logp is not None or g_prob is not None or g_depth is not None:
+            g = _native.dpv_reduce_backward(logp, dc, g_logp=g_logp, g_prob=g_prob, g_depth=g_depth)
+        return (g if ctx.needs_input_grad[0] else None, g if ctx.needs_input_grad[1] else None) + (None,) * 7
+
+
+class _DpvExpectFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dpv, dc, bv_log):
+        ctx.save_for_backward(dpv, dc)
+        ctx.bv_log = bv_log
+        return _native.dpv_expect(dpv, dc, bv_log)
+
+    @staticmethod
+    def backward(ctx, g_depth):
+        dpv, dc = ctx.saved_tensors
+        return _native.dpv_expect_backward(dpv, dc, ctx.bv_log, g_depth), None, None
 
 
 class _CorrelationFn(torch.autograd.Function):
