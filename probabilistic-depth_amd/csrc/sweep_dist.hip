@@ -97,6 +97,9 @@ struct __attribute__((aligned(16))) DistLds {
     int item[2];                 // work item: current / next
     int iflag;                   // the batch item in work: 1 = fp16 overflow in the pack, 2 = outside the domain (guard)
     unsigned char wide[64];      // per batch item: pixel blocks are 16x1 (else 8x2)
+#if DIST_ABL & 4
+    float abl_ray[4];            // (timing only) ray = (x ax + bx, y ay + by, 1), fitted to batch item 0's rays
+#endif
 };
 
 // NCHK = chunks of 32 channels (dist_layout.hpp); NH = groups of 64 planes (ceil(D / 64): 1 or 2), each a pass of its own per
@@ -131,6 +134,13 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     if (tid < 128) { L.ctab[0][tid] = (tid & 1) ? INT_MIN : INT_MAX; L.ctab[1][tid] = (tid & 1) ? INT_MIN : INT_MAX; }
     if (tid < 64) L.wide[tid] = 1;
     if (tid < 2) { L.ired[tid][0] = INT_MAX; L.ired[tid][1] = INT_MIN; }
+#if DIST_ABL & 4
+    if (tid == 0) {
+        const float* r = KARG(const float*, a.rays);
+        const int HW = KARG(int, a.H) * KARG(int, a.W), W = KARG(int, a.W);
+        L.abl_ray[0] = r[1] - r[0]; L.abl_ray[1] = r[0]; L.abl_ray[2] = r[HW + W] - r[HW]; L.abl_ray[3] = r[HW];
+    }
+#endif
     __syncthreads();
     // Shape of the pixel blocks of a batch item: 16x1 where the epipolar lines of view 0 run along the source rows (a
     // rectified pair: the 16 pixels of a row share two source rows), else 8x2 (pick.hpp; any choice is correct).
@@ -229,7 +239,8 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         for (int i = 0; i < slot * DIST_STAGGER; ++i) __builtin_amdgcn_s_sleep(100);
     }
     // loop-carried scalars of the kernel in ONE register: bit 0 = the slot of L.item in use, bit 1 = the set of row-table arrays of
-    // the pass (alternating), bits 2.. = 1 + the batch item whose tables (means, homography terms, camera constants) are in LDS
+    // the pass (alternating), bit 2 = the pixel inputs of the next item are on their way to the zone (below), bits 3.. = 1 + the
+    // batch item whose tables (means, homography terms, camera constants) are in LDS
     int state = 0;
     int n_direct = 0;     // (thread 0) pixel blocks evaluated directly
     // The queue runs one item ahead: (thread 0) the atomic that pops item i + 1 is issued when item i starts, its result is
@@ -248,11 +259,72 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             if (!ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
         }
     };
+    // Prefetch (DIST_PREFETCH).  A pixel block's own inputs -- its 16 rays and the reference features of its pixels -- were
+    // waited for in its positions and centring phases with nothing else in flight (profiles/r07_ab/: 7 % of the headline
+    // call).  Behind the LAST barrier of a block (every wave is done with its Q records) each wave moves exactly what it will
+    // read of the NEXT block's inputs into the zone -- L.Qs, dead until the next block's Q records arrive behind its first
+    // barrier -- by LDS-DMA (no registers in between, nothing for the compiler to wait for), ahead of the block's log-DPV
+    // stores.  The next block reads them back in front of its view loop behind a COUNTED wait: those stores are not waited for.
+    // Zone of wave w (floats from w ZW): component i of pixel n's ray at 16 i + n; at 64 + 128 mm + 16 c + n channel
+    // 32 mm + 8 w + c of pixel n (c < 8: the wave's channel pairs tq = 4 w + c / 2); the tail round (wave 0) from 4 ZW.
+    constexpr bool PF = DIST_PREFETCH && !(DIST_ABL & 4) && !DIST_ABL_NOB3;
+    constexpr int ZW = 64 + 128 * NCHK;
+    static_assert(4 * ZW + 128 <= (int)(sizeof(Lds::Qs) / sizeof(float)), "the prefetch zone does not fit L.Qs");
+    // A block that was not prefetched (a workgroup's first, every block of a workgroup-per-item launch, the block behind a skipped
+    // one) moves its inputs the same way at the top of its item and waits for them with vmcnt(0): nothing else is in flight then
+    // but its tables' loads.  (Registers loaded on one path and read from LDS on the other: the compiler waited out every
+    // outstanding store in front of the LDS reads, lest a late load overwrite them.)
+    // DMA lane (n, kq) of wave w: pixel n (p4 = its clamped byte offset in a plane); ray component kq (3: none) / channel
+    // 8 w + 4 j + kq of instruction j of a round.
+    auto dma_pixels = [&](int wave, int b, int p4) {
+        const int H = KARG(int, a.H), W = KARG(int, a.W), C = KARG(int, a.C), HW = H * W;
+        const int kq = (opaque_v((int)threadIdx.x) & 63) >> 4;
+        const __amdgpu_buffer_rsrc_t rray =
+            __builtin_amdgcn_make_buffer_rsrc((void*)(KARG(const float*, a.rays) + (size_t)b * 3 * HW), 0, 3 * HW * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rref = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(KARG(const float*, a.ref) + (size_t)b * KARG(long long, a.ref_bstride)), 0, C * HW * 4, 0x00020000);
+        dma_b32(rray, lds_addr_of(&L.Qs[wave * ZW]), kq < 3 ? kq * HW * 4 + p4 : OOB, 0);
+#pragma unroll
+        for (int mm = 0; mm < NCHK; ++mm)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int cr = 8 * wave + 4 * j + kq;   // (channel - 32 mm; beyond C: out of range, zero)
+                dma_b32(rref, lds_addr_of(&L.Qs[wave * ZW + 64 + 128 * mm + 64 * j]), cr < C - 32 * mm ? cr * HW * 4 + p4 : OOB, 32 * mm * HW * 4);
+            }
+        if (wave == 0) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int cr = 4 * j + kq;
+                dma_b32(rref, lds_addr_of(&L.Qs[4 * ZW + 64 * j]), cr < C - 32 * NCHK ? cr * HW * 4 + p4 : OOB, 32 * NCHK * HW * 4);
+            }
+        }
+    };
+    auto prefetch_next = [&](int wave) {   // (every thread, behind a workgroup barrier: the next item is in L.item)
+        const int nitem = __builtin_amdgcn_readfirstlane(L.item[state & 1]);
+        if (nitem < 0) return;
+        int b, tx, ty, sub;
+        decode(nitem, b, tx, ty, sub);
+        const int H = KARG(int, a.H), W = KARG(int, a.W);
+        const bool wide = b < 64 ? L.wide[b] != 0 : false;
+        if ((wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1)) >= H) return;   // (below the image: the item is skipped)
+        const int n = opaque_v((int)threadIdx.x) & 15;
+        const int x = wide ? tx * 16 + n : tx * 16 + 8 * (sub & 1) + (n & 7);
+        const int y = wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1) + (n >> 3);
+        dma_pixels(wave, b, (min(y, H - 1) * W + min(x, W - 1)) * 4);
+        state |= 4;
+    };
     if (tid == 0) {
         L.item[0] = ONE_EACH ? (got_own < items_of(xcd) ? (xcd << 28) | got_own : -1) : resolve(got_own);
         if (!ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
     }
     PDEPTH_LDS_BARRIER();   // the first item is published
+    // The queue pop returns into a register that is carried round the item loop, and the compiler's own wait for it at the
+    // loop's register copies is vmcnt(0) -- behind a block's log-DPV stores their whole latency, every block -- as soon as ONE
+    // path into the copies leaves the pop unwaited.  So every path waits for it by a wait the compiler sees (an explicit
+    // s_waitcnt; vmcnt(n) with n < 16, expcnt and lgkmcnt not waited for): the block's epilogue with the stores left in flight,
+    // the rare skipped blocks and the start with vmcnt(0).
+#define PDEPTH_POP_WAIT(n) __builtin_amdgcn_s_waitcnt(0x0f70 | (n))
+    PDEPTH_POP_WAIT(0);
 
     for (;;) {
         // (a plain LDS read: behind the barrier's memory clobber it cannot be hoisted.  Through a volatile generic pointer --
@@ -260,6 +332,8 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         //  previous pixel block's stores, 2 us per item)
         const int item = __builtin_amdgcn_readfirstlane(L.item[state & 1]);
         state ^= 1;
+        const int pf = state & 4;   // (the item's pixel inputs are on their way to the zone)
+        state ^= pf;
         if (item < 0) break;
         DSTAMP(0)   // queue
         const int wave = opaque_s(__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6));   // (per item: its multiples are not kept -- spilled -- across the kernel)
@@ -273,6 +347,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                 resolve_next();
                 publish_next();
                 PDEPTH_LDS_BARRIER();
+                PDEPTH_POP_WAIT(0);
                 continue;
             }
             // lane roles: in the vector phases thread (n, tq) owns pixel n of the block and planes 64 h + 4 tq .. + 3; in the
@@ -297,6 +372,17 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                 const int y = wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1) + (n >> 3);
                 xlive = x < W && y < H;
                 p = min(y, H - 1) * W + min(x, W - 1);
+                if (DIST_ABL & 4) {   // timing only: no pixel loads (how much of the kernel is their exposed latency?)
+#if DIST_ABL & 4
+                    const v4f ar = *reinterpret_cast<const v4f*>(L.abl_ray);
+                    ray[0] = __builtin_fmaf((float)min(x, W - 1), ar.x, ar.y); ray[1] = __builtin_fmaf((float)min(y, H - 1), ar.z, ar.w); ray[2] = 1.0f;
+#pragma unroll
+                    for (int mm = 0; mm < MP; ++mm)
+                        for (int i = 0; i < 2; ++i) rv[mm][i] = L.dcl[(32 * mm + 2 * tq + i + n) & 63];
+#endif
+                } else if (PF) {
+                    if (!pf) dma_pixels(wave, b, p * 4);   // (read back in front of the view loop)
+                } else {
 #pragma unroll
                 for (int i = 0; i < 3; ++i) ray[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rray, p * 4, i * HW * 4, 0));
 #pragma unroll
@@ -309,6 +395,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                         rv[mm][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                             rref, mine && 2 * tq + i < C - 32 * mm ? ((2 * tq + i) * HW + p) * 4 : OOB, 32 * mm * HW * 4, 0));
                 }
+                }
             }
             DSTAMP(1)   // item set-up, pixel loads issued
             // (the pixel loads above are in flight while the tables of a new batch item are built: where every workgroup runs ONE
@@ -316,9 +403,9 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             // per BATCH item, for every wave: scaled channel means, the views' homography terms, the camera constants, the item's
             // flags (visible behind the barrier in front of the first block's centring).  Items come out of the queues batch item
             // by batch item: the tables are rebuilt a few times per launch, not once per tile.
-            const bool new_b = b + 1 != state >> 2;
+            const bool new_b = b + 1 != state >> 3;
             if (new_b) {
-                state = (state & 3) | ((b + 1) << 2);
+                state = (state & 7) | ((b + 1) << 3);
                 // (the lane's roles re-derived here: hoisted out of the item loop, the invariants of this rarely run block were
                 //  spilled registers of the whole kernel)
                 const int tid = opaque_v((int)threadIdx.x), lane = tid & 63;
@@ -408,6 +495,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                     resolve_next();
                     publish_next();
                     PDEPTH_LDS_BARRIER();
+                    PDEPTH_POP_WAIT(0);
                     continue;
                 }
             }
@@ -417,6 +505,22 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             float cost[NC];
 #pragma unroll
             for (int j = 0; j < NC; ++j) cost[j] = 0.0f;
+            if (PF) {   // the inputs from the zone; a prefetched block's wait leaves the last block's log-DPV stores in flight
+                if (pf && (KARG(float*, a.logp_out) != nullptr || KARG(float*, a.depth_out) != nullptr)) {   // (NC log-DPV stores behind the DMA)
+                    if (NC == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                } else {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (no stores behind the DMA, or not prefetched)
+                }
+                const float* const z = &L.Qs[wave * ZW];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) ray[i] = z[16 * i + n];
+#pragma unroll
+                for (int mm = 0; mm < MP; ++mm)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        rv[mm][i] = mm < NCHK ? z[64 + 128 * mm + 16 * (2 * kq + i) + n] : (wave == 0 ? L.Qs[4 * ZW + 16 * (2 * kq + i) + n] : 0.0f);
+            }
 
             constexpr bool RETRY = NH == 2;   // (passes that do not fit are run again in halves: below)
             for (int v = 0; v < V; ++v) {
@@ -781,7 +885,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                 // features from the operand image in LDS.  An item whose features did not fit the fp16 range: NaN.
                 // (the shapes re-read here: kept from the top of the item for this rarely run block, they were spilled scalars)
                 const int H = KARG(int, a.H), W = KARG(int, a.W), V = KARG(int, a.V), C = KARG(int, a.C), D = KARG(int, a.D);
-                const int b = opaque_s((state >> 2) - 1);   // (the batch item in work)
+                const int b = opaque_s((state >> 3) - 1);   // (the batch item in work)
                 const v4f c0 = *reinterpret_cast<const v4f*>(&L.cst[0]), c1 = *reinterpret_cast<const v4f*>(&L.cst[4]);
                 const bool ovf = (L.iflag & 1) != 0;
                 (void)0;
@@ -903,8 +1007,14 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                         E = __builtin_fmaf(part[w].z, scw, E);
                     }
                     const float ls = logf(S_);
-                    if (logp_out) {
-                        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)(logp_out + (size_t)b * D * (HW4 >> 2)), 0, D * HW4, 0x00020000);
+                    // The next block's inputs, ahead of the stores below: they are the NC vector-memory instructions the next block's
+                    // counted wait leaves in flight (the depth store is not counted: a wave none of whose lanes store may skip it).
+                    // The pop is waited for first: behind the DMA, a wait for it would be one for the DMA as well.
+                    if (PF) { PDEPTH_POP_WAIT(0); prefetch_next(wave); }
+                    {   // (issued whether the caller asked for the log-DPV or not -- beyond an empty descriptor they are dropped --: NC
+                        //  stores behind the queue pop on every path, PDEPTH_POP_WAIT below)
+                        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(
+                            (void*)(logp_out ? logp_out + (size_t)b * D * (HW4 >> 2) : nullptr), 0, logp_out ? D * HW4 : 0, 0x00020000);
 #pragma unroll
                         for (int j = 0; j < NC; ++j)
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, (cost[j] - M) - ls), rl, ovoff,
@@ -912,13 +1022,17 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                     }
                     if (depth_out && xlive && tq == 0) depth_out[(size_t)b * (HW4 >> 2) + p] = E / S_;
                 }
+                if (!PF) PDEPTH_POP_WAIT(NC);   // (the pop, not the log-DPV stores)
             } else {
                 publish_next();
                 PDEPTH_LDS_BARRIER();   // (every wave is done with the block's operand image before the next block's centring)
+                PDEPTH_POP_WAIT(0);
+                if (PF) prefetch_next(wave);
             }
             DSTAMP(11)   // barrier + merge + stores
         }   // the pixel block
     }   // items
+#undef PDEPTH_POP_WAIT
 #ifdef DIST_STAMPS
     if ((threadIdx.x & 63) == 0)
         for (int i = 0; i < 12; ++i) atomicAdd(reinterpret_cast<unsigned long long*>(KARG(int*, queue) + 8) + i, stamp_acc[i]);

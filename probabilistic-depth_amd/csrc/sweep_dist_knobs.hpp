@@ -40,9 +40,13 @@
 #ifndef DIST_QSTRIDE
 #define DIST_QSTRIDE 64    // ints between the queue counters of two XCDs (1 -- all eight on one line, round 5 --: memory-side atomics on one line are served one by one, ~13 ns each)
 #endif
+#ifndef DIST_PREFETCH
+#define DIST_PREFETCH 0    // 1: the next pixel block's rays and reference features moved to LDS by LDS-DMA behind the last barrier of the current
+#endif                     //    one (bit-identical; headline 0.389 -> 0.407 ms: the second decode and the DMA issue cost more than the wait they hide;
+                           //    profiles/r07_ab/)
 #ifndef DIST_ABL
-#define DIST_ABL 0         // timing only (wrong results), bits: 1 = every sample position computed twice, 2 = no texel loads
-#endif
+#define DIST_ABL 0         // timing only (wrong results), bits: 1 = every sample position computed twice, 2 = no texel loads,
+#endif                     //    4 = no pixel loads (rays from a linear fit of batch item 0's, reference features from LDS constants)
 #ifndef DIST_ABL_NOB3
 #define DIST_ABL_NOB3 0    // timing only (wrong results): no barrier in front of the merge of the waves' softmax parts
 #endif

@@ -31,6 +31,12 @@ __device__ __forceinline__ void dma_b128(Rsrc rsrc, unsigned lds_addr, int voff,
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
                  :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
 }
+// ... 4 bytes per active lane, to m0 + 4 * lane (an offset beyond the descriptor writes zero)
+template <typename Rsrc>
+__device__ __forceinline__ void dma_b32(Rsrc rsrc, unsigned lds_addr, int voff, int soff) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
+                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
+}
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)p;
 }
