@@ -56,7 +56,8 @@ extern "C" {
                                 * 6: the distance-form layout is 320 bytes per texel at C = 67 (336 in v5): a workspace packed by a v5
                                 *    library must be re-packed; PDEPTH_ALGO_CORR answers in lab builds only;
                                 *    backward-compatible additions within 6: pdepth_sweep_backward_f32, pdepth_dpv_reduce_backward_f32,
-                                *    pdepth_dpv_expect_backward_f32 */
+                                *    pdepth_dpv_expect_backward_f32; pdepth_dpv_soft_ce_workspace_bytes, pdepth_dpv_soft_ce_f32,
+                                *    pdepth_dpv_soft_ce_backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -409,6 +410,44 @@ int pdepth_dpv_reduce_backward_f32(const float *logp, const float *d_candi, int3
  */
 int pdepth_dpv_expect_backward_f32(const float *dpv, const float *d_candi, int32_t B, int32_t D, int32_t H, int32_t W,
                                    int32_t bv_log, const float *g_depth, float *g_dpv, void *stream);
+
+/*
+ * Training loss on a log-DPV: soft-label cross-entropy over the depth axis, fused with the expectation, for the whole batch in
+ * one call (soft_cross_entropy_loss(BV_log=True), losses/loss_blocks.py:186-202, called per item and per side at
+ * losses/losses.py:32-67; dpv_to_depthmap(BV_log=True), utils/img_utils.py:52-61, called again at losses/losses.py:80-88).
+ *   logp     [B,D,H,W] contiguous fp32 log-probabilities; d_candi [D];
+ *   label    [B,D,H,W] contiguous soft label (the loader's soft_labels / soft_labels_imgsize), or NULL;
+ *   depth_gt [B,H,W] depth map, or NULL: the label is formed in the kernel as gen_soft_label_torch(d_candi, depth_gt, variance,
+ *            zero_invalid=True, pow) does (utils/img_utils.py:24-47; kittiloader/batch_scheduler.py:99-109):
+ *            g_d = exp(-|d_d - depth|^pow / (2 sqrt(variance)^pow)), label_d = g_d / sum_d g_d, and -1 on every plane of a pixel
+ *            whose sum is 0 or NaN.  No label tensor is read or written.  variance > 0, pow > 0 (2 in the reference);
+ *            exactly one of label / depth_gt is non-NULL;
+ *   mask     [B,H,W] or NULL.
+ *     ce[b,p]   = - sum_d label[b,d,p] logp[b,d,p]
+ *     loss[b]   = sum_p ce[b,p] mask[b,p] / count[b],   count[b] = #{p : mask[b,p] == 1}   (the weight is the mask's value, the
+ *                 count the number of entries equal to one, as in the reference); 0 where count[b] == 0; pixels whose mask is 0
+ *                 are skipped, not multiplied; without a mask the mean over all pixels, count[b] = H W
+ *     depth[b,p]= sum_d d_d exp(logp[b,d,p])   (depth NULL = not wanted): the bits of pdepth_dpv_expect_f32(bv_log = 1)
+ *   loss [B], count [B] (float).  The volume is read once.  The sum over pixels is reproducible bit for bit: one partial sum per
+ *   workgroup of 256 pixels in the workspace, added in a fixed order by a second launch -- no atomics.
+ *   workspace: pdepth_dpv_soft_ce_workspace_bytes(B, H, W) bytes (8 bytes per 256 pixels), 256-byte aligned.
+ */
+size_t pdepth_dpv_soft_ce_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_dpv_soft_ce_f32(const float *logp, const float *d_candi, const float *label, const float *depth_gt, float variance,
+                           float pow, const float *mask, int32_t B, int32_t D, int32_t H, int32_t W, float *loss, float *count,
+                           float *depth, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Backward of pdepth_dpv_soft_ce_f32 with respect to logp (what autograd does behind losses/loss_blocks.py:186-202 and
+ * utils/img_utils.py:52-61), one pass, one store per element:
+ *     g_logp[b,d,p] = - g_loss[b] mask[b,p] / count[b] label[b,d,p]        (0 where count[b] == 0 or mask[b,p] == 0)
+ *                   + g_depth[b,p] d_d exp(logp[b,d,p])                     (g_depth [B,H,W] or NULL = zero)
+ *   label / depth_gt / variance / pow / mask as in the forward (the label is formed again from depth_gt), count [B] from the
+ *   forward, g_loss [B] or NULL = zero (not both NULL).  The label, the mask, depth_gt and d_candi are data: no gradient.
+ */
+int pdepth_dpv_soft_ce_backward_f32(const float *logp, const float *d_candi, const float *label, const float *depth_gt,
+                                    float variance, float pow, const float *mask, const float *count, int32_t B, int32_t D,
+                                    int32_t H, int32_t W, const float *g_loss, const float *g_depth, float *g_logp, void *stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "pdepth_correlation_output_size", "pdepth_correlation_forward_f16", "pdepth_correlation_backward_f16",
     "pdepth_pack_views_f32", "pdepth_sweep_centres_source", "pdepth_sweep_source_layout",
     "pdepth_sweep_backward_f32", "pdepth_dpv_reduce_backward_f32", "pdepth_dpv_expect_backward_f32",
+    "pdepth_dpv_soft_ce_workspace_bytes", "pdepth_dpv_soft_ce_f32", "pdepth_dpv_soft_ce_backward_f32",
 )
 
 
@@ -145,6 +146,15 @@ def load():
     lib.pdepth_sweep_backward_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera)] + [c_void_p] * 7
     lib.pdepth_dpv_reduce_backward_f32.argtypes = [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 5
     lib.pdepth_dpv_expect_backward_f32.argtypes = [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p] * 3
+    # the loss entries live in their own object (csrc/loss.hip).  The product library must have them; an experiment library
+    # named by PDEPTH_LIB may be linked from a subset of the objects: it loads, and a loss call on it raises (_loss_entry)
+    if hasattr(lib, "pdepth_dpv_soft_ce_f32") or path == LIB_PATH:
+        lib.pdepth_dpv_soft_ce_workspace_bytes.restype = c_size_t
+        lib.pdepth_dpv_soft_ce_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+        lib.pdepth_dpv_soft_ce_f32.argtypes = [c_void_p] * 4 + [c_float, c_float, c_void_p] + [c_int32] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
+        lib.pdepth_dpv_soft_ce_backward_f32.argtypes = [c_void_p] * 4 + [c_float, c_float, c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 4
+        for fn in ("pdepth_dpv_soft_ce_f32", "pdepth_dpv_soft_ce_backward_f32"):
+            getattr(lib, fn).restype = c_int
     for fn in ("pdepth_sweep_cost_f32", "pdepth_sweep_dpv_f32", "pdepth_dpv_reduce_f32",
                "pdepth_dpv_expect_f32", "pdepth_warp_feature_f32", "pdepth_sample_coords_f32",
                "pdepth_dpv_fuse_f32", "pdepth_correlation_forward_f32", "pdepth_inverse_warp_f32",
@@ -823,5 +833,95 @@ def dpv_expect_backward(dpv, d_candi, bv_log, g_depth):
     with _on_device(dpv.device):
         rc = lib.pdepth_dpv_expect_backward_f32(dpv.data_ptr(), d_candi.data_ptr(), B, D, H, W, int(bool(bv_log)), g_depth.data_ptr(),
                                                 out.data_ptr(), _stream(dpv.device))
+    _check(rc, lib)
+    return out
+
+
+# ---- training loss (ops.dpv_soft_ce) ------------------------------------------------------------------------------------------
+def _soft_ce_args(who, logp, d_candi, label, depth_gt, variance, mask, pow):
+    """Shape checks (before any device check) and the contiguous fp32 tensors of the two cross-entropy entries."""
+    if logp.dim() != 4:
+        raise RuntimeError(f"{who}: logp must be [B,D,H,W]")
+    B, D, H, W = logp.shape
+    if d_candi.numel() != D:
+        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    if (label is None) == (depth_gt is None):
+        raise RuntimeError(f"{who}: give exactly one label source, label [B,D,H,W] or depth_gt [B,H,W]")
+    if label is not None:
+        _shape(label, (B, D, H, W), "label", who)
+    else:
+        _shape(depth_gt, (B, H, W), "depth_gt", who)
+        if variance is None or not float(variance) > 0.0:
+            raise RuntimeError(f"{who}: the from-depth form needs variance > 0")
+    if mask is not None:
+        _shape(mask, (B, H, W), "mask", who)
+    _dev(logp, "logp"), _dev(d_candi, "d_candi")
+    opt = []
+    for nm, t in (("label", label), ("depth_gt", depth_gt), ("mask", mask)):
+        if t is not None:
+            if not t.is_cuda:
+                raise RuntimeError(f"{nm}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+            t = t.contiguous().float()
+        opt.append(t)
+    var = float(variance) if depth_gt is not None else 0.0
+    return (B, D, H, W), logp.contiguous(), d_candi.contiguous(), opt[0], opt[1], opt[2], var, float(pow)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _loss_entry(lib, name):
+    """A loss entry of the loaded library; a library linked without csrc/loss.o is an error here, there is no other path."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{name}: the loaded library was linked without csrc/loss.hip; there is no fallback")
+    return fn
+
+
+def dpv_soft_ce(logp, d_candi, label=None, depth_gt=None, variance=None, mask=None, want_depth=False, pow=2.0):
+    """logp [B,D,H,W] + (label [B,D,H,W] | depth_gt [B,H,W], variance) [+ mask [B,H,W]] -> (loss [B], count [B], depth [B,H,W] |
+    None): pdepth_dpv_soft_ce_f32 on the current stream, no host synchronisation."""
+    who = "dpv_soft_ce"
+    lib = load()
+    _no_autograd(who, logp)
+    (B, D, H, W), logp, d_candi, label, depth_gt, mask, var, pw = _soft_ce_args(who, logp, d_candi, label, depth_gt, variance, mask, pow)
+    dev = logp.device
+    out = torch.empty((2, B), dtype=torch.float32, device=dev)
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
+    ws_bytes = _loss_entry(lib, "pdepth_dpv_soft_ce_workspace_bytes")(B, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _loss_entry(lib, "pdepth_dpv_soft_ce_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw, _ptr(mask),
+                                        B, D, H, W, out[0].data_ptr(), out[1].data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
+                                        _stream(dev))
+    _check(rc, lib)
+    return out[0], out[1], depth
+
+
+def dpv_soft_ce_backward(logp, d_candi, count, label=None, depth_gt=None, variance=None, mask=None, g_loss=None, g_depth=None,
+                         pow=2.0):
+    """-> g_logp [B,D,H,W] (pdepth_dpv_soft_ce_backward_f32); count [B] is the forward's."""
+    who = "dpv_soft_ce_backward"
+    if g_loss is None and g_depth is None:
+        raise RuntimeError(f"{who}: no incoming gradient")
+    (B, D, H, W), logp, d_candi, label, depth_gt, mask, var, pw = _soft_ce_args(who, logp, d_candi, label, depth_gt, variance, mask, pow)
+    _shape(count, (B,), "count", who)
+    if g_loss is not None:
+        _shape(g_loss, (B,), "g_loss", who)
+        g_loss = g_loss.contiguous().float()
+        _dev(g_loss, "g_loss")
+    if g_depth is not None:
+        _shape(g_depth, (B, H, W), "g_depth", who)
+        g_depth = g_depth.contiguous().float()
+        _dev(g_depth, "g_depth")
+    count = count.contiguous()
+    _dev(count, "count")
+    lib = load()
+    out = torch.empty_like(logp)
+    with _on_device(logp.device):
+        rc = _loss_entry(lib, "pdepth_dpv_soft_ce_backward_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw, _ptr(mask),
+                                                 count.data_ptr(), B, D, H, W, _ptr(g_loss), _ptr(g_depth), out.data_ptr(),
+                                                 _stream(logp.device))
     _check(rc, lib)
     return out

@@ -73,6 +73,13 @@ int sweep_impl() {
 #endif
 }
 
+}  // namespace
+
+// for C entries defined beside their kernels (loss.hip): the message pdepth_last_error() returns on this thread
+int pdepth::api_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
+namespace {
+
 int launched(hipError_t e, const char* who) {
     if (e != hipSuccess) return fail(PDEPTH_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
     return PDEPTH_OK;

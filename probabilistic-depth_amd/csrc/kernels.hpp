@@ -169,6 +169,19 @@ hipError_t launch_dpv_reduce_backward(const float* logp, const float* d_candi, i
 hipError_t launch_dpv_expect_backward(const float* dpv, const float* d_candi, int B, int D, int H, int W, int bv_log,
                                       const float* g_depth, float* g_dpv, hipStream_t stream);
 
+// capi.hip: sets the message pdepth_last_error() returns on this thread, returns code
+int api_error(int code, const char* msg);
+
+// loss.hip: soft-label cross-entropy (+ expectation) of a log-DPV, forward and backward.  Exactly one of label [B,D,H,W] /
+// depth_gt [B,H,W] is non-null; mask, depth, g_loss, g_depth may be nullptr
+size_t dpv_soft_ce_workspace_bytes(int B, int H, int W);
+hipError_t launch_dpv_soft_ce(const float* logp, const float* d_candi, const float* label, const float* depth_gt, float variance,
+                              float pw, const float* mask, int B, int D, int H, int W, float* loss, float* count, float* depth,
+                              void* workspace, hipStream_t stream);
+hipError_t launch_dpv_soft_ce_backward(const float* logp, const float* d_candi, const float* label, const float* depth_gt,
+                                       float variance, float pw, const float* mask, const float* count, int B, int D, int H, int W,
+                                       const float* g_loss, const float* g_depth, float* g_logp, hipStream_t stream);
+
 // sweep_bwd.hip: gradient of the cost volume with respect to the NCHW features (either output may be nullptr, not both;
 // grad_src [B,V,C,H,W] contiguous, zeroed by the launcher; grad_ref [B,C,H,W] contiguous)
 hipError_t launch_sweep_backward(const SweepArgs& a, const float* grad_cost, float* grad_ref, float* grad_src, hipStream_t stream);

@@ -1,0 +1,132 @@
+"""BaseLoss / DefaultLoss with the signature, the target keys and the weighting of the reference's losses/losses.py.
+
+BaseLoss.forward(output, target): output = (left, right) dicts with "output" / "output_refined" (lists of log-DPVs
+[B,D,h,w] / [B,D,H,W]); target = (left, right) dicts with soft_labels, soft_labels_imgsize (lists of [D,h,w] or tensors
+[B,D,h,w]), masks, masks_imgsizes [B,1,h,w], intrinsics, intrinsics_up [B,3,3], rgb [B,V,3,H,W], T_left2right [4,4],
+d_candi; cfg.loss.{ce,dsc,dc,rsc,rsc_low,smooth}_mul.
+
+Against the reference: every volume goes through ONE ops.dpv_soft_ce call for the whole batch (the reference walks items
+and sides in Python, losses.py:32-67), the depth maps of the last volumes come out of the same pass (the reference
+regresses them again, :80-88), an item without a valid pixel contributes 0 on the device, and nothing is read back to the
+host: no .item(), no truth test on a tensor, no host copy.  With labels_from_depth=True and dmaps / dmap_imgsizes in the
+target, the soft labels are formed inside the kernel from the depth maps (variance cfg.var.softce, prepared as the loader
+does: clamp(d_candi[0], d_candi[-1]) * mask, kittiloader/batch_scheduler.py:105-106) and soft_labels* may be absent.
+"""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+from .loss_blocks import (depth_consistency_loss, depth_stereo_consistency_loss, edge_aware_smoothness_loss,
+                          rgb_stereo_consistency_loss)
+
+
+def _stacked(labels):
+    return labels if isinstance(labels, torch.Tensor) else torch.stack(list(labels))
+
+
+class BaseLoss(nn.Module):
+    def __init__(self, cfg, id, labels_from_depth=False):
+        super().__init__()
+        self.cfg = cfg
+        self.id = id
+        self.labels_from_depth = labels_from_depth
+
+    def _cross_entropy(self, volumes, tgt, label_key, depth_key, mask_key, d_candi):
+        """(sum over the volumes and the items of the per-item cross-entropy, depth map [B,h,w] of the last volume)."""
+        mask = tgt[mask_key][:, 0]
+        src = {}
+        if self.labels_from_depth and depth_key in tgt:
+            src["depth_gt"] = tgt[depth_key].float().clamp(float(d_candi[0]), float(d_candi[-1])) * mask
+            src["variance"] = float(self.cfg.var.softce)
+        else:
+            src["label"] = _stacked(tgt[label_key])
+        total, depth = 0, None
+        for n, vol in enumerate(volumes):
+            loss, dm = ops.dpv_soft_ce(vol, d_candi, mask=mask, want_depth=(n == len(volumes) - 1), **src)
+            total = total + loss.sum()
+            depth = dm if dm is not None else depth
+        return total, depth
+
+    def forward(self, output, target):
+        out_l, out_r = output
+        tgt_l, tgt_r = target
+        mul = self.cfg.loss
+        device = out_l["output"][-1].device
+        d_candi = tgt_l["d_candi"]
+        B = out_l["output"][-1].shape[0]
+
+        # cross-entropy of every volume; the depth maps of the last low-resolution and refined volumes
+        ce_loss, ce_count = 0, 0
+        small, large = {}, {}
+        for side, out, tgt in (("l", out_l, tgt_l), ("r", out_r, tgt_r)):
+            lo, small[side] = self._cross_entropy(out["output"], tgt, "soft_labels", "dmaps", "masks", d_candi)
+            hi, large[side] = self._cross_entropy(out["output_refined"], tgt, "soft_labels_imgsize", "dmap_imgsizes",
+                                                  "masks_imgsizes", d_candi)
+            ce_loss = ce_loss + lo + hi
+        ce_count = (len(out_l["output"]) + len(out_l["output_refined"])) * B   # (left and right of an item count once)
+
+        # the pose between the two cameras and its inverse, inverted where it arrives (a CPU tensor from the loader)
+        T = tgt_l["T_left2right"].float()
+        T_inv = torch.inverse(T) if not T.is_cuda else torch.linalg.inv_ex(T).inverse
+        pose_l2r = T.unsqueeze(0).to(device, non_blocking=True)     # target = left, source = right
+        pose_r2l = T_inv.unsqueeze(0).to(device, non_blocking=True)
+
+        dc_loss = 0
+        if mul.dc_mul != 0:
+            dc_loss = (depth_consistency_loss(large["l"], small["l"], per_item=True).sum() +
+                       depth_consistency_loss(large["r"], small["r"], per_item=True).sum())
+
+        dsc_loss = 0
+        if mul.dsc_mul != 0:
+            for hi in (True, False):
+                dm = large if hi else small
+                mk = "masks_imgsizes" if hi else "masks"
+                ik = "intrinsics_up" if hi else "intrinsics"
+                dl, dr = dm["l"].unsqueeze(1), dm["r"].unsqueeze(1)
+                # right into left, then left into right
+                dsc_loss = dsc_loss + depth_stereo_consistency_loss(dr, dl, tgt_r[mk], tgt_l[mk], pose_l2r, tgt_l[ik],
+                                                                    pose_src2target=pose_r2l, per_item=True).sum()
+                dsc_loss = dsc_loss + depth_stereo_consistency_loss(dl, dr, tgt_l[mk], tgt_r[mk], pose_r2l, tgt_r[ik],
+                                                                    pose_src2target=pose_l2r, per_item=True).sum()
+
+        rgb_l, rgb_r = tgt_l["rgb"][:, -1], tgt_r["rgb"][:, -1]
+        rsc_loss = 0
+        if mul.rsc_mul != 0:
+            rsc_loss = (rgb_stereo_consistency_loss(rgb_r, rgb_l, large["l"], pose_l2r, tgt_l["intrinsics_up"], per_item=True).sum() +
+                        rgb_stereo_consistency_loss(rgb_l, rgb_r, large["r"], pose_r2l, tgt_r["intrinsics_up"], per_item=True).sum())
+
+        rsc_low_loss = 0
+        if mul.rsc_low_mul != 0:
+            low_l = F.interpolate(rgb_l, scale_factor=0.25, mode="bilinear")
+            low_r = F.interpolate(rgb_r, scale_factor=0.25, mode="bilinear")
+            rsc_low_loss = (rgb_stereo_consistency_loss(low_r, low_l, small["l"], pose_l2r, tgt_l["intrinsics"], per_item=True).sum() +
+                            rgb_stereo_consistency_loss(low_l, low_r, small["r"], pose_r2l, tgt_r["intrinsics"], per_item=True).sum())
+
+        smooth_loss = 0
+        if mul.smooth_mul != 0:   # (a mean over the batch times B = the sum of the per-item means)
+            smooth_loss = B * (edge_aware_smoothness_loss([large["l"].unsqueeze(1)], rgb_l, 1) +
+                               edge_aware_smoothness_loss([large["r"].unsqueeze(1)], rgb_r, 1))
+
+        loss = torch.zeros((), dtype=torch.float32, device=device)
+        bsize = float(2 * B)
+        if bsize != 0:
+            loss = loss + ((ce_loss / ce_count) * mul.ce_mul + (dsc_loss / bsize) * mul.dsc_mul + (dc_loss / bsize) * mul.dc_mul +
+                           (rsc_loss / bsize) * mul.rsc_mul + (rsc_low_loss / bsize) * mul.rsc_low_mul +
+                           (smooth_loss / bsize) * mul.smooth_mul)
+        return loss
+
+
+class DefaultLoss(nn.Module):
+    """The placeholder of the reference (losses/losses.py:212-239): the L1 norm of the last low-resolution volumes of both
+    sides, once per item of the batch."""
+
+    def __init__(self, cfg, id):
+        super().__init__()
+        self.cfg = cfg
+        self.id = id
+
+    def forward(self, output, target):
+        out_l, out_r = output
+        n = len(target[0]["soft_labels"])
+        return n * (out_l["output"][-1].abs().sum() + out_r["output"][-1].abs().sum())

@@ -157,6 +157,25 @@ def dpv_expect(dpv, d_candi, BV_log=False):
     return _native.dpv_expect(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
 
 
+def dpv_soft_ce(logp, d_candi, label=None, depth_gt=None, variance=None, mask=None, want_depth=False, pow=2.0):
+    """Soft-label cross-entropy of a log-DPV [B,D,H,W] over the depth axis, per item, fused with the expectation:
+    (loss [B], depth [B,H,W] | None).  soft_cross_entropy_loss(BV_log=True) for the whole batch (losses/loss_blocks.py:186-202)
+    + dpv_to_depthmap (utils/img_utils.py:52-61) in one pass over the volume.
+
+    The label is `label` [B,D,H,W] or, given `depth_gt` [B,H,W] and `variance`, what gen_soft_label_torch(d_candi, depth_gt,
+    variance, zero_invalid=True, pow) would build (utils/img_utils.py:24-47) -- formed in the kernel, never stored.
+    mask [B,H,W] | [B,1,H,W] | None: loss[b] = sum(ce * mask) / #(mask == 1), 0 for an item without a valid pixel (decided on
+    the device).  Differentiable with respect to logp only; depth equals dpv_expect(logp, d_candi, BV_log=True) bit for bit."""
+    if mask is not None and mask.dim() == 4:
+        mask = mask[:, 0]
+    dc = d_candi_tensor(d_candi, logp.device)
+    if _wants_grad(logp):
+        _refuse_grad("dpv_soft_ce", label=label, depth_gt=depth_gt, mask=mask, d_candi=d_candi)
+        return _DpvSoftCeFn.apply(logp, dc, label, depth_gt, variance, mask, bool(want_depth), float(pow))
+    loss, _, depth = _native.dpv_soft_ce(logp, dc, label, depth_gt, variance, mask, want_depth, pow)
+    return loss, depth
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
@@ -290,6 +309,26 @@ class _DpvExpectFn(torch.autograd.Function):
     def backward(ctx, g_depth):
         dpv, dc = ctx.saved_tensors
         return _native.dpv_expect_backward(dpv, dc, ctx.bv_log, g_depth), None, None
+
+
+class _DpvSoftCeFn(torch.autograd.Function):
+    """dpv_soft_ce under autograd: (loss, depth | None); the backward is one pass of csrc/loss.hip over the volume."""
+
+    @staticmethod
+    def forward(ctx, logp, dc, label, depth_gt, variance, mask, want_depth, pow):
+        ctx.set_materialize_grads(False)
+        loss, count, depth = _native.dpv_soft_ce(logp, dc, label, depth_gt, variance, mask, want_depth, pow)
+        ctx.save_for_backward(logp, dc, count, label, depth_gt, mask)
+        ctx.cfg = (variance, pow)
+        return loss, depth
+
+    @staticmethod
+    def backward(ctx, g_loss, g_depth):
+        logp, dc, count, label, depth_gt, mask = ctx.saved_tensors
+        g = None
+        if g_loss is not None or g_depth is not None:
+            g = _native.dpv_soft_ce_backward(logp, dc, count, label, depth_gt, ctx.cfg[0], mask, g_loss, g_depth, ctx.cfg[1])
+        return (g,) + (None,) * 7
 
 
 class _CorrelationFn(torch.autograd.Function):

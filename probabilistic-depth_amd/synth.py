@@ -157,6 +157,15 @@ def default_cfg(nmode="default", ndepth=64, feature_dim=64, model_name="base"):
                         "bn_avg": True, "d_min": 5.0, "d_max": 40.0, "qpower": 1.0}})
 
 
+def default_loss_cfg(nmode="default", ndepth=64, feature_dim=64, model_name="base", loss_name="base"):
+    """default_cfg plus what losses.get_loss reads: data.loss_name, var.softce and the loss multipliers of configs/default_mono.json."""
+    cfg = default_cfg(nmode, ndepth, feature_dim, model_name)
+    cfg.data["loss_name"] = loss_name
+    cfg.var["softce"] = 0.3
+    cfg["loss"] = Cfg({"ce_mul": 1.0, "dsc_mul": 1.0, "rsc_mul": 1.0, "smooth_mul": 0.5, "dc_mul": 0.25, "rsc_low_mul": 0.0})
+    return cfg
+
+
 HOT_PATH_VAR_KEYS = ("ndepth", "d_min", "d_max", "qpower", "sigma_soft_max", "feature_dim", "nmode")
 
 

@@ -1,5 +1,7 @@
 """Drop-in for the hot-path functions of the reference's utils/img_utils.py."""
 import numpy as np
+import torch
+import torch.nn.functional as F
 
 from .. import ops
 
@@ -9,6 +11,34 @@ def dpv_to_depthmap(dpv, d_candi, BV_log=False):
     if dpv.shape[0] != 1:
         raise Exception("Unable to handle this case")
     return ops.dpv_expect(dpv, d_candi, BV_log=BV_log)
+
+
+def gaussian_torch(x, mu, sig, pow=2.):
+    """exp(-|x - mu|^pow / (2 sig^pow)) (utils/img_utils.py:24-25); sig is a tensor."""
+    return torch.exp(-torch.pow(torch.abs(x - mu), pow) / (2 * torch.pow(sig, pow)))
+
+
+def gen_soft_label_torch(d_candi, depthmap, variance, zero_invalid=False, pow=2.):
+    """Soft label [D,H,W] of a depth map [H,W]: a Gaussian of variance `variance` (a tensor) around the depth, evaluated at the
+    candidates and normalised over them (utils/img_utils.py:31-47).  A pixel whose Gaussians all underflow divides 0 by 0:
+    NaN on every plane, or -1 with zero_invalid.  A torch composition for the data loader's side; the loss itself forms the
+    label inside its kernel (ops.dpv_soft_ce(depth_gt=...)) and needs no such tensor."""
+    planes = torch.as_tensor(np.asarray(d_candi), dtype=torch.float32).to(depthmap.device).reshape(-1, 1, 1)
+    dists = gaussian_torch(planes.expand(-1, depthmap.shape[0], depthmap.shape[1]), depthmap, torch.sqrt(variance), pow)
+    dists = dists / torch.sum(dists, dim=0)
+    if zero_invalid:
+        dists = torch.where(torch.isnan(dists), torch.full_like(dists, -1.0), dists)
+    return dists
+
+
+def minpool(tensor, scale, default=0):
+    """Minimum over scale x scale blocks (utils/img_utils.py:87-95); with `default`, zeros stand for "no value": they are
+    lifted to `default` before the pooling and blocks that held nothing else come back as 0."""
+    if default:
+        lifted = torch.where(tensor == 0, torch.full_like(tensor, default), tensor)
+        small = -F.max_pool2d(-lifted, scale)
+        return torch.where(small == default, torch.zeros_like(small), small)
+    return -F.max_pool2d(-tensor, scale)
 
 
 def powerf(d_min, d_max, nDepth, power):

@@ -101,7 +101,31 @@ def inverse_warp(img, depth, pose, intrinsics, mode="bilinear", rotation_mode="e
         raise RuntimeError("inverse_warp: pose must be [B,6] or [B,4,4]")
     intrinsics = intrinsics.float()
     proj = torch.matmul(intrinsics, pose_mat.float())
-    Kinv = intrinsics.inverse()
+    return warp_with_matrices(img, depth, intrinsics.inverse(), proj, mode)
+
+
+def warp_with_matrices(img, depth, Kinv, proj, mode="bilinear"):
+    """inverse_warp from the two matrices it derives: Kinv [B,3,3] = intrinsics^-1, proj [B,3,4] = intrinsics @ pose[:3].
+    For callers that form them without a host check (losses/: torch.inverse reads its status back from the device)."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (img, depth, Kinv, proj)):
         return _InverseWarpFn.apply(img.float(), depth.float(), Kinv, proj, mode)
     return _native.inverse_warp(img.float(), depth.float(), Kinv, proj, mode)
+
+
+def transform_dmap(depth_img, pose, intrinsics):
+    """Depth map [H,W] seen from another camera: every pixel is lifted to its 3-D point (depth clamped to 1e-3 from below),
+    moved by the 4x4 `pose`, and the new z is returned at the SAME pixel -- no resampling (utils/inverse_warp.py:212-253).
+    Differentiable with respect to the depth.  Also takes a batch: depth_img [B,H,W], intrinsics [B,3,3], pose [4,4] |
+    [1,4,4] | [B,4,4]."""
+    H, W = depth_img.shape[-2:]
+    fx, cx = intrinsics[..., 0, 0][..., None, None], intrinsics[..., 0, 2][..., None, None]
+    fy, cy = intrinsics[..., 1, 1][..., None, None], intrinsics[..., 1, 2][..., None, None]
+    ys, xs = torch.meshgrid(torch.arange(0, H, device=depth_img.device).float(), torch.arange(0, W, device=depth_img.device).float(),
+                            indexing="ij")
+    ys = (ys - cy) / fy
+    xs = (xs - cx) / fx
+    z = depth_img.clamp(min=1e-3)
+    cloud = torch.stack([xs * z, ys * z, z, torch.ones_like(z)], dim=-3)
+    moved = torch.matmul(pose, cloud.reshape(cloud.shape[:-2] + (H * W,)))
+    out = moved[..., 2, :]
+    return out.reshape(depth_img.shape) if out.numel() == depth_img.numel() else out.reshape(out.shape[:-1] + (H, W))
