@@ -54,7 +54,7 @@ extern "C" {
 
 #define PDEPTH_ABI_VERSION 6   /* 5: PDEPTH_ALGO_DIST (what AUTO runs), pdepth_sweep_source_layout, layout tag in the workspace;
                                 * 6: the distance-form layout is 320 bytes per texel at C = 67 (336 in v5): a workspace packed by a v5
-                                *    library must be re-packed; PDEPTH_ALGO_CORR answers in lab builds only;
+                                *    library must be re-packed; PDEPTH_ALGO_CORR is refused (PDEPTH_E_ARG; since retired with CELLS and MFMA);
                                 *    backward-compatible additions within 6: pdepth_sweep_backward_f32, pdepth_dpv_reduce_backward_f32,
                                 *    pdepth_dpv_expect_backward_f32; pdepth_dpv_soft_ce_workspace_bytes, pdepth_dpv_soft_ce_f32,
                                 *    pdepth_dpv_soft_ce_backward_f32 */
@@ -88,10 +88,10 @@ enum {
     /* implementation selectors (parity tests, A/B timing): what AUTO may pick, forced.  Same workspace as AUTO. */
     PDEPTH_ALGO_TILED_1 = 2, /* LDS-tiled band kernel, one 16x4 tile per block                          */
     PDEPTH_ALGO_TILED_2 = 3, /* LDS-tiled band kernel, two tiles per block (D <= 64)                    */
-    PDEPTH_ALGO_CELLS = 4,   /* lab builds only (make LAB=1): cell-list kernels of round 2 (L2, D <= 128)           */
-    PDEPTH_ALGO_MFMA = 5,    /* lab builds only: matrix-pipe kernel of round 3 (L2, D <= 128, C <= 72)              */
-    PDEPTH_ALGO_CORR = 6,    /* LAB BUILDS ONLY since ABI 6 (PDEPTH_E_ARG otherwise): correlation form on mean-centred features, fp32 matrix instructions (L2 metric, D <= 128,
-                                C <= 72; other inputs: PDEPTH_E_ARG): the default of ABI 4, kept as an independent check */
+    /* retired values: the numbers stay reserved, a descriptor that names one is refused with PDEPTH_E_ARG */
+    PDEPTH_ALGO_CELLS = 4,   /* RETIRED: cell-list kernels of round 2                                               */
+    PDEPTH_ALGO_MFMA = 5,    /* RETIRED: fp32 matrix-pipe kernel of round 3                                         */
+    PDEPTH_ALGO_CORR = 6,    /* RETIRED: correlation form on mean-centred features (the default of ABI 4)           */
     PDEPTH_ALGO_DIST = 7     /* distance form sum_t w_t |s_t - r|^2 - Q on fp16 high / low parts, matrix pipe (L2 metric,
                                 D <= 128, C <= 72, V <= 8; other inputs: PDEPTH_E_ARG): what AUTO runs on those shapes  */
 };
@@ -100,7 +100,7 @@ enum {
 enum {
     PDEPTH_LAYOUT_NONE = 0,        /* the descriptor does not run on a packed source                                   */
     PDEPTH_LAYOUT_C4 = 1,          /* channel-group-planar float4 + Gram planes (LDS-tiled kernel)                     */
-    PDEPTH_LAYOUT_C4_CENTRED = 2,  /* the same on mean-centred features (PDEPTH_ALGO_CORR)                             */
+    PDEPTH_LAYOUT_C4_CENTRED = 2,  /* RETIRED (was PDEPTH_ALGO_CORR's): the number stays reserved, no descriptor selects it */
     PDEPTH_LAYOUT_DIST16 = 3       /* fp16 high / low planes in matrix-operand order + neighbour differences, ring of
                                       zero-feature texels (PDEPTH_ALGO_DIST; csrc/dist_layout.hpp)                     */
 };
@@ -218,7 +218,7 @@ size_t pdepth_sweep_workspace_bytes(const pdepth_sweep_desc *desc);
 
 /* 1 if the packing entry points (pdepth_pack_source_f32, pdepth_pack_views_f32) subtract the channel means from the
  * packed source for `desc` -- i.e. the sweep it selects is the distance-form kernel (PDEPTH_ALGO_DIST, directly or through
- * PDEPTH_ALGO_AUTO; lab builds: also PDEPTH_ALGO_CORR) --, else 0.  A packed workspace must be swept with a descriptor for which this answer is the same (the centred and the
+ * PDEPTH_ALGO_AUTO) --, else 0.  A packed workspace must be swept with a descriptor for which this answer is the same (the centred and the
  * plain layout differ; the library cannot tell them apart from the host).  No reference counterpart: the reference
  * never re-lays its features (warping/homography.py:123-129 works on the NCHW tensors). */
 int pdepth_sweep_centres_source(const pdepth_sweep_desc *desc);

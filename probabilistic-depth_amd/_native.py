@@ -18,7 +18,9 @@ LIB_PATH = os.path.join(_HERE, "libpdepth_hip.so")
 
 METRIC_L2, METRIC_L1 = 0, 1
 ALGO_AUTO, ALGO_DIRECT, ALGO_TILED_1, ALGO_TILED_2, ALGO_CELLS, ALGO_MFMA, ALGO_CORR, ALGO_DIST = 0, 1, 2, 3, 4, 5, 6, 7
-LAYOUT_NONE, LAYOUT_C4, LAYOUT_C4_CENTRED, LAYOUT_DIST16 = 0, 1, 2, 3
+LAYOUT_NONE, LAYOUT_C4, LAYOUT_DIST16 = 0, 1, 3   # (2: a retired layout; pdepth_sweep_source_layout never answers it)
+# workspace ints behind the tile flags that the diagnostics below read (csrc/kernels.hpp; tests/test_capi_symbols.py compares them)
+NONCENTRED_SLOT, LAYOUT_SLOT, DIST_DIRECT_LAST_SLOT, DIST_NONCE_SLOT = 51, 56, 59, 60
 BLAS_FMA, BLAS_SEPARATE = 0, 1
 
 # every symbol include/pdepth.h declares (tests check the library exports all of them)
@@ -99,7 +101,7 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    # experiments only (tools/variants_cells.sh): PDEPTH_LIB points at a library built with other kernel knobs
+    # experiments only (tools/variants_dist.sh): PDEPTH_LIB points at a library built with other kernel knobs
     path = os.environ.get("PDEPTH_LIB") or LIB_PATH
     if not os.path.exists(path):
         raise RuntimeError(
@@ -259,10 +261,10 @@ def _blas(blas_mode):
 
 
 def selected_kernel(B, V, C, D, H, W, metric=METRIC_L2, algo=ALGO_AUTO):
-    """Name of the sweep kernel family a descriptor selects ('dist' | 'corr' | 'tiled' | 'direct'): pdepth_sweep_source_layout."""
+    """Name of the sweep kernel family a descriptor selects ('dist' | 'tiled' | 'direct'): pdepth_sweep_source_layout."""
     lib = load()
     desc = SweepDesc(B, V, C, D, H, W, int(metric), int(algo), BLAS_FMA, 1.0, C * H * W, V * C * H * W, C * H * W)
-    return {LAYOUT_DIST16: "dist", LAYOUT_C4_CENTRED: "corr", LAYOUT_C4: "tiled"}.get(lib.pdepth_sweep_source_layout(ctypes.byref(desc)), "direct")
+    return {LAYOUT_DIST16: "dist", LAYOUT_C4: "tiled"}.get(lib.pdepth_sweep_source_layout(ctypes.byref(desc)), "direct")
 
 
 class PackedSource:
@@ -277,12 +279,12 @@ class PackedSource:
     @property
     def centred(self):
         """The channel means were subtracted (pdepth_sweep_centres_source)."""
-        return self.layout in (LAYOUT_C4_CENTRED, LAYOUT_DIST16)
+        return self.layout == LAYOUT_DIST16
 
 
 def pack_source(src, n_planes=64, algo=ALGO_AUTO, metric=METRIC_L2):
     """src [B,V,C,H,W] fp32 device tensor -> PackedSource (n_planes and algo only select the kernel that will sweep it, like
-    desc.D and desc.algo: the layout the correlation-form kernel takes is mean-centred, the LDS-tiled kernel's is not)."""
+    desc.D and desc.algo: the layout the distance-form kernel takes is mean-centred, the LDS-tiled kernel's is not)."""
     lib = load()
     _no_autograd("pack_source", src)
     _dev(src, "src")
@@ -416,24 +418,21 @@ def _queue_slot(B, H, W, slot):
 def noncentred_guard(B, H, W):
     """Diagnostics: did the pre-pass of the last sweep on a NOT centred source (LDS-tiled kernel) find channel offsets larger
     than the spread of the features -- the tiled kernel then evaluated every plane directly (csrc/sweep_pack.hip)."""
-    return None if _last_workspace is None else _queue_slot(B, H, W, 51) != 0
+    return None if _last_workspace is None else _queue_slot(B, H, W, NONCENTRED_SLOT) != 0
 
 
 def fallback_tiles(B, H, W, gather_flag=1):
     """Diagnostics: how much of the last sweep left the fast path.  After the distance-form kernel (ALGO_AUTO / 'dist' on its
-    shapes) or the correlation-form kernel ('corr'): passes over a block of 16 pixels they evaluated directly (the kernel
-    that ran zeroes its own count per call; the other's count stays at what its last call left); after the LDS-tiled
-    kernel: 16x4 tiles left to the gather kernel (flag 1; lab builds: the cell-list path flags 1 = redone by its generic
-    kernel, 2 = gather kernel)."""
+    shapes): passes over a block of 16 pixels it evaluated directly (the kernel zeroes its count per call); after the
+    LDS-tiled kernel: 16x4 tiles left to the gather kernel.  gather_flag: the tile-flag value counted (the gather kernel's
+    is 1)."""
     if _last_workspace is None:
         return 0
     n = B * ((W + 15) // 16) * ((H + 3) // 4)
-    layout = _queue_slot(B, H, W, 56)
-    if layout == LAYOUT_DIST16:   # (nonce << 20) | count; a count tagged by another call's nonce is stale (kernels.hpp: DIST_NONCE_SLOT)
-        tagged, nonce = _queue_slot(B, H, W, 59), _queue_slot(B, H, W, 60)
+    direct = 0
+    if _queue_slot(B, H, W, LAYOUT_SLOT) == LAYOUT_DIST16:   # (nonce << 20) | count; a count tagged by another call's nonce is stale (kernels.hpp: DIST_NONCE_SLOT)
+        tagged, nonce = _queue_slot(B, H, W, DIST_DIRECT_LAST_SLOT), _queue_slot(B, H, W, DIST_NONCE_SLOT)
         direct = (tagged & 0xFFFFF) if nonce != 0 and (tagged >> 20) == nonce else 0
-    else:
-        direct = _queue_slot(B, H, W, 54) if layout == LAYOUT_C4_CENTRED else 0
     return int((_last_workspace[: 4 * n].view(torch.int32) == gather_flag).sum().item()) + direct
 
 

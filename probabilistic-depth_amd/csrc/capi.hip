@@ -4,7 +4,6 @@
 
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 
 #include "../../include/pdepth.h"
 #include "kernels.hpp"
@@ -51,28 +50,6 @@ pdepth::SweepArgs make_args(const pdepth_sweep_desc* d, const pdepth_camera* cam
     return a;
 }
 
-// Implementation behind ALGO_AUTO.  L2 metric, C <= 72, D <= 128, at most 8 views: the distance-form kernel on the matrix
-// pipe (sweep_dist.hip).  Everything else that fits a packed layout (L1 has no such form; wider features; more planes): the
-// LDS-tiled kernel (sweep_tiled.hip).  Lab builds (-DPDEPTH_LAB) read PDEPTH_SWEEP_IMPL once per process to put another
-// implementation behind AUTO for A/B timing: corr | tiled | mfma | cells (the kernels of earlier rounds, kept as
-// independent checks); the product library has no such switch.
-enum { IMPL_DEFAULT = 0, IMPL_CELLS = 1, IMPL_TILED = 2, IMPL_MFMA = 3, IMPL_CORR = 4 };
-int sweep_impl() {
-#ifdef PDEPTH_LAB
-    static const int impl = [] {
-        const char* f = getenv("PDEPTH_SWEEP_IMPL");
-        if (!f) return (int)IMPL_DEFAULT;
-        if (f[0] == 'c' && f[1] == 'e') return (int)IMPL_CELLS;
-        if (f[0] == 'c' && f[1] == 'o') return (int)IMPL_CORR;
-        if (f[0] == 'm') return (int)IMPL_MFMA;
-        return f[0] == 't' ? (int)IMPL_TILED : (int)IMPL_DEFAULT;
-    }();
-    return impl;
-#else
-    return IMPL_DEFAULT;
-#endif
-}
-
 }  // namespace
 
 // for C entries defined beside their kernels (loss.hip): the message pdepth_last_error() returns on this thread
@@ -108,25 +85,16 @@ pdepth::SweepArgs shape_args(const pdepth_sweep_desc* d) {
 //   distance form (sweep_dist.hip; layout dist_layout.hpp): what AUTO runs for L2, D <= 128, C <= 72, V <= 8
 bool uses_dist(const pdepth_sweep_desc* d) {
     if (!uses_packed_source(d) || d->metric != PDEPTH_METRIC_L2) return false;
-    if (d->algo != PDEPTH_ALGO_DIST && !(d->algo == PDEPTH_ALGO_AUTO && sweep_impl() == IMPL_DEFAULT)) return false;
+    if (d->algo != PDEPTH_ALGO_DIST && d->algo != PDEPTH_ALGO_AUTO) return false;
     return pdepth::sweep_dist_supports(shape_args(d));
 }
-//   correlation form on mean-centred features (sweep_corr.hip; centred channel-group-planar layout): on request
-//   (round 4's default; since round 6 in lab builds only -- make LAB=1 --, like the cell-list and first matrix-pipe kernels)
-bool uses_corr(const pdepth_sweep_desc* d) {
-#ifndef PDEPTH_LAB
-    (void)d;
-    return false;
-#else
-    if (!uses_packed_source(d) || d->metric != PDEPTH_METRIC_L2) return false;
-    if (d->algo != PDEPTH_ALGO_CORR && !(d->algo == PDEPTH_ALGO_AUTO && sweep_impl() == IMPL_CORR)) return false;
-    return pdepth::sweep_corr_supports(shape_args(d));
-#endif
-}
+//   LDS-tiled kernel (sweep_tiled.hip; channel-group-planar layout): every other shape that fits a packed layout (L1 has no
+//   distance form; wider features; more planes), and TILED_1 / TILED_2 on request
+//   gather kernel (sweep_direct.hip; no packed source): ALGO_DIRECT and the shapes beyond the packed layouts
 int source_layout(const pdepth_sweep_desc* d) {
     if (!uses_packed_source(d)) return PDEPTH_LAYOUT_NONE;
     if (uses_dist(d)) return PDEPTH_LAYOUT_DIST16;
-    return uses_corr(d) ? PDEPTH_LAYOUT_C4_CENTRED : PDEPTH_LAYOUT_C4;
+    return PDEPTH_LAYOUT_C4;
 }
 
 // packed_ready: src is NULL and the workspace already holds the packed source (pdepth_pack_source_f32)
@@ -142,20 +110,8 @@ int sweep_common(const pdepth_sweep_desc* d, const pdepth_camera* cam, const flo
         return fail(PDEPTH_E_ARG, "%s: undefined metric for feature distance (%d)", who, d->metric);
     if (d->algo < PDEPTH_ALGO_AUTO || d->algo > PDEPTH_ALGO_DIST)
         return fail(PDEPTH_E_ARG, "%s: unknown algo %d", who, d->algo);
-#ifdef PDEPTH_LAB
-    if (d->algo == PDEPTH_ALGO_CELLS && (d->metric != PDEPTH_METRIC_L2 || d->D > pdepth::sweep_cells_max_planes()))
-        return fail(PDEPTH_E_ARG, "%s: PDEPTH_ALGO_CELLS needs the L2 metric and D <= %d", who, pdepth::sweep_cells_max_planes());
-    if (d->algo == PDEPTH_ALGO_MFMA) {
-        const pdepth::SweepArgs probe = make_args(d, cam, ref, src, d_candi);
-        if (!pdepth::sweep_mfma_supports(probe))
-            return fail(PDEPTH_E_ARG, "%s: PDEPTH_ALGO_MFMA needs the L2 metric, D <= 128 and C <= 72", who);
-    }
-#else
     if (d->algo == PDEPTH_ALGO_CELLS || d->algo == PDEPTH_ALGO_MFMA || d->algo == PDEPTH_ALGO_CORR)
-        return fail(PDEPTH_E_ARG, "%s: PDEPTH_ALGO_CELLS / PDEPTH_ALGO_MFMA / PDEPTH_ALGO_CORR exist in lab builds only (make LAB=1)", who);
-#endif
-    if (d->algo == PDEPTH_ALGO_CORR && !uses_corr(d))
-        return fail(PDEPTH_E_ARG, "%s: PDEPTH_ALGO_CORR needs the L2 metric, D <= 128 and C <= 72", who);
+        return fail(PDEPTH_E_ARG, "%s: PDEPTH_ALGO_CELLS / PDEPTH_ALGO_MFMA / PDEPTH_ALGO_CORR are retired (the values stay reserved)", who);
     if (d->algo == PDEPTH_ALGO_DIST && !uses_dist(d))
         return fail(PDEPTH_E_ARG, "%s: PDEPTH_ALGO_DIST needs the L2 metric, D <= 128, C <= 72 and at most 8 source views", who);
     if (d->algo == PDEPTH_ALGO_TILED_2 && d->D > 64)
@@ -183,14 +139,6 @@ int sweep_common(const pdepth_sweep_desc* d, const pdepth_camera* cam, const flo
         if (d->algo == PDEPTH_ALGO_TILED_2)
             return launched(pdepth::launch_sweep_tiled_n2(a, workspace, (hipStream_t)stream, packed_ready), who);
         if (uses_dist(d)) return launched(pdepth::launch_sweep_dist(a, workspace, (hipStream_t)stream, packed_ready), who);
-#ifdef PDEPTH_LAB
-        if (uses_corr(d)) return launched(pdepth::launch_sweep_corr(a, workspace, (hipStream_t)stream, packed_ready), who);
-        if (d->algo == PDEPTH_ALGO_MFMA || (d->algo == PDEPTH_ALGO_AUTO && sweep_impl() == IMPL_MFMA && pdepth::sweep_mfma_supports(a)))
-            return launched(pdepth::launch_sweep_mfma(a, workspace, (hipStream_t)stream, packed_ready), who);
-        if (d->algo == PDEPTH_ALGO_CELLS || (d->algo == PDEPTH_ALGO_AUTO && d->metric == PDEPTH_METRIC_L2 &&
-                                             d->D <= pdepth::sweep_cells_max_planes() && sweep_impl() == IMPL_CELLS))
-            return launched(pdepth::launch_sweep_cells(a, workspace, (hipStream_t)stream, packed_ready), who);
-#endif
         return launched(pdepth::launch_sweep_tiled(a, workspace, (hipStream_t)stream, packed_ready), who);
     }
     return launched(pdepth::launch_sweep_direct(a, (hipStream_t)stream), who);
@@ -216,7 +164,7 @@ int pdepth_sweep_source_layout(const pdepth_sweep_desc* desc) {
 
 int pdepth_sweep_centres_source(const pdepth_sweep_desc* desc) {
     const int l = pdepth_sweep_source_layout(desc);
-    return (l == PDEPTH_LAYOUT_C4_CENTRED || l == PDEPTH_LAYOUT_DIST16) ? 1 : 0;
+    return l == PDEPTH_LAYOUT_DIST16 ? 1 : 0;
 }
 
 int pdepth_sweep_cost_f32(const pdepth_sweep_desc* desc, const pdepth_camera* cam, const float* ref,
@@ -254,7 +202,7 @@ int pdepth_pack_source_f32(const pdepth_sweep_desc* desc, const float* src, void
     a.B = desc->B; a.V = desc->V; a.C = desc->C; a.D = desc->D; a.H = desc->H; a.W = desc->W;
     a.src_bstride = desc->src_bstride; a.src_vstride = desc->src_vstride;
     if (uses_dist(desc)) return launched(pdepth::launch_pack_dist(a, workspace, (hipStream_t)stream), who);
-    return launched(pdepth::launch_pack_c4(a, workspace, (hipStream_t)stream, uses_corr(desc)), who);
+    return launched(pdepth::launch_pack_c4(a, workspace, (hipStream_t)stream), who);
 }
 
 int pdepth_pack_views_f32(const pdepth_sweep_desc* desc, const float* feat, const float* rgb, int32_t pool_rate, float* ref_out,
@@ -278,7 +226,7 @@ int pdepth_pack_views_f32(const pdepth_sweep_desc* desc, const float* feat, cons
         return launched(pdepth::launch_pack_views_dist(a, feat, rgb, pool_rate, desc->H * pool_rate, desc->W * pool_rate, ref_out, workspace,
                                                        (hipStream_t)stream), who);
     return launched(pdepth::launch_pack_views(a, feat, rgb, pool_rate, desc->H * pool_rate, desc->W * pool_rate, ref_out, workspace,
-                                              (hipStream_t)stream, uses_corr(desc)), who);
+                                              (hipStream_t)stream), who);
 }
 
 int pdepth_sweep_dpv_packed_f32(const pdepth_sweep_desc* desc, const pdepth_camera* cam, const float* ref,

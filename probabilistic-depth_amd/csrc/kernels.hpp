@@ -27,12 +27,9 @@ struct SweepArgs {
     float sigma;
     long long ref_bstride, src_bstride, src_vstride;
     // the source views in the sweep kernels' staging layout ([B*V][C/4 + 2][H][W] float4, sweep_tiled.hip), set by the
-    // launchers of the tiled / cell-list paths: the gather kernel reads it for the tiles handed to it when src == nullptr
+    // launcher of the tiled path: the gather kernel reads it for the tiles handed to it when src == nullptr
     // (packed-source entry: the caller no longer has the NCHW source)
     const void* packed_src;
-    // device-side choice between two sweep kernels launched back to back (pick.hpp): 0 = none (the kernel runs), PICK_SKIP_IF_SET
-    // = leave at once if queue[PICK_SLOT] != 0, PICK_RUN_IF_SET = leave at once if it is 0.  In the pre-pass: != 0 = compute it.
-    int pick;
 };
 // conditioning above which a batch item is routed to the gather kernel (sweep_dist.hip: "Conditioning"; sweep_pack.hip)
 #ifndef PDEPTH_COND_LIMIT
@@ -43,13 +40,9 @@ struct SweepArgs {
 #ifndef PDEPTH_COND_LIMIT_TILED
 #define PDEPTH_COND_LIMIT_TILED 1.5e-4f
 #endif
-constexpr int PICK_SLOT = 50, PICK_MFMA = 1;          // workspace int behind the tile flags (cleared with them)
-// more of the 64 workspace ints behind the tile flags:
+// the 64 workspace ints behind the tile flags.  Slots 50 and 52-55 are reserved and kept zero (they belonged to retired kernels;
+// the pack kernels and the flag clear zero them with the rest), so a workspace packed by an earlier build of ABI 6 stays valid.
 constexpr int NONCENTRED_SLOT = 51;        // set by the pre-pass of a NOT centred source whose channel offsets exceed the spread (sweep_pack.hip)
-constexpr int CORR_DONE_SLOT = 52;         // sweep_corr.hip: workgroups that have left (the last one zeroes the queue counters)
-constexpr int CORR_DIRECT_SLOT = 53;       // ... pixel blocks evaluated directly, this call so far / of the last finished call
-constexpr int CORR_DIRECT_LAST_SLOT = 54;
-constexpr int CORR_PACK_TIMEOUT_SLOT = 55;   // ... workgroups that gave up waiting for the in-kernel pack (never, unless the counters were corrupted)
 // channel statistics of the source (workspace tail, sweep_pack.hip): per batch item mu[c] at +0, var[c] at +STATS_VAR, the
 // squared offset that was NOT subtracted at +STATS_OFF, the largest sampled |x| at +STATS_AMAX, half the mean squared
 // difference of samples STATS_LAG_PX texels apart at +STATS_LAG (the spread of a channel at the distance of a plane sweep:
@@ -62,13 +55,14 @@ constexpr int STATS_LAG_PX = 16;
 // which staging layout the packed-source region holds (written by the pack kernels, checked by the sweep kernels: a sweep on
 // another family's layout fills its outputs with NaN instead of returning numbers computed from the wrong bytes)
 constexpr int LAYOUT_SLOT = 56;
-constexpr int LAYOUT_C4 = 1, LAYOUT_C4_CENTRED = 2, LAYOUT_DIST16 = 3;   // (0: nothing packed yet)
-constexpr int DIST_DONE_SLOT = 57, DIST_DIRECT_SLOT = 58, DIST_DIRECT_LAST_SLOT = 59;   // sweep_dist.hip: as the CORR_ slots
+constexpr int LAYOUT_C4 = 1, LAYOUT_DIST16 = 3;   // (0: nothing packed yet; 2: reserved, a retired layout)
+// sweep_dist.hip: workgroups that have left (the last one zeroes the queue counters); pixel blocks evaluated directly, this call
+// so far / of the last finished call
+constexpr int DIST_DONE_SLOT = 57, DIST_DIRECT_SLOT = 58, DIST_DIRECT_LAST_SLOT = 59;
 // DIST_DIRECT_LAST_SLOT holds (nonce << 20) | count, DIST_NONCE_SLOT the nonce of the last call: a count whose nonce is another
 // call's reads as 0 (where every workgroup runs one item there is no counter of finished workgroups to reset anything by: 2 048
 // returning atomics on one address were a quarter of such a launch)
 constexpr int DIST_NONCE_SLOT = 60;
-constexpr int PICK_SKIP_IF_SET = 1, PICK_RUN_IF_SET = 2;
 
 // First statement of a sweep kernel on a packed source: does the workspace hold the layout this kernel reads?  If not (a C
 // caller swept a workspace packed for another kernel family: include/pdepth.h, pdepth_sweep_source_layout) every output of
@@ -87,7 +81,6 @@ __device__ __forceinline__ bool poison_on_foreign_layout(const SweepArgs& a, con
         for (size_t i = i0; i < nmap; i += step) a.depth_out[i] = nan;
     return true;
 }
-constexpr int PH_PRE = 1, PH_KERNEL = 2, PH_GATHER = 4, PH_ALL = 7;   // phases of a sweep launcher: pre-pass / flag clear, kernel, gather
 
 // sweep_direct.hip
 hipError_t launch_sweep_direct(const SweepArgs& a, hipStream_t stream);
@@ -104,21 +97,17 @@ int sweep_direct_max_planes(int C);
 size_t sweep_tiled_workspace_bytes(int B, int V, int C, int H, int W);
 int sweep_tiled_max_planes();
 // packed_ready: the workspace already holds the packed source of exactly these views (pdepth_pack_source_f32)
-hipError_t launch_sweep_tiled(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false, int phases = PH_ALL);     // picks a variant
-hipError_t launch_sweep_tiled_n1(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false, int phases = PH_ALL);  // one 16x4 tile per block
-hipError_t launch_sweep_tiled_n2(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false, int phases = PH_ALL);  // two tiles per block
+hipError_t launch_sweep_tiled(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false);     // picks a variant
+hipError_t launch_sweep_tiled_n1(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false);  // one 16x4 tile per block
+hipError_t launch_sweep_tiled_n2(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false);  // two tiles per block
 
 // sweep_pack.hip: pre-pass of the packed-source kernels (channel statistics + packed source + Gram planes; clears flags and
-// queue counters).  centre: subtract the channel means (sweep_corr.hip); else the plain layout (mu = 0)
-hipError_t launch_pack_c4(const SweepArgs& a, void* workspace, hipStream_t stream, bool centre);
-// ... of a call whose sweep kernel packs the source itself: statistics + workspace bookkeeping only
-hipError_t launch_stats_only(const SweepArgs& a, void* workspace, hipStream_t stream);
-bool sweep_ws_holds_pack_counters(int B, int H, int W);
-int* sweep_ws_pack_counters(const SweepArgs& a, void* workspace);
+// queue counters) in the plain layout (nothing subtracted: mu = 0)
+hipError_t launch_pack_c4(const SweepArgs& a, void* workspace, hipStream_t stream);
 hipError_t clear_sweep_flags(const SweepArgs& a, void* workspace, hipStream_t stream);
 // encoder epilogue: cat(feat, avg_pool2d(rgb)) -> packed source views + NCHW reference view, in one pass (a.C = Cf + 3)
 hipError_t launch_pack_views(const SweepArgs& a, const float* feat, const float* rgb, int rate, int img_h, int img_w, float* ref_out,
-                             void* workspace, hipStream_t stream, bool centre);
+                             void* workspace, hipStream_t stream);
 int sweep_device_cus();
 // workspace head shared by the packed-source kernels: tile flags (+ the 64 queue / counter ints behind them); its tail
 size_t sweep_ws_flag_only_bytes(int B, int H, int W);
@@ -137,22 +126,6 @@ hipError_t launch_pack_views_dist(const SweepArgs& a, const float* feat, const f
 // sweep_dist.hip (L2 only): distance form sum_t w_t |s_t - r|^2 - Q on the matrix pipe (fp16 high / low parts), C <= 72, D <= 128
 bool sweep_dist_supports(const SweepArgs& a);
 hipError_t launch_sweep_dist(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false);
-
-// sweep_corr.hip (L2 only): correlation form on mean-centred features, one workgroup per block of 16 pixels
-bool sweep_corr_supports(const SweepArgs& a);
-hipError_t launch_sweep_corr(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false);
-
-// sweep_mfma.hip (L2 only; same workspace as the tiled kernel): the channel contraction on the matrix pipe
-bool sweep_mfma_supports(const SweepArgs& a);
-hipError_t launch_sweep_mfma(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false, int phases = PH_ALL);
-
-// sweep_cells.hip (L2 only; same workspace as the tiled kernel)
-int sweep_cells_max_planes();
-hipError_t launch_sweep_cells(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false);
-
-// sweep_cells_fast.hip: straight-line instantiation (D = 64 or 128), flags the tiles it leaves to the generic kernel
-hipError_t launch_sweep_cells_fast(const SweepArgs& a, const float4* packed, int* flags, int* queue, int* redo_list,
-                                   int tiles_x, int tiles, int n_cu, hipStream_t stream);
 
 // dpv.hip
 hipError_t launch_dpv_reduce(const float* logits, const float* d_candi, int B, int D, int H,

@@ -1,6 +1,5 @@
-// One texel of the packed source (sweep_pack.hip says what the layout is): shared by the pack kernel of the pre-pass and
-// by the correlation-form sweep kernel, which packs batch item b + 1 while it sweeps item b (sweep_corr.hip).
-// One thread per texel, channels in order (sequential fma: deterministic, the same bits on either path).
+// One texel of the packed source (sweep_pack.hip says what the layout is), as the pack kernel of the pre-pass writes it.
+// One thread per texel, channels in order (sequential fma: deterministic).
 #pragma once
 #include <hip/hip_runtime.h>
 

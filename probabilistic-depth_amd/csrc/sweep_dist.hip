@@ -36,9 +36,9 @@
 #include <cstdlib>
 
 #include "dist_layout.hpp"
+#include "epipolar_probe.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
-#include "pick.hpp"
 #include "wave_util.hpp"
 
 #include "sweep_dist_knobs.hpp"
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
 #endif
     __syncthreads();
     // Shape of the pixel blocks of a batch item: 16x1 where the epipolar lines of view 0 run along the source rows (a
-    // rectified pair: the 16 pixels of a row share two source rows), else 8x2 (pick.hpp; any choice is correct).
+    // rectified pair: the 16 pixels of a row share two source rows), else 8x2 (epipolar_probe.hpp; any choice is correct).
     if ((int)(tid >> 2) < min(KARG(int, a.B), 64) && epipolar_probe_is_steep(da.a, tid >> 2, tid & 3)) L.wide[tid >> 2] = 0;
 
     // ---- work queue (per XCD) -------------------------------------------------------------------------------------------

@@ -6,21 +6,20 @@
 //     [64 ints]                                              queue counters of the persistent kernels + the slots of kernels.hpp
 //     [packed source: B*V x (ceil(C/4) + 2) x H x W float4]  planes g < ceil(C/4): channels 4g..4g+3 of every texel, minus
 //                                                            mu[c]; then the two Gram planes
-//     [tile list]                                            (lab builds: the cell-list kernels)
+//     [reserved: as many bytes as the tile flags]            (a retired kernel's tile list; keeps the statistics where they were)
 //     [statistics: B x STATS_STRIDE floats]                  mu[c] (the constant subtracted per channel; zeros = not centred)
 //                                                            at +0, var[c] at +STATS_VAR
 //
-// Mean-centring (sweep_corr.hip says why): mu[b][c] = mean of channel c over a sample of 8 rows of source view 0 of
-// item b -- an estimate is all it takes, the correlation form is exact for ANY constant; what matters is that the
-// residual offset is small against the spread.  Consumers that do not centre (the LDS-tiled kernel: direct form on the
-// near planes) get mu = 0 and the layout is bit for bit the uncentred one; for those the pre-pass also raises
-// NONCENTRED_SLOT when sum mu^2 > sum var / 2, and the tiled kernel then evaluates every plane directly.
+// Mean-centring: mu[b][c] = mean of channel c over a sample of 8 rows of source view 0 of item b -- an estimate is all it
+// takes, what matters is that the residual offset is small against the spread.  The distance-form layout is centred
+// (pack_dist.hip reads these statistics).  The layout packed here is not (the LDS-tiled kernel: direct form on the near
+// planes): mu = 0, and the pre-pass raises NONCENTRED_SLOT when the squared channel offsets exceed half the summed
+// variances; the tiled kernel then evaluates every plane directly.
 #include <hip/hip_runtime.h>
 
 #include "dist_layout.hpp"
 #include "kernels.hpp"
 #include "pack_body.hpp"
-#include "pick.hpp"
 #include "stats_body.hpp"
 
 namespace pdepth {
@@ -30,19 +29,10 @@ namespace {
 constexpr int TW = 16, TH = 4;
 using namespace stats_body;
 
-// flags != nullptr: the call's workspace bookkeeping is done here (the sweep kernel that packs the source itself has no
-// pack kernel in front of it): tile flags and queue slots cleared, the pack counters of the sweep kernel zeroed.
 __global__ __launch_bounds__(256) void feature_stats_kernel(const float* __restrict__ src, long long bstride, long long vstride, int V,
                                                             const float* __restrict__ ref, long long ref_bstride, int C, int H, int W,
-                                                            float* __restrict__ stats, int centre, int* __restrict__ flags, int nflags,
-                                                            int* __restrict__ pack_ctr, int nctr) {
+                                                            float* __restrict__ stats, int centre) {
     const int c = blockIdx.x, b = blockIdx.y;
-    if (flags) {
-        // (nflags covers the tile flags and the 64 queue ints behind them)
-        for (int i = (b * gridDim.x + c) * 256 + threadIdx.x; i < nflags; i += gridDim.x * gridDim.y * 256) flags[i] = 0;
-        if (c == 0 && b == 0)
-            for (int i = threadIdx.x; i < nctr; i += 256) pack_ctr[i] = 0;
-    }
     float* st = stats + (size_t)b * STATS_STRIDE;
     if (c == 0 && threadIdx.x < STATS_VAR - C && C + (int)threadIdx.x < STATS_VAR) {   // channels beyond C
         st[C + threadIdx.x] = 0.0f; st[STATS_VAR + C + threadIdx.x] = 0.0f; st[STATS_OFF + C + threadIdx.x] = 0.0f;
@@ -73,7 +63,7 @@ __global__ __launch_bounds__(256) void view_stats_kernel(const float* __restrict
 
 // the first block of a pack kernel: queue counters and slots cleared, the tiled kernel's guard set (header)
 __device__ __forceinline__ void reset_queue_and_guard(int* __restrict__ queue, const float* __restrict__ stats, int B, int layout) {
-    if (threadIdx.x < 64 && threadIdx.x != PICK_SLOT) queue[threadIdx.x] = threadIdx.x == LAYOUT_SLOT ? layout : 0;
+    if (threadIdx.x < 64) queue[threadIdx.x] = threadIdx.x == LAYOUT_SLOT ? layout : 0;
     float off = 0.0f, var = 0.0f;
     for (int i = threadIdx.x; i < B * STATS_VAR; i += 256) {
         const int b = i / STATS_VAR, c = i - b * STATS_VAR;
@@ -109,10 +99,8 @@ __device__ __forceinline__ void route_ill_conditioned_items(float* __restrict__ 
 // (channels beyond C are zero), and the last two planes hold, for texel (x, y) and with s'(.) ABSENT (zero) outside the image:
 //     plane C/4     : ( <s'(x,y),s'(x,y)>, <s'(x,y),s'(x+1,y)>, <s'(x,y),s'(x,y+1)>, <s'(x,y),s'(x+1,y+1)> + <s'(x+1,y),s'(x,y+1)> )
 //     plane C/4 + 1 : ( <s'(x,y),mu>, 0, 0, 0 )
-// (the two diagonal products only ever enter a cost as their sum; a consumer that adds the first component of the second
-//  plane to it -- the kernels of earlier rounds, which found the second product there -- adds <s, 0> = 0 on the plain layout)
+// (the two diagonal products only ever enter a cost as their sum; mu = 0 here, so the second plane is zero)
 // One thread per texel, channels in order (sequential fma: deterministic); the neighbours' loads hit L1/L2.
-template <bool CENTRE>   // (false: mu = 0 -- no statistics are read, the loop is the plain re-layout)
 __global__ __launch_bounds__(256) void pack_c4_kernel(const float* __restrict__ src, long long bstride,
                                                       long long vstride, int V, int C, int H, int W,
                                                       float4* __restrict__ out, int* __restrict__ flags, int nflags, SweepArgs pa, int* queue,
@@ -121,10 +109,7 @@ __global__ __launch_bounds__(256) void pack_c4_kernel(const float* __restrict__ 
     // also clears the tile flags of this call (saves a memset launch)
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < nflags; i += gridDim.x * gridDim.y * 256) flags[i] = 0;
     if (blockIdx.x == 0 && blockIdx.y == 0) {
-        reset_queue_and_guard(queue, stats, pa.B, CENTRE ? LAYOUT_C4_CENTRED : LAYOUT_C4);
-        if (threadIdx.x == 0) queue[PICK_SLOT] = 0;
-        __syncthreads();
-        if (pa.pick != 0) pick_for_launch(pa, queue, threadIdx.x, 256);
+        reset_queue_and_guard(queue, stats, pa.B, LAYOUT_C4);
         if (pa.d_candi != nullptr) route_ill_conditioned_items(const_cast<float*>(stats), pa);   // (a sweep's pre-pass; pdepth_pack_source_f32 has no candidates)
     }
     // XCD-aware block order (workgroups are dealt round-robin over the 8 XCDs): every XCD packs one contiguous band
@@ -133,20 +118,13 @@ __global__ __launch_bounds__(256) void pack_c4_kernel(const float* __restrict__ 
     const int blk = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
     const int pix = blk * 256 + threadIdx.x;
     const int bv = blockIdx.y;
-    // the constants subtracted per channel: through LDS (a scalar load per channel in the loop below would sit in front of
-    // every group of texel loads)
-    __shared__ float mu[STATS_VAR];   // (CENTRE: C <= 72, every index of the loop below lies inside)
-    if (CENTRE) {
-        if (threadIdx.x < STATS_VAR) mu[threadIdx.x] = stats[(size_t)(bv / V) * STATS_STRIDE + threadIdx.x];
-        __syncthreads();
-    }
     if (pix >= HW) return;
     const int y = pix / W, x = pix - y * W;
     const bool hr = x + 1 < W, hd = y + 1 < H;
     const float* s = src + (size_t)(bv / V) * bstride + (size_t)(bv % V) * vstride + pix;
     const int ngrp = (C + 3) / 4;
     float4* o = out + (size_t)bv * (ngrp + 2) * HW + pix;
-    pack_texel<CENTRE>(s, C, HW, W, hr, hd, mu, [&](int g, float4 q) { o[(size_t)g * HW] = q; });
+    pack_texel<false>(s, C, HW, W, hr, hd, nullptr, [&](int g, float4 q) { o[(size_t)g * HW] = q; });
 }
 
 // Encoder epilogue: what the host model does between its feature encoder and the sweep --
@@ -161,12 +139,11 @@ __global__ __launch_bounds__(256) void pack_c4_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void pack_views_kernel(const float* __restrict__ feat, const float* __restrict__ rgb, int V, int Cf,
                                                          int H, int W, int rate, int IH, int IW, float4* __restrict__ out,
                                                          float* __restrict__ ref_out, int* __restrict__ flags, int nflags, int* queue,
-                                                         const float* __restrict__ stats, int B, int centred) {
+                                                         const float* __restrict__ stats, int B) {
     const int HW = H * W, C = Cf + 3;
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < nflags; i += gridDim.x * gridDim.y * 256) flags[i] = 0;
     if (blockIdx.x == 0 && blockIdx.y == 0) {
-        reset_queue_and_guard(queue, stats, B, centred ? LAYOUT_C4_CENTRED : LAYOUT_C4);
-        if (threadIdx.x == 0) queue[PICK_SLOT] = 0;
+        reset_queue_and_guard(queue, stats, B, LAYOUT_C4);
     }
     const int nb = gridDim.x, xcd = blockIdx.x & 7, qq = nb >> 3, rr = nb & 7;   // XCD-aware block order, as pack_c4_kernel
     const int blk = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
@@ -274,17 +251,6 @@ __global__ __launch_bounds__(256) void pack_views_kernel(const float* __restrict
     o[(size_t)(ngrp + 1) * HW] = make_float4(mm, 0.f, 0.f, 0.f);
 }
 
-// flag clear of a call on an already packed source when the kernel is chosen on the device (lab builds; else: a memset)
-__global__ __launch_bounds__(256) void clear_and_pick_kernel(SweepArgs pa, int* flags, int nflags, int* queue) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < nflags; i += gridDim.x * 256)
-        if (flags + i != queue + PICK_SLOT && flags + i != queue + NONCENTRED_SLOT && flags + i != queue + LAYOUT_SLOT) flags[i] = 0;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) queue[PICK_SLOT] = 0;
-        __syncthreads();
-        pick_for_launch(pa, queue, threadIdx.x, 256);
-    }
-}
-
 // flag clear that keeps the guard slot the pre-pass wrote; the routing flags of the items for THIS call's candidates and sigma
 __global__ __launch_bounds__(256) void clear_flags_kernel(int* flags, int nflags, int* queue, SweepArgs pa, float* stats) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nflags; i += gridDim.x * 256)
@@ -309,7 +275,7 @@ size_t packed_bytes(int B, int V, int C, int H, int W) {
 size_t sweep_ws_flag_only_bytes(int B, int H, int W) { return flag_only_bytes(B, H, W); }
 size_t sweep_ws_flag_bytes(int B, int H, int W) { return flag_bytes(B, H, W); }
 size_t sweep_ws_stats_offset(int B, int V, int C, int H, int W) {
-    // flags + queue counters, packed source, then the list of tiles the fast cell-list kernel leaves to the generic one
+    // flags + queue counters, packed source, then the reserved bytes a retired kernel's tile list occupied (header)
     return flag_bytes(B, H, W) + packed_bytes(B, V, C, H, W) + flag_only_bytes(B, H, W);
 }
 size_t sweep_tiled_workspace_bytes(int B, int V, int C, int H, int W) {
@@ -317,29 +283,25 @@ size_t sweep_tiled_workspace_bytes(int B, int V, int C, int H, int W) {
 }
 
 // pre-pass of a call: channel statistics, packed source + Gram planes, tile flags and queue counters cleared
-hipError_t launch_pack_c4(const SweepArgs& a, void* workspace, hipStream_t stream, bool centre) {
+hipError_t launch_pack_c4(const SweepArgs& a, void* workspace, hipStream_t stream) {
     int* flags = reinterpret_cast<int*>(workspace);
     float4* packed = reinterpret_cast<float4*>(static_cast<char*>(workspace) + flag_bytes(a.B, a.H, a.W));
     float* stats = reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
     const int HW = a.H * a.W;
     hipLaunchKernelGGL(feature_stats_kernel, dim3(a.C < STATS_VAR ? a.C : STATS_VAR, a.B), dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, 1,
-                       (const float*)nullptr, 0ll, a.C, a.H, a.W, stats, (centre && a.C <= 72) ? 1 : 0, (int*)nullptr, 0, (int*)nullptr, 0);
+                       (const float*)nullptr, 0ll, a.C, a.H, a.W, stats, 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     dim3 pgrid((HW + 255) / 256, a.B * a.V);
     int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
-    if (centre && a.C <= 72)
-        hipLaunchKernelGGL(pack_c4_kernel<true>, pgrid, dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, a.V, a.C, a.H, a.W, packed,
-                           flags, (int)(flag_only_bytes(a.B, a.H, a.W) / sizeof(int)), a, queue, stats);
-    else
-        hipLaunchKernelGGL(pack_c4_kernel<false>, pgrid, dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, a.V, a.C, a.H, a.W, packed,
-                           flags, (int)(flag_only_bytes(a.B, a.H, a.W) / sizeof(int)), a, queue, stats);
+    hipLaunchKernelGGL(pack_c4_kernel, pgrid, dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, a.V, a.C, a.H, a.W, packed,
+                       flags, (int)(flag_only_bytes(a.B, a.H, a.W) / sizeof(int)), a, queue, stats);
     return hipGetLastError();
 }
 
 hipError_t launch_feature_stats(const SweepArgs& a, float* stats, hipStream_t stream) {
     hipLaunchKernelGGL(feature_stats_kernel, dim3(a.C < STATS_VAR ? a.C : STATS_VAR, a.B), dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, a.V,
-                       a.ref, a.ref_bstride, a.C, a.H, a.W, stats, 1, (int*)nullptr, 0, (int*)nullptr, 0);
+                       a.ref, a.ref_bstride, a.C, a.H, a.W, stats, 1);
     return hipGetLastError();
 }
 hipError_t launch_view_stats(const SweepArgs& a, const float* feat, const float* rgb, int rate, int img_h, int img_w, float* stats, hipStream_t stream) {
@@ -348,35 +310,21 @@ hipError_t launch_view_stats(const SweepArgs& a, const float* feat, const float*
     return hipGetLastError();
 }
 
-// Pre-pass of a call whose sweep kernel packs the source itself (sweep_corr.hip): the channel statistics, and the workspace
-// bookkeeping the pack kernel otherwise does.  The pack counters (two ints per batch item) live in the tile-list region.
-bool sweep_ws_holds_pack_counters(int B, int H, int W) { return (size_t)2 * B * sizeof(int) <= flag_only_bytes(B, H, W); }
-int* sweep_ws_pack_counters(const SweepArgs& a, void* workspace) {
-    return reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_bytes(a.B, a.H, a.W) + packed_bytes(a.B, a.V, a.C, a.H, a.W));
-}
-hipError_t launch_stats_only(const SweepArgs& a, void* workspace, hipStream_t stream) {
-    float* stats = reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
-    hipLaunchKernelGGL(feature_stats_kernel, dim3(a.C < STATS_VAR ? a.C : STATS_VAR, a.B), dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, 1,
-                       (const float*)nullptr, 0ll, a.C, a.H, a.W, stats, 1, reinterpret_cast<int*>(workspace), (int)(flag_bytes(a.B, a.H, a.W) / sizeof(int)),
-                       sweep_ws_pack_counters(a, workspace), 2 * a.B);
-    return hipGetLastError();
-}
-
 // the encoder epilogue (pack_views_kernel): a.C = Cf + 3, a.V source views, views V+1 per item in feat / rgb
 hipError_t launch_pack_views(const SweepArgs& a, const float* feat, const float* rgb, int rate, int img_h, int img_w, float* ref_out,
-                             void* workspace, hipStream_t stream, bool centre) {
+                             void* workspace, hipStream_t stream) {
     int* flags = reinterpret_cast<int*>(workspace);
     float4* packed = reinterpret_cast<float4*>(static_cast<char*>(workspace) + flag_bytes(a.B, a.H, a.W));
     float* stats = reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
     int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
     const int HW = a.H * a.W;
     hipLaunchKernelGGL(view_stats_kernel, dim3(a.C < STATS_VAR ? a.C : STATS_VAR, a.B), dim3(256), 0, stream, feat, rgb, a.V, a.C - 3, a.H,
-                       a.W, rate, img_h, img_w, stats, centre ? 1 : 0);
+                       a.W, rate, img_h, img_w, stats, 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     dim3 pgrid((HW + 255) / 256, a.B * (a.V + 1));
     hipLaunchKernelGGL(pack_views_kernel, pgrid, dim3(256), 0, stream, feat, rgb, a.V, a.C - 3, a.H, a.W, rate, img_h, img_w, packed, ref_out,
-                       flags, (int)(flag_only_bytes(a.B, a.H, a.W) / sizeof(int)), queue, stats, a.B, centre ? 1 : 0);
+                       flags, (int)(flag_only_bytes(a.B, a.H, a.W) / sizeof(int)), queue, stats, a.B);
     return hipGetLastError();
 }
 
@@ -385,11 +333,8 @@ hipError_t launch_pack_views(const SweepArgs& a, const float* feat, const float*
 hipError_t clear_sweep_flags(const SweepArgs& a, void* workspace, hipStream_t stream) {
     int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
     const int nflags = (int)(flag_bytes(a.B, a.H, a.W) / sizeof(int));
-    if (a.pick != 0)
-        hipLaunchKernelGGL(clear_and_pick_kernel, dim3((nflags + 2047) / 2048), dim3(256), 0, stream, a, reinterpret_cast<int*>(workspace), nflags, queue);
-    else
-        hipLaunchKernelGGL(clear_flags_kernel, dim3((nflags + 2047) / 2048), dim3(256), 0, stream, reinterpret_cast<int*>(workspace), nflags, queue, a,
-                           reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W)));
+    hipLaunchKernelGGL(clear_flags_kernel, dim3((nflags + 2047) / 2048), dim3(256), 0, stream, reinterpret_cast<int*>(workspace), nflags, queue, a,
+                       reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W)));
     return hipGetLastError();
 }
 

@@ -52,11 +52,8 @@
 // ~3e-7 (direct) and ~5e-7 (band) of the largest cost of the volume, i.e. an ulp or two of the fp32 cost.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "geometry.hpp"
 #include "kernels.hpp"
-#include "pick.hpp"
 
 namespace pdepth {
 
@@ -183,7 +180,6 @@ template <int METRIC, bool SPEC>
 __global__ __launch_bounds__(NT, PDEPTH_OCC) void sweep_tiled_kernel(SweepArgs a, const float4* __restrict__ packed,
                                                               int* __restrict__ tile_flags, int* __restrict__ queue,
                                                               int tiles_x, int ntile, const float* __restrict__ route_stats) {
-    if (PDEPTH_COLD_ARG(int, pick) == PICK_SKIP_IF_SET && queue[PICK_SLOT] != 0) return;   // (the pre-pass chose the other kernel: pick.hpp)
     if (poison_on_foreign_layout(a, queue, LAYOUT_C4)) return;
     const int aD = SPEC ? 64 : a.D, aC = SPEC ? 67 : a.C, aV = SPEC ? 1 : a.V;
     extern __shared__ __attribute__((aligned(16))) float4 lds4[];
@@ -264,7 +260,7 @@ __global__ __launch_bounds__(NT, PDEPTH_OCC) void sweep_tiled_kernel(SweepArgs a
         tile_ = band_first_of(qx) + ti;
         const int tiles_y_ = ntile / tiles_x;
         if (rr == 0 && tiles_y_ % 16 == 0 && tiles_y_ * tiles_x == ntile) {
-            // XCD q owns half-bands q and 8 + q of the image's 16 (as the matrix-pipe kernel, sweep_mfma.hip): on a forward
+            // XCD q owns half-bands q and 8 + q of the image's 16: on a forward
             // motion the cost of a tile grows with its distance from the image centre, and this way every XCD gets the same
             // mix; the heavier half first and, inside a half, columns from both image borders inwards.
             const int hb_rows = tiles_y_ / 16, half_tiles = hb_rows * tiles_x;
@@ -928,32 +924,36 @@ static size_t flag_bytes(int B, int H, int W) { return sweep_ws_flag_bytes(B, H,
 // Two tiles per block pay off when two such blocks fit a CU (the cost tiles of both sub-tiles live in LDS: D <= 64)
 // and the image is large enough for the wider windows not to dominate; measured on the BASELINE configurations.
 // (PDEPTH_ALGO_TILED_1 / _2 force a variant.)
-hipError_t launch_sweep_tiled(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready, int phases) {
+hipError_t launch_sweep_tiled(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready) {
     const bool two = a.D <= 64 && (long long)a.H * a.W >= 96 * 1024 && a.W >= 128;
-    return two ? launch_sweep_tiled_n2(a, workspace, stream, packed_ready, phases) : launch_sweep_tiled_n1(a, workspace, stream, packed_ready, phases);
+    return two ? launch_sweep_tiled_n2(a, workspace, stream, packed_ready) : launch_sweep_tiled_n1(a, workspace, stream, packed_ready);
 }
 
 #endif
+
+// one instantiation of this variant's kernel on the persistent grid
+// (the dynamic-LDS attribute is per kernel, sticky and the same on every device: set it whenever more than the
+//  default is needed -- no cached state, and a failure is reported instead of surfacing as a launch error)
+template <int METRIC, bool SPEC>
+static hipError_t launch_tiled_kernel(const SweepArgs& a, dim3 grid, size_t lds, hipStream_t stream, const float4* packed, int* flags,
+                                      int* queue, int tiles_x, int tiles, const float* route_stats) {
+    auto kern = PDEPTH_VARIANT::sweep_tiled_kernel<METRIC, SPEC>;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, stream, a, packed, flags, queue, tiles_x, tiles, route_stats);
+    return hipGetLastError();
+}
 
 // Launches the pre-pass, this variant's tiled kernel, then the gather kernel on the tiles it flagged.
-// lab builds, PDEPTH_NO_SPEC=1 (read once): always the general instantiation (A/B timing of the compile-time specialisation)
-static bool getenv_once_no_spec() {
-#ifdef PDEPTH_LAB
-    static const bool v = [] { const char* e = getenv("PDEPTH_NO_SPEC"); return e && e[0] == '1'; }();
-    return v;
-#else
-    return false;
-#endif
-}
-
-hipError_t PDEPTH_CAT(launch_sweep_tiled_n, PDEPTH_NSUB)(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready, int phases) {
+hipError_t PDEPTH_CAT(launch_sweep_tiled_n, PDEPTH_NSUB)(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready) {
     const int tiles16_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;  // the gather kernel's (and the flags') tiles
     const int tiles_x = (a.W + TW * NSUB - 1) / (TW * NSUB);                  // this kernel's work items per row
     const int tiles = tiles_x * tiles_y;
     int* flags = reinterpret_cast<int*>(workspace);
     float4* packed = reinterpret_cast<float4*>(static_cast<char*>(workspace) + flag_bytes(a.B, a.H, a.W));
-    hipError_t e = hipSuccess;
-    if (phases & PH_PRE) e = packed_ready ? clear_sweep_flags(a, workspace, stream) : launch_pack_c4(a, workspace, stream, /*centre=*/false);
+    hipError_t e = packed_ready ? clear_sweep_flags(a, workspace, stream) : launch_pack_c4(a, workspace, stream);
     if (e != hipSuccess) return e;
     const size_t lds = tiled_lds_bytes(a.D);
     int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
@@ -968,34 +968,13 @@ hipError_t PDEPTH_CAT(launch_sweep_tiled_n, PDEPTH_NSUB)(const SweepArgs& a, voi
     dim3 grid(nblk);
     // (routing: the pre-pass / the flag clear of this call has set flag 1 of the statistics row of every ill-conditioned item)
     const float* route_stats = reinterpret_cast<const float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
-    // (the dynamic-LDS attribute is per kernel, sticky and the same on every device: set it whenever more than the
-    //  default is needed -- no cached state, and a failure is reported instead of surfacing as a launch error)
-    if (phases & PH_KERNEL) {
-    if (a.metric == 0 && a.D == 64 && a.C == 67 && a.V == 1 && !getenv_once_no_spec()) {
-        auto kern = PDEPTH_VARIANT::sweep_tiled_kernel<0, true>;
-        if (lds > 64 * 1024) {
-            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(NT), lds, stream, a, packed, flags, queue, tiles_x, tiles, route_stats);
-    } else if (a.metric == 0) {
-        auto kern = PDEPTH_VARIANT::sweep_tiled_kernel<0, false>;
-        if (lds > 64 * 1024) {
-            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(NT), lds, stream, a, packed, flags, queue, tiles_x, tiles, route_stats);
-    } else {
-        auto kern = PDEPTH_VARIANT::sweep_tiled_kernel<1, false>;
-        if (lds > 64 * 1024) {
-            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(NT), lds, stream, a, packed, flags, queue, tiles_x, tiles, route_stats);
-    }
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess || !(phases & PH_GATHER)) return e;
+    if (a.metric == 0 && a.D == 64 && a.C == 67 && a.V == 1)
+        e = launch_tiled_kernel<0, true>(a, grid, lds, stream, packed, flags, queue, tiles_x, tiles, route_stats);
+    else if (a.metric == 0)
+        e = launch_tiled_kernel<0, false>(a, grid, lds, stream, packed, flags, queue, tiles_x, tiles, route_stats);
+    else
+        e = launch_tiled_kernel<1, false>(a, grid, lds, stream, packed, flags, queue, tiles_x, tiles, route_stats);
+    if (e != hipSuccess) return e;
     SweepArgs ag = a;
     ag.packed_src = packed;   // (the gather kernel's source when the caller passed a packed source only)
     return launch_sweep_direct_flagged(ag, flags, queue + GATHER_COUNT_SLOT, tiles16_x, tiles16_x * tiles_y, stream);

@@ -67,40 +67,14 @@ PDEPTH_WAVE_REDUCE(wave_min_i, "v_min_i32_dpp", min)
 PDEPTH_WAVE_REDUCE(wave_max_i, "v_max_i32_dpp", max)
 #undef PDEPTH_WAVE_REDUCE
 
-// plane_sample_pos_fast() of geometry.hpp for two planes at a time in packed fp32 (v_pk_mul / v_pk_add / v_pk_fma_f32:
-// each component rounds exactly like the scalar instruction, so the positions are bit-identical)
-__device__ __forceinline__ v2f splat2(float x) { return v2f{x, x}; }
-__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ v2f div_core2(v2f n, v2f d, v2f y) {
-    const v2f q0 = n * y;
-    const v2f r0 = fma2(-d, q0, n);
-    const v2f q1 = fma2(r0, y, q0);
-    const v2f r1 = fma2(-d, q1, n);
-    return fma2(r1, y, q1);
-}
-// CAUTION (gfx950, ROCm 7.2; measured in sweep_dist.hip, tools/dbg/dist_dbg.py): in a kernel whose other waves run
-// v_mfma_f32_16x16x32_f16 on the same SIMD, these packed instructions now and then leave the LOW half of a result
-// unwritten in lanes 48..63 (a sample's position then lacks exactly one operation of the chain below: px without K@t,
-// gy without the "- cy", ...).  Never in the first pass of a workgroup (every wave of the chip is in its position phase
-// then), on any later pass a few hundred samples per launch; a drain of all counters and s_nops in front make no
-// difference, the scalar chain of geometry.hpp on the same inputs is always right.  sweep_corr.hip (fp32 matrix
-// instructions in the other waves) has run this code through tens of thousands of soak cases without a miss.
-__device__ __forceinline__ void plane_sample_pos_fast2(const ViewXform& x, float t2a, float t2b, float t2c, v2f d, float cx, float cy,
-                                                       float rcx, float rcy, float half_w, float half_h, v2f& ix, v2f& iy) {
-    const v2f px = splat2(x.kt[0]) + splat2(t2a) * d;
-    const v2f py = splat2(x.kt[1]) + splat2(t2b) * d;
-    const v2f pz = splat2(x.kt[2]) + splat2(t2c) * d;
-    const v2f den = pz + splat2(1e-10f);
-    const v2f y0 = v2f{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-    const v2f e = fma2(-den, y0, splat2(1.0f));
-    const v2f y = fma2(e, y0, y0);
-    const v2f u = div_core2(px, den, y);
-    const v2f v = div_core2(py, den, y);
-    const v2f gx = div_core2(u - splat2(cx), splat2(cx), splat2(rcx));
-    const v2f gy = div_core2(v - splat2(cy), splat2(cy), splat2(rcy));
-    ix = fma2(gx + splat2(1.0f), splat2(half_w), splat2(-0.5f));
-    iy = fma2(gy + splat2(1.0f), splat2(half_h), splat2(-0.5f));
-}
+// CAUTION, packed fp32 (v_pk_mul / v_pk_add / v_pk_fma_f32) on gfx950, ROCm 7.2; measured in sweep_dist.hip with
+// plane_sample_pos_fast() of geometry.hpp written for two planes at a time (tools/dbg/dist_dbg.py): in a kernel whose other
+// waves run v_mfma_f32_16x16x32_f16 on the same SIMD, these packed instructions now and then leave the LOW half of a result
+// unwritten in lanes 48..63 (a sample's position then lacks exactly one operation of the chain: px without K@t, gy without
+// the "- cy", ...).  Never in the first pass of a workgroup (every wave of the chip is in its position phase then), on any
+// later pass a few hundred samples per launch; a drain of all counters and s_nops in front make no difference, the scalar
+// chain of geometry.hpp on the same inputs is always right.  So no kernel of this library uses packed fp32
+// (tests/test_isa_guard.py checks the listing of sweep_dist.hip).
 
 // Footprint of a sample position as make_footprint() (geometry.hpp) computes it, packed: (y0 << 16) | (x0 & 0xffff) of the
 // top-left texel, or NO_CELL when no tap lies inside the image (NaN positions included); fw, fn = the fractions.

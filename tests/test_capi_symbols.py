@@ -122,14 +122,15 @@ def test_product_path_has_no_cpu_fallback():
 
 
 def test_product_library_carries_no_lab_bench():
-    """the default build holds the product kernels only -- the kernels of earlier rounds and their
-    experiment switches live under csrc/lab/ (make LAB=1) --, a product sweep source has at most five preprocessor
-    conditionals (diagnostic builds), and the shipped library does not answer the lab selectors."""
+    """VERDICT r3 item 8, then the retirement of the lab kernels: the library holds the product kernels only -- no csrc/lab/
+    directory, no LAB switch in the Makefile, no PDEPTH_LAB conditional and no getenv( anywhere under csrc/ --, a product sweep
+    source has at most five preprocessor conditionals (diagnostic builds), and the library refuses the retired selectors."""
     import re
     csrc = os.path.join(REPO, "probabilistic-depth_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
     srcs = re.search(r"^SRCS = (.*)$", mk, re.M).group(1).split()
-    assert not any(s.startswith("lab/") for s in srcs) and "sweep_dist.hip" in srcs and "sweep_corr.hip" not in srcs and "ifdef LAB" in mk
+    assert not any(s.startswith("lab/") for s in srcs) and "sweep_dist.hip" in srcs and "sweep_corr.hip" not in srcs
+    assert not os.path.exists(os.path.join(csrc, "lab")) and "LAB" not in mk
     for f in srcs:
         if f.startswith("sweep_"):
             n = len(re.findall(r"^\s*#\s*if", open(os.path.join(csrc, f)).read(), re.M))
@@ -139,25 +140,42 @@ def test_product_library_carries_no_lab_bench():
     for n in names:
         assert hasattr(lib, n)
     assert (_native.ALGO_CORR, _native.ALGO_DIST) == (6, 7)
-    # the lab selectors (the cell-list, fp32-matrix and correlation-form kernels of rounds 2 / 3 / 4) are refused by the product
-    # library, by name
+    # the retired selectors (the cell-list, fp32-matrix and correlation-form kernels of rounds 2 / 3 / 4) are refused, by name
     cam = _native.Camera(1, 1, 1, 1, 1)
     for algo in (_native.ALGO_CELLS, _native.ALGO_MFMA, _native.ALGO_CORR):
         desc = _native.SweepDesc(1, 1, 4, 8, 8, 16, 0, algo, 0, 1.0, 512, 512, 512)
         rc = lib.pdepth_sweep_dpv_f32(ctypes.byref(desc), ctypes.byref(cam), 1, 1, 1, None, 1, 1, 256, 1 << 20, None)
-        assert rc == 1 and b"lab builds only" in lib.pdepth_last_error()
-    # ... and it reads no environment: every experiment switch of the sources (PDEPTH_SWEEP_IMPL, PDEPTH_CORR_FUSE_PACK,
-    # PDEPTH_NO_SPEC, PDEPTH_CORR_NO_MFMA) sits behind #ifdef PDEPTH_LAB, so their names are not in the binary
+        msg = lib.pdepth_last_error()
+        assert rc == 1 and b"retired" in msg
+        for name in (b"PDEPTH_ALGO_CELLS", b"PDEPTH_ALGO_MFMA", b"PDEPTH_ALGO_CORR"):
+            assert name in msg, (name, msg)
+        # ... and no descriptor selects the retired centred channel-group-planar layout (2) any more
+        assert lib.pdepth_sweep_source_layout(ctypes.byref(desc)) == _native.LAYOUT_C4
+    # ... and it reads no environment: the experiment switches of earlier rounds are not in the binary, and
+    # no source under csrc/ calls getenv or knows a lab build
     blob = open(_native.LIB_PATH, "rb").read()
     for name in (b"PDEPTH_SWEEP_IMPL", b"PDEPTH_CORR_FUSE_PACK", b"PDEPTH_NO_SPEC", b"PDEPTH_CORR_NO_MFMA"):
         assert name not in blob, name
-    for f in os.listdir(csrc):
-        if f.endswith((".hip", ".hpp")):
-            body = open(os.path.join(csrc, f)).read()
-            for m in re.finditer(r"getenv\(", body):
-                head = body[:m.start()]
-                opened = len(re.findall(r"^\s*#\s*ifdef PDEPTH_LAB", head, re.M)) + len(re.findall(r"^\s*#\s*if defined\(PDEPTH_LAB\)", head, re.M))
-                assert opened > 0 and head.rfind("PDEPTH_LAB") > head.rfind("#endif"), f"{f}: getenv outside a lab-only block"
+    for root, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".hip", ".hpp", ".h", ".sh")) or f == "Makefile":
+                body = open(os.path.join(root, f)).read()
+                assert "getenv(" not in body and "PDEPTH_LAB" not in body, f
+
+
+def test_binding_reads_the_workspace_slots_the_kernels_write():
+    """_native.py reads diagnostics out of the 64 workspace ints behind the tile flags; the slot numbers and layout tags are
+    those of csrc/kernels.hpp."""
+    import re
+    hpp = open(os.path.join(REPO, "probabilistic-depth_amd", "csrc", "kernels.hpp")).read()
+    consts = {k: int(v) for k, v in re.findall(r"\b([A-Z][A-Z0-9_]*)\s*=\s*(\d+)\s*[,;]", hpp)}
+    for name in ("NONCENTRED_SLOT", "LAYOUT_SLOT", "DIST_DIRECT_LAST_SLOT", "DIST_NONCE_SLOT", "LAYOUT_C4", "LAYOUT_DIST16"):
+        assert name in consts, name
+        assert getattr(_native, name) == consts[name], (name, getattr(_native, name), consts[name])
+    # ... and the header's numbers of the layouts
+    h = open(os.path.join(REPO, "include", "pdepth.h")).read()
+    for name in ("LAYOUT_NONE", "LAYOUT_C4", "LAYOUT_DIST16"):
+        assert int(re.search(r"PDEPTH_%s = (\d+)" % name, h).group(1)) == getattr(_native, name), name
 
 
 def test_header_says_what_the_code_does():

@@ -150,7 +150,7 @@ def test_packed_source_is_tied_to_the_kernel_family(dev):
     for ps, kw in ((centred, dict(algo="tiled1")), (plain, dict(algo="auto")), (centred, dict(feat_dist="L1"))):
         with pytest.raises(RuntimeError, match="another kernel family"):
             ops.sweep_dpv(d["ref"], ps, *args, **kw)
-    with pytest.raises(RuntimeError, match="lab builds only"):   # (round 4's correlation-form kernel: make LAB=1)
+    with pytest.raises(RuntimeError, match="PDEPTH_ALGO_CORR are retired"):   # (round 4's correlation-form kernel)
         ops.sweep_dpv(d["ref"], d["src"], *args, algo="corr")
     first = {}
     for ps, algo in ((centred, "auto"), (plain, "tiled1")):

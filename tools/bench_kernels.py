@@ -64,7 +64,7 @@ def main():
     sweep_case("cfg1/2 model-real 64x128 B=4", 4, 67, 64, 64, 128, 1, "mono", steps=50)
     sweep_case("cfg5 D=128 512x1024 V=4 B=2 (per-GPU share of B=16)", 2, 67, 128, 512, 1024, 4, "mono", steps=5)
     sweep_case("cfg2 mono 256x512 B=4 gather kernel", 4, 67, 64, 256, 512, 1, "mono", algo="direct", steps=5)
-    # the implementations behind "auto", forced (A/B): the correlation-form kernel, one-tile and two-tile builds of the tiled kernel
+    # the implementations behind "auto", forced (A/B): one-tile and two-tile builds of the tiled kernel
     for algo in ("tiled1", "tiled2"):
         sweep_case("cfg2 mono 256x512 B=4", 4, 67, 64, 256, 512, 1, "mono", algo=algo)
         sweep_case("cfg3 stereo 256x512 B=4", 4, 67, 64, 256, 512, 1, "stereo", algo=algo)

@@ -42,7 +42,7 @@ def tm(name, B, C, D, H, W, V, pose, algo, steps=20):
     f = lambda: ops.sweep_dpv(d["ref"], d["src"], d["K"], d["R"], d["t"], d["rays"], d["cxcy"], dc, 10.0, algo=algo)
     ms = min(timeit(f, steps=steps) for _ in range(3))
     line = "%-28s %-7s %8.4f ms  fallback %d" % (name, algo, ms, pdepth_amd._native.fallback_tiles(B, H, W))
-    if algo in ("auto", "corr", "dist"):
+    if algo in ("auto", "dist"):
         ps = ops.pack_source(d["src"], D, algo)
         g = lambda: ops.sweep_dpv(d["ref"], ps, d["K"], d["R"], d["t"], d["rays"], d["cxcy"], dc, 10.0, algo=algo)
         line += "   packed entry %8.4f ms" % min(timeit(g, steps=steps) for _ in range(3))
@@ -72,5 +72,3 @@ tm("cfg2 mono 256x512", 4, 67, 64, 256, 512, 1, "mono", "tiled2")
 tm("model-real 64x128 B=4", 4, 67, 64, 64, 128, 1, "mono", "dist", steps=50)
 tm("model-real 64x128 B=1", 1, 67, 64, 64, 128, 1, "mono", "dist", steps=50)
 tm("cfg5 D=128 512x1024 V=4", 2, 67, 128, 512, 1024, 4, "mono", "dist", steps=5)
-tm("cfg2 mono 256x512", 4, 67, 64, 256, 512, 1, "mono", "corr")
-tm("cfg3 stereo 256x512", 4, 67, 64, 256, 512, 1, "stereo", "corr")

@@ -1,4 +1,4 @@
-"""Times the tiled kernel (algo tiled2 / tiled1) with the library PDEPTH_LIB selects (A/B of tools/variants_tiled.sh builds)."""
+"""Times the tiled kernel (algo tiled2 / tiled1) with the library PDEPTH_LIB selects (A/B of `SRC=sweep_tiled tools/variants_dist.sh` builds)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -1,7 +1,7 @@
 // Numerics + layout probe for the distance-form sweep kernel (csrc/sweep_dist.hip):
 //   Y[texel][pixel] = |s_texel - r_pixel|^2 over C = 67 channels, three ways:
 //     (a) v_mfma_f32_16x16x32_f16 on fp16 hi/lo splits (7 instructions, specials folded: N_t, rr_n as fp16 pieces)
-//     (b) v_mfma_f32_16x16x4_f32 chain for X, Y = N - 2X + rr in fp32 (what sweep_corr.hip's form costs in rounding)
+//     (b) v_mfma_f32_16x16x4_f32 chain for X, Y = N - 2X + rr in fp32 (what the retired correlation-form kernel's form cost in rounding)
 //     (c) host fp64 on the fp32 inputs
 // plus: A/B lane-map check with exact integer data, fp16 subnormal operands, and MFMA issue rate.
 // Build: hipcc -O3 --offload-arch=gfx950 -o tools/mb_split16 tools/mb_split16.hip

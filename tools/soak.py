@@ -1,5 +1,5 @@
 """Soak test on the GPU box: random shapes / poses / depth candidates / metrics, every implementation forced in turn
-(the distance-form and the correlation-form kernels where they apply -- L2, D <= 128, C <= 72, V <= 8 --, both builds of the
+(the distance-form kernel where it applies -- L2, D <= 128, C <= 72, V <= 8 --, both builds of the
 tiled kernel; with SOAK_DPV every fourth case the `auto` selection), against the gather kernel, which evaluates in the
 reference's op order (channel sums in ATen's cascade order since round 5).
 
@@ -172,7 +172,7 @@ def main():
         d = {kk: (v.to(DEV) if isinstance(v, torch.Tensor) else v) for kk, v in b.items()}
         metric = "L1" if case % 7 == 3 else "L2"
         algo = ("tiled1", "dist", "direct", "auto", "tiled2")[case % 5]   # (period 5: every kernel meets offsets -- even cases -- and the oracle leg -- every third)
-        if algo in ("corr", "dist") and (metric == "L1" or s["D"] > 128 or s["C"] > 72):
+        if algo == "dist" and (metric == "L1" or s["D"] > 128 or s["C"] > 72):
             algo = "tiled1"
         if algo == "tiled2" and s["D"] > 64:
             algo = "tiled1"
@@ -180,8 +180,8 @@ def main():
             algo = "tiled1"
         if force:
             algo = force
-            if force in ("corr", "dist") and (metric == "L1" or s["D"] > 128 or s["C"] > 72):
-                algo = "tiled1"   # (shapes the correlation-form kernel is not built for)
+            if force == "dist" and (metric == "L1" or s["D"] > 128 or s["C"] > 72):
+                algo = "tiled1"   # (shapes the distance-form kernel is not built for)
         args = (d["ref"], d["src"], d["K"], d["R"], d["t"], d["rays"], d["cxcy"], d["d_candi"], 8.0)
         tag = describe(case, algo, s, metric)
         if DPV:
