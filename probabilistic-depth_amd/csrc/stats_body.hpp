@@ -1,6 +1,5 @@
 // Channel statistics of the feature views (the constant that is subtracted per channel, the fp16 scale, the guard's energy and
-// lagged spread): the body of feature_stats_kernel / view_stats_kernel (sweep_pack.hip), shared with the pack kernel of the
-// distance-form layout, which runs it in its first workgroups (pack_dist.hip: one pre-pass launch instead of two).
+// lagged spread): the body of feature_stats_kernel / view_stats_kernel (sweep_pack.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

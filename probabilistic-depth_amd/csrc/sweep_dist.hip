@@ -71,18 +71,16 @@ struct DistArgs {
 
 // exp(x) for x <= 0 (softmax terms): the hardware 2^t on the rounded product t = x log2(e).  The product's rounding error
 // (2^-24 |t|) is a relative error |t| ln2 2^-24 of the result: 4e-7 for the terms within a factor 1000 of the largest one,
-// which are the ones that carry a depth map or a normaliser; geometry.hpp's exp_nonpos (12 instructions) keeps 1.5 ulp
-// for every term (DIST_EXACT_EXP restores it).
+// which are the ones that carry a depth map or a normaliser (geometry.hpp's exp_nonpos keeps 1.5 ulp for every term, in 12
+// instructions).
 __device__ __forceinline__ float dist_exp(float x) {
-    if (DIST_EXACT_EXP) return exp_nonpos(x);
     return __builtin_amdgcn_exp2f((x < -1000.0f ? -1000.0f : x) * 1.44269502162933349609375f);   // (a NaN passes through, as in exp_nonpos)
 }
 
 template <int MAXB, int NAC>
 struct __attribute__((aligned(16))) DistLds {
     static constexpr int XSTRIDE = MAXB * 16 + 4;   // floats per pixel of the Y buffer (stride / 4 odd: conflict-free b128 stores)
-    float Ys[16 * XSTRIDE + DIST_YSKEW];   // Y[pixel][slot]; the rows of pixels 8 .. 15 begin DIST_YSKEW floats later (their slots differ from
-                                           // those of pixels 0 .. 7 by a source row = a multiple of 16: the same LDS banks without the skew)
+    float Ys[16 * XSTRIDE];      // Y[pixel][slot]
     float Qs[(MAXB + 3) / 4 * 256 + 8];   // Q record (Dx0, Dy0, Dd, Dx1) per slot (moved in groups of four blocks: whole groups)
     _Float16 Bs[NAC * 4 * 16 * 8];   // pixel-side operands of the block's 16 pixels: [chunk][kq][pixel][8], -2 x (high | low) parts
     float rp[4 * 16 * 2];        // per wave and pixel: partial |r'|^2, |r|^2 (scaled)
@@ -97,9 +95,6 @@ struct __attribute__((aligned(16))) DistLds {
     int item[2];                 // work item: current / next
     int iflag;                   // the batch item in work: 1 = fp16 overflow in the pack, 2 = outside the domain (guard)
     unsigned char wide[64];      // per batch item: pixel blocks are 16x1 (else 8x2)
-#if DIST_ABL & 4
-    float abl_ray[4];            // (timing only) ray = (x ax + bx, y ay + by, 1), fitted to batch item 0's rays
-#endif
 };
 
 // NCHK = chunks of 32 channels (dist_layout.hpp); NH = groups of 64 planes (ceil(D / 64): 1 or 2), each a pass of its own per
@@ -134,13 +129,6 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     if (tid < 128) { L.ctab[0][tid] = (tid & 1) ? INT_MIN : INT_MAX; L.ctab[1][tid] = (tid & 1) ? INT_MIN : INT_MAX; }
     if (tid < 64) L.wide[tid] = 1;
     if (tid < 2) { L.ired[tid][0] = INT_MAX; L.ired[tid][1] = INT_MIN; }
-#if DIST_ABL & 4
-    if (tid == 0) {
-        const float* r = KARG(const float*, a.rays);
-        const int HW = KARG(int, a.H) * KARG(int, a.W), W = KARG(int, a.W);
-        L.abl_ray[0] = r[1] - r[0]; L.abl_ray[1] = r[0]; L.abl_ray[2] = r[HW + W] - r[HW]; L.abl_ray[3] = r[HW];
-    }
-#endif
     __syncthreads();
     // Shape of the pixel blocks of a batch item: 16x1 where the epipolar lines of view 0 run along the source rows (a
     // rectified pair: the 16 pixels of a row share two source rows), else 8x2 (epipolar_probe.hpp; any choice is correct).
@@ -152,12 +140,6 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     // items of the others.
     const int xcd = blockIdx.x & 7;
     if (blockIdx.x == 0 && tid == 0) KARG(int*, queue)[DIST_NONCE_SLOT] = KARG(int, nonce);   // (diagnostics: whose count DIST_DIRECT_LAST_SLOT holds)
-    // the tags of the fused statistics (pack_dist.hip: fused_stats) are cleared for the next call on this workspace: a captured graph
-    // replays the pack kernel with the same tag (workgroup 1; nobody reads the tags during a sweep)
-    if (blockIdx.x == 1 % gridDim.x) {
-        float* st = const_cast<float*>(KARG(const float*, stats));
-        for (int i = tid; i < KARG(int, a.B) * STATS_VAR; i += 256) reinterpret_cast<int*>(st + (size_t)(i / STATS_VAR) * STATS_STRIDE + STATS_READY)[i % STATS_VAR] = 0;
-    }
     auto band_tiles_of = [&](int q) { const int nt = KARG(int, ntile); return (nt >> 3) + (q < (nt & 7) ? 1 : 0); };
     auto band_first_of = [&](int q) {
         const int nt = KARG(int, ntile), qq = nt >> 3, rr8 = nt & 7;
@@ -202,14 +184,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         b_ = small_idx ? fdiv(tidx, band_tiles) : tidx / band_tiles;
         const int ti = tidx - b_ * band_tiles;
         int tile = band_first_of(q_) + ti;
-        if (DIST_BANDS == 8 && rr8 == 0 && tiles_y_ % 8 == 0 && tiles_y_ * tiles_x == ntile) {
-            // XCD q owns band q of the image's 8 (twice the rows of the half-bands below: the source rows a band reaches
-            // beyond itself are fetched by 8 L2s per item, not 16)
-            const int hb_rows = tiles_y_ / 8;
-            const int cc = small_idx ? fdiv(ti, hb_rows) : ti / hb_rows, r_ = ti - cc * hb_rows;
-            const int col = DIST_COL_ALT ? ((cc & 1) ? tiles_x - 1 - (cc >> 1) : (cc >> 1)) : cc;
-            tile = (q_ * hb_rows + r_) * tiles_x + col;
-        } else if (rr8 == 0 && tiles_y_ % 16 == 0 && tiles_y_ * tiles_x == ntile) {
+        if (rr8 == 0 && tiles_y_ % 16 == 0 && tiles_y_ * tiles_x == ntile) {
             // XCD q owns half-bands q and 8 + q of the image's 16: on a forward motion the cost of a tile grows with its
             // distance from the image centre, and this way every XCD gets the same mix; the heavier half first and, inside
             // a half, columns left to right.  (Any static partition is valid: dry queues steal.)
@@ -217,8 +192,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             const int second = ti >= half_tiles ? 1 : 0, tih = ti - second * half_tiles;
             const int hbi = (q_ < 4) == (second == 0) ? q_ : 8 + q_;
             const int cc = small_idx ? fdiv(tih, hb_rows) : tih / hb_rows, r_ = tih - cc * hb_rows;
-            const int col = DIST_COL_ALT ? ((cc & 1) ? tiles_x - 1 - (cc >> 1) : (cc >> 1)) : cc;
-            tile = (hbi * hb_rows + r_) * tiles_x + col;
+            tile = (hbi * hb_rows + r_) * tiles_x + cc;
         } else if (rr8 == 0 && qq % tiles_x == 0) {   // the band is a whole number of tile rows: column by column
             const int band_rows = qq / tiles_x, tc = small_idx ? fdiv(ti, band_rows) : ti / band_rows;
             tile = (q_ * band_rows + (ti - tc * band_rows)) * tiles_x + tc;
@@ -231,13 +205,6 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
 #define ONE_EACH (KARG(int, one_each) != 0)
     __syncthreads();
 
-    // Persistent grid: the workgroups a CU starts with would run their first passes in lockstep -- every phase of all three at
-    // once on the same pipes; the second and third begin 5 and 11 us later (they drift apart by themselves within a few
-    // passes; -0.9 % / -1.8 % of the headline launch, profiles/r05_ab/staggered_start.txt).  Not where a workgroup runs one item.
-    if (DIST_STAGGER && !ONE_EACH) {
-        const int slot = ((int)blockIdx.x >> 3) / 32 % 3;
-        for (int i = 0; i < slot * DIST_STAGGER; ++i) __builtin_amdgcn_s_sleep(100);
-    }
     // loop-carried scalars of the kernel in ONE register: bit 0 = the slot of L.item in use, bit 1 = the set of row-table arrays of
     // the pass (alternating), bit 2 = the pixel inputs of the next item are on their way to the zone (below), bits 3.. = 1 + the
     // batch item whose tables (means, homography terms, camera constants) are in LDS
@@ -267,7 +234,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     // stores.  The next block reads them back in front of its view loop behind a COUNTED wait: those stores are not waited for.
     // Zone of wave w (floats from w ZW): component i of pixel n's ray at 16 i + n; at 64 + 128 mm + 16 c + n channel
     // 32 mm + 8 w + c of pixel n (c < 8: the wave's channel pairs tq = 4 w + c / 2); the tail round (wave 0) from 4 ZW.
-    constexpr bool PF = DIST_PREFETCH && !(DIST_ABL & 4) && !DIST_ABL_NOB3;
+    constexpr bool PF = DIST_PREFETCH != 0;
     constexpr int ZW = 64 + 128 * NCHK;
     static_assert(4 * ZW + 128 <= (int)(sizeof(Lds::Qs) / sizeof(float)), "the prefetch zone does not fit L.Qs");
     // A block that was not prefetched (a workgroup's first, every block of a workgroup-per-item launch, the block behind a skipped
@@ -372,29 +339,21 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                 const int y = wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1) + (n >> 3);
                 xlive = x < W && y < H;
                 p = min(y, H - 1) * W + min(x, W - 1);
-                if (DIST_ABL & 4) {   // timing only: no pixel loads (how much of the kernel is their exposed latency?)
-#if DIST_ABL & 4
-                    const v4f ar = *reinterpret_cast<const v4f*>(L.abl_ray);
-                    ray[0] = __builtin_fmaf((float)min(x, W - 1), ar.x, ar.y); ray[1] = __builtin_fmaf((float)min(y, H - 1), ar.z, ar.w); ray[2] = 1.0f;
-#pragma unroll
-                    for (int mm = 0; mm < MP; ++mm)
-                        for (int i = 0; i < 2; ++i) rv[mm][i] = L.dcl[(32 * mm + 2 * tq + i + n) & 63];
-#endif
-                } else if (PF) {
+                if (PF) {
                     if (!pf) dma_pixels(wave, b, p * 4);   // (read back in front of the view loop)
                 } else {
 #pragma unroll
-                for (int i = 0; i < 3; ++i) ray[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rray, p * 4, i * HW * 4, 0));
+                    for (int i = 0; i < 3; ++i) ray[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rray, p * 4, i * HW * 4, 0));
 #pragma unroll
-                for (int mm = 0; mm < MP; ++mm) {
-                    // (the tail round's loads are issued by every wave -- beyond the descriptor in waves 1..3 -- : registers that
-                    //  only wave 0 loads made the compiler wait, at the top of every trip, for the previous trip's stores)
-                    const bool mine = mm < NCHK || wave == 0;
+                    for (int mm = 0; mm < MP; ++mm) {
+                        // (the tail round's loads are issued by every wave -- beyond the descriptor in waves 1..3 -- : registers that
+                        //  only wave 0 loads made the compiler wait, at the top of every trip, for the previous trip's stores)
+                        const bool mine = mm < NCHK || wave == 0;
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        rv[mm][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                            rref, mine && 2 * tq + i < C - 32 * mm ? ((2 * tq + i) * HW + p) * 4 : OOB, 32 * mm * HW * 4, 0));
-                }
+                        for (int i = 0; i < 2; ++i)
+                            rv[mm][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                rref, mine && 2 * tq + i < C - 32 * mm ? ((2 * tq + i) * HW + p) * 4 : OOB, 32 * mm * HW * 4, 0));
+                    }
                 }
             }
             DSTAMP(1)   // item set-up, pixel loads issued
@@ -568,12 +527,6 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             plane_sample_pos_fast(xf, t2a, t2b, t2c, dk[j], c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, ix, iy);
                             cell[j] = cell_of(ix, iy, W, H, fw[j], fn[j]);
                             if (k >= D || !xlive || !mine) cell[j] = NO_CELL;
-                            if (DIST_ABL & 1) {   // timing only: the position chain a second time (how much of the kernel is vector issue?)
-                                float ix2, iy2, f2, g2;
-                                plane_sample_pos_fast(xf, t2a, t2b, t2c, dk[j] * 1.0001f, c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, ix2, iy2);
-                                const int c2 = cell_of(ix2, iy2, W, H, f2, g2);
-                                asm volatile("" :: "v"(c2), "v"(f2), "v"(g2));
-                            }
                         }
                         // (pinned: the optimiser otherwise carries the positions AND their floors to the combine instead of the fractions)
 #pragma unroll
@@ -670,14 +623,11 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                         }
                         centred = true;
                     }
-                    // the pixel-side operands of lane (n, kq): high[NCHK], low[NCHK], tail -- from LDS once per pass, or (DIST_BV_LDS)
-                    // chunk by chunk in front of the multiplications of every block: twenty registers for a second texel operand set
+                    // the pixel-side operands of lane (n, kq): high[NCHK], low[NCHK], tail -- from LDS once per pass
                     h8 Bv[NAC];
                     const _Float16* const bsl = &L.Bs[(kq * 16 + n) * 8];
-                    if (!DIST_BV_LDS) {
 #pragma unroll
-                        for (int i = 0; i < NAC; ++i) Bv[i] = *reinterpret_cast<const h8*>(bsl + i * 512);
-                    }
+                    for (int i = 0; i < NAC; ++i) Bv[i] = *reinterpret_cast<const h8*>(bsl + i * 512);
                     // ---- the row table, cut into blocks of 16 texels: every wave for itself, lane = texel row yb + lane -----
                     const int yb = __builtin_amdgcn_readfirstlane(L.ired[par][0]), yt = __builtin_amdgcn_readfirstlane(L.ired[par][1]);
                     int nb = 0, lo = 0, nblk = 0, fb = 0;
@@ -739,8 +689,8 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             boff = lane < nb ? ((yb + rho + dist::RING) * (Wp / dist::GROUP) + (xs + dist::RING) / dist::GROUP) * GB : OOB;
                         }
                         // (the tail chunk: planes high | low | high again | specials = the tail's planes 0, 1, 0, 2 for K slices 0 .. 3)
-                        auto fetch = [&](int set, int i, int soff) {   // chunk i: planes 4 i .. 4 i + 3 (the lane's: + kq, in voffA)
-                            if (DIST_ABL & 2) { S[set][i] = *reinterpret_cast<const h8*>(bsl + i * 512); return; }   // timing only: no texel loads
+                        // (the lane's constants captured by value: by reference the kernel took a scalar register more)
+                        auto fetch = [&S, rsrc, voffA, kq](int set, int i, int soff) {   // chunk i: planes 4 i .. 4 i + 3 (the lane's: + kq, in voffA)
                             const int voff = i == NAC - 1 ? voffA - (kq == 2 ? 2 * PB : (kq == 3 ? PB : 0)) : voffA;
                             S[set][i] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff + i * 4 * PB, 0));
                         };
@@ -751,7 +701,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                         };
                         // wave w: blocks w q .. w q + q - 1 (consecutive blocks: consecutive slots)
                         const int q = (nb + 3) >> 2, b0 = wave * q, b1 = min(nb, b0 + q);
-                        if (DIST_XPRIO) __builtin_amdgcn_s_setprio(DIST_XPRIO);
+                        __builtin_amdgcn_s_setprio(1);   // (the matrix phase ahead of the other workgroups' vector phases)
                         if (go) {
 #pragma unroll
                             for (int u = 0; u < NS; ++u)
@@ -790,40 +740,24 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                                     const bool more = bj + NS < b1;   // uniform
                                     const int soff = more ? __builtin_amdgcn_readlane(boff, bj + NS) : 0;
                                     v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
-                                    if (DIST_BV_LDS) {
 #pragma unroll
-                                        for (int c = 0; c < NCHK; ++c) {
-                                            const h8 bh = *reinterpret_cast<const h8*>(bsl + c * 512);
-                                            const h8 bl = *reinterpret_cast<const h8*>(bsl + (NCHK + c) * 512);
-                                            acc = DIST_MFMA(S[u][c], bh, acc);
-                                            acc = DIST_MFMA(S[u][NCHK + c], bh, acc);
-                                            if (more) fetch(u, NCHK + c, soff);
-                                            acc = DIST_MFMA(S[u][c], bl, acc);
-                                            if (more) fetch(u, c, soff);
-                                        }
-                                        const h8 bt = *reinterpret_cast<const h8*>(bsl + (NAC - 1) * 512);
-                                        acc = DIST_MFMA(S[u][NAC - 1], bt, acc);
-                                        if (more) fetch(u, NAC - 1, soff);
-                                    } else {
-#pragma unroll
-                                        for (int c = 0; c < NCHK; ++c) {
-                                            acc = DIST_MFMA(S[u][c], Bv[c], acc);
-                                            acc = DIST_MFMA(S[u][c], Bv[NCHK + c], acc);
-                                            if (more) fetch(u, c, soff);
-                                            acc = DIST_MFMA(S[u][NCHK + c], Bv[c], acc);
-                                            if (more) fetch(u, NCHK + c, soff);
-                                        }
-                                        acc = DIST_MFMA(S[u][NAC - 1], Bv[NAC - 1], acc);
-                                        if (more) fetch(u, NAC - 1, soff);
+                                    for (int c = 0; c < NCHK; ++c) {
+                                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][c], Bv[c], acc, 0, 0, 0);
+                                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][c], Bv[NCHK + c], acc, 0, 0, 0);
+                                        if (more) fetch(u, c, soff);
+                                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][NCHK + c], Bv[c], acc, 0, 0, 0);
+                                        if (more) fetch(u, NCHK + c, soff);
                                     }
+                                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][NAC - 1], Bv[NAC - 1], acc, 0, 0, 0);
+                                    if (more) fetch(u, NAC - 1, soff);
                                     // Y[texel 4 kq ..][pixel n] of the block
-                                    *reinterpret_cast<v4f*>(&L.Ys[n * XSTRIDE + (n >> 3) * DIST_YSKEW + 16 * bj + 4 * kq]) = acc;
+                                    *reinterpret_cast<v4f*>(&L.Ys[n * XSTRIDE + 16 * bj + 4 * kq]) = acc;
                                 }
                             }
                             DSTAMP(6)   // slots, loads + multiplications
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's Q records have landed in LDS
                         }
-                        if (DIST_XPRIO) __builtin_amdgcn_s_setprio(0);
+                        __builtin_amdgcn_s_setprio(0);
                     }
                     DSTAMP(7)   // wait for the Q records
                     PDEPTH_LDS_BARRIER();   // Y and the Q records of the pass are complete
@@ -839,7 +773,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                         if (attempt != 0) failmask |= 1u << ((v * NH + h) * 2 + attempt - 1);
                     } else if (attempt == 0 || (wave >> 1) == attempt - 1) {   // (`mine`, formed again: kept from the top of the attempt it is a lane mask in two scalar registers)
                         const float cinv = L.cst[7];
-                        const float* yr = &L.Ys[n * XSTRIDE + (n >> 3) * DIST_YSKEW];
+                        const float* yr = &L.Ys[n * XSTRIDE];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             // (no tap inside the image: the taps read zero, cost = |r|^2 -- and NaN where the position itself
@@ -921,7 +855,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             const long long t10 = dist::texel_offset(C, H, W, 0, cyy + dist::RING + 1, cxx + dist::RING), t11 = dist::texel_offset(C, H, W, 0, cyy + dist::RING + 1, cxx + dist::RING + 1);
                             const long long pstep = dist::texel_offset(C, H, W, 1, 0, 0);   // from a plane to the next
                             float part = 0.0f;
-#pragma unroll DIST_DIRECT_UNROLL
+#pragma unroll 1   // (one channel group's taps in flight; 3 or 9: 168 registers under the launch bound and config 5 8 % slower)
                             for (int g = 0; g < 4 * NCHK + 1; ++g) {
                                 // planes of the group's high and low parts; the pixel's: chunk g >> 2 (tail: 2 NCHK), K slice g & 3 (tail: 0 | 2)
                                 const bool tail = g == 4 * NCHK;
@@ -965,7 +899,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                 const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)(cost_out + (size_t)b * D * (HW4 >> 2)), 0, D * HW4, 0x00020000);
 #pragma unroll
                 for (int j = 0; j < NC; ++j)   // (planes beyond D lie beyond the descriptor: dropped)
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, cost[j]), rc, ovoff, pl0 + (64 * (j >> 2) + (j & 3)) * HW4, DIST_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, cost[j]), rc, ovoff, pl0 + (64 * (j >> 2) + (j & 3)) * HW4, 0);
             }
             float* const logp_out = KARG(float*, a.logp_out);
             float* const depth_out = KARG(float*, a.depth_out);
@@ -992,7 +926,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                 }
                 DSTAMP(10)   // cost stores, partial softmax
                 publish_next();
-                if (!DIST_ABL_NOB3) PDEPTH_LDS_BARRIER();
+                PDEPTH_LDS_BARRIER();
                 {
                     v4f part[4];
 #pragma unroll
@@ -1018,7 +952,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
 #pragma unroll
                         for (int j = 0; j < NC; ++j)
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, (cost[j] - M) - ls), rl, ovoff,
-                                                                  pl0 + (64 * (j >> 2) + (j & 3)) * HW4, DIST_STORE_AUX);
+                                                                  pl0 + (64 * (j >> 2) + (j & 3)) * HW4, 0);
                     }
                     if (depth_out && xlive && tq == 0) depth_out[(size_t)b * (HW4 >> 2) + p] = E / S_;
                 }
@@ -1127,7 +1061,7 @@ hipError_t launch_sweep_dist(const SweepArgs& a, void* workspace, hipStream_t st
     int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + sweep_ws_flag_only_bytes(a.B, a.H, a.W));
     const float* stats = reinterpret_cast<const float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
     if (!packed_ready) {
-        hipError_t e = launch_pack_dist(a, workspace, stream, /*fuse_stats=*/true);
+        hipError_t e = launch_pack_dist(a, workspace, stream);
         if (e != hipSuccess) return e;
     }
     const int nck = dist::nchk(a.C);
