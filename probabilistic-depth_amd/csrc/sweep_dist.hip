@@ -27,8 +27,11 @@
 //       A pass whose planes need more than MAXB blocks or 64 rows (extreme poses), and every pass of a batch item whose
 //       statistics put it outside the domain of the distance form (guard below), is evaluated directly by the same
 //       workgroup behind the view loop, in the reference's own form on the packed features.
-//   scheduling.  Persistent workgroups pull 16x4 tiles from per-XCD queues (balanced half-bands, stealing); the last
-//       workgroup to leave zeroes the queue counters: a call on an already packed source is this one launch.
+//   scheduling.  Persistent workgroups pull pixel blocks -- 16 pixels, 16x1 or 8x2: the four of a 16x4 tile are consecutive
+//       items -- from per-XCD queues (balanced half-bands, stealing), one item ahead; thread 0 decodes the next item once for
+//       the workgroup, under the current block's pixel loads, into a record in LDS that every wave starts the block from.
+//       Launches of up to six items per resident workgroup have no queue: a workgroup per item.  The last workgroup to
+//       leave zeroes the queue counters: a call on an already packed source is this one launch.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -92,7 +95,7 @@ struct __attribute__((aligned(16))) DistLds {
     int ctab[2][64 * 2];         // per cell row (modulo 64): (min, max) x0; two sets, alternating by pass
     int ired[2][2];              // min / max cell row of the pass; two sets
     int brow[MAXB + 2];          // per block of the pass: its row (written alike by every wave, read back by the same wave)
-    int item[2];                 // work item: current / next
+    v4i rec[2];                  // decoded work item, current / next (ItemRec below: thread 0 writes, every wave reads)
     int iflag;                   // the batch item in work: 1 = fp16 overflow in the pack, 2 = outside the domain (guard)
     unsigned char wide[64];      // per batch item: pixel blocks are 16x1 (else 8x2)
 };
@@ -172,6 +175,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     };
     // floor(nn / dd) for 0 <= nn < 2^22, 0 < dd (an integer divide costs ~40 dependent instructions)
     auto fdiv = [](int nn, int dd) { return (int)(((float)nn + 0.5f) * __builtin_amdgcn_rcpf((float)dd)); };
+    // (thread 0 only, in publish(): no wave decodes an item for itself)
     auto decode = [&](int item, int& b_, int& tx_, int& ty_, int& sub_) {
         const int ntile = KARG(int, ntile), tiles_x = KARG(int, tiles_x), H = KARG(int, a.H);
         const int qq = ntile >> 3, rr8 = ntile & 7;
@@ -205,25 +209,64 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
 #define ONE_EACH (KARG(int, one_each) != 0)
     __syncthreads();
 
-    // loop-carried scalars of the kernel in ONE register: bit 0 = the slot of L.item in use, bit 1 = the set of row-table arrays of
+    // loop-carried scalars of the kernel in ONE register: bit 0 = the slot of L.rec in use, bit 1 = the set of row-table arrays of
     // the pass (alternating), bit 2 = the pixel inputs of the next item are on their way to the zone (below), bits 3.. = 1 + the
     // batch item whose tables (means, homography terms, camera constants) are in LDS
     int state = 0;
     int n_direct = 0;     // (thread 0) pixel blocks evaluated directly
-    // The queue runs one item ahead: (thread 0) the atomic that pops item i + 1 is issued when item i starts, its result is
-    // resolved and published in LDS in front of the LAST barrier of item i -- the workgroup goes from one pixel block to
-    // the next without a barrier of the queue's own.
+    // The queue runs one item ahead: (thread 0) the atomic that pops item i + 1 is issued a block ahead, its result is resolved,
+    // DECODED and published in LDS (L.rec) in front of the LAST barrier of item i -- the workgroup goes from one pixel block to
+    // the next without a barrier of the queue's own, and no wave decodes an item for itself.
     int got_own = (tid == 0 && !ONE_EACH) ? atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1) : (int)(blockIdx.x >> 3);
-    // resolve_next(): BEFORE the block's stores are issued -- the result of the atomic is waited for with a vmcnt, and memory
+    // resolve_next(): at the top of the block (record_next() below says why), at any rate BEFORE the block's stores are issued -- the result of the atomic is waited for with a vmcnt, and memory
     // operations complete in issue order: behind the stores that wait is the stores' whole latency, for thread 0's wave and, at
     // the next barrier, for the workgroup (2 us per pixel block when it was there).
     int next_item = -1;
     // ("thread 0" asked of a value the optimiser cannot see through: the lane mask of `tid == 0` is not kept across the kernel)
     auto resolve_next = [&]() { if (opaque_v((int)threadIdx.x) == 0) next_item = ONE_EACH ? -1 : resolve(got_own); };
+    // The item record: thread 0 decodes an item ONCE for the workgroup and leaves in LDS what the top of the item needs of it --
+    //   .x  the raw item (queue << 28 | index), -1: every queue is dry (nothing else of the record is valid then)
+    //   .y  the batch item b
+    //   .z  (y0 << 16) | x0: the first pixel of the block, the tile's block (sub) and the item's block shape applied
+    //   .w  REC_WIDE: blocks of the batch item are 16x1 (else 8x2); REC_BELOW: the block lies below the image (skipped);
+    //       REC_FIRST: block 0 of tile 0 (the one that marks a routed batch item)
+    // -- one 16-byte LDS read and four v_readfirstlane per wave in place of a decode per wave (a dozen kernel-argument reads, each
+    // a scalar round trip, three or four reciprocal divisions and the half-band arithmetic: profiles/r10_item_record/).
+    // L.wide is complete behind the __syncthreads() above.
+    constexpr int REC_WIDE = 1, REC_BELOW = 2, REC_FIRST = 4;
+    auto publish = [&](int slot, int item) {   // (thread 0, in front of a workgroup barrier)
+        v4i r = v4i{item, 0, 0, 0};
+        if (item >= 0) {
+            int b, tx, ty, sub;
+            decode(item, b, tx, ty, sub);
+            const bool wide = b < 64 ? L.wide[b] != 0 : false;
+            const int x0 = wide ? tx * 16 : tx * 16 + 8 * (sub & 1), y0 = wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1);
+            r.y = b;
+            r.z = (y0 << 16) | x0;   // (W, H <= 32760: sweep_dist_supports)
+            r.w = (wide ? REC_WIDE : 0) | (y0 >= KARG(int, a.H) ? REC_BELOW : 0) | ((tx | ty | sub) == 0 ? REC_FIRST : 0);
+        }
+        L.rec[slot] = r;
+    };
+    // record_next(): the next item's record into the slot the current item does not use -- nobody has read that slot since the top
+    // of the previous item, several barriers back.  Where (DIST_DECODE_EARLY): right behind resolve_next(), which then stands
+    // at the top of the item behind the issue of the block's pixel loads (the pop it reads was waited for at the end of the
+    // previous block: PDEPTH_POP_WAIT), so that thread 0's decode runs while every wave waits for those loads anyway; and the
+    // pop of the item after the next is issued there as well: it has the whole block to return, and the waits for it at the
+    // end of the block find it done.  (Not with the prefetch, whose counted wait at the top of a block counts the vector-memory
+    // operations behind the DMA: the pop stays in publish_next().)  Else in publish_next(), in front of the block's last
+    // barrier, with resolve_next() in front of the block's stores.  profiles/r10_item_record/ has both.
+    constexpr bool EARLY = DIST_DECODE_EARLY != 0;
+    constexpr bool POP_EARLY = EARLY && DIST_PREFETCH == 0;
+    auto record_next = [&]() {
+        if (opaque_v((int)threadIdx.x) == 0) {
+            publish(state & 1, next_item);
+            if (POP_EARLY && !ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
+        }
+    };
     auto publish_next = [&]() {   // (thread 0, in front of a workgroup barrier)
         if (opaque_v((int)threadIdx.x) == 0) {
-            L.item[state & 1] = next_item;
-            if (!ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
+            if (!EARLY) publish(state & 1, next_item);
+            if (!POP_EARLY && !ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
         }
     };
     // Prefetch (DIST_PREFETCH).  A pixel block's own inputs -- its 16 rays and the reference features of its pixels -- were
@@ -266,22 +309,21 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             }
         }
     };
-    auto prefetch_next = [&](int wave) {   // (every thread, behind a workgroup barrier: the next item is in L.item)
-        const int nitem = __builtin_amdgcn_readfirstlane(L.item[state & 1]);
-        if (nitem < 0) return;
-        int b, tx, ty, sub;
-        decode(nitem, b, tx, ty, sub);
+    auto prefetch_next = [&](int wave) {   // (every thread, behind a workgroup barrier: the next item's record is in L.rec)
+        const v4i nrec = L.rec[state & 1];
+        if (__builtin_amdgcn_readfirstlane(nrec.x) < 0) return;
+        const int fl = __builtin_amdgcn_readfirstlane(nrec.w);
+        if (fl & REC_BELOW) return;   // (below the image: the item is skipped)
+        const int b = __builtin_amdgcn_readfirstlane(nrec.y), xy = __builtin_amdgcn_readfirstlane(nrec.z);
         const int H = KARG(int, a.H), W = KARG(int, a.W);
-        const bool wide = b < 64 ? L.wide[b] != 0 : false;
-        if ((wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1)) >= H) return;   // (below the image: the item is skipped)
         const int n = opaque_v((int)threadIdx.x) & 15;
-        const int x = wide ? tx * 16 + n : tx * 16 + 8 * (sub & 1) + (n & 7);
-        const int y = wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1) + (n >> 3);
+        const int x = (xy & 0xffff) + ((fl & REC_WIDE) ? n : (n & 7));
+        const int y = (xy >> 16) + ((fl & REC_WIDE) ? 0 : (n >> 3));
         dma_pixels(wave, b, (min(y, H - 1) * W + min(x, W - 1)) * 4);
         state |= 4;
     };
     if (tid == 0) {
-        L.item[0] = ONE_EACH ? (got_own < items_of(xcd) ? (xcd << 28) | got_own : -1) : resolve(got_own);
+        publish(0, ONE_EACH ? (got_own < items_of(xcd) ? (xcd << 28) | got_own : -1) : resolve(got_own));
         if (!ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
     }
     PDEPTH_LDS_BARRIER();   // the first item is published
@@ -297,21 +339,21 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         // (a plain LDS read: behind the barrier's memory clobber it cannot be hoisted.  Through a volatile generic pointer --
         //  round 5 -- it was a FLAT load, and a flat load is waited for with vmcnt(0): every item began by waiting out the
         //  previous pixel block's stores, 2 us per item)
-        const int item = __builtin_amdgcn_readfirstlane(L.item[state & 1]);
+        const v4i rec = L.rec[state & 1];   // (one 16-byte read: the item as thread 0 decoded it)
         state ^= 1;
         const int pf = state & 4;   // (the item's pixel inputs are on their way to the zone)
         state ^= pf;
-        if (item < 0) break;
+        if (__builtin_amdgcn_readfirstlane(rec.x) < 0) break;
         DSTAMP(0)   // queue
         const int wave = opaque_s(__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6));   // (per item: its multiples are not kept -- spilled -- across the kernel)
-        int b, tx, ty, sub;
-        decode(item, b, tx, ty, sub);
+        const int b = __builtin_amdgcn_readfirstlane(rec.y), xy0 = __builtin_amdgcn_readfirstlane(rec.z), recfl = __builtin_amdgcn_readfirstlane(rec.w);
         const int H = KARG(int, a.H), W = KARG(int, a.W), V = KARG(int, a.V), C = KARG(int, a.C), D = KARG(int, a.D);
-        const bool wide = b < 64 ? L.wide[b] != 0 : false;
+        const bool wide = (recfl & REC_WIDE) != 0;
 
         {
-            if ((wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1)) >= H) {   // the block lies below the image (uniform)
+            if (recfl & REC_BELOW) {   // the block lies below the image (uniform)
                 resolve_next();
+                if (EARLY) record_next();
                 publish_next();
                 PDEPTH_LDS_BARRIER();
                 PDEPTH_POP_WAIT(0);
@@ -335,8 +377,8 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                     __builtin_amdgcn_make_buffer_rsrc((void*)(KARG(const float*, a.rays) + (size_t)b * 3 * HW), 0, 3 * HW * 4, 0x00020000);
                 const __amdgpu_buffer_rsrc_t rref = __builtin_amdgcn_make_buffer_rsrc(
                     (void*)(KARG(const float*, a.ref) + (size_t)b * KARG(long long, a.ref_bstride)), 0, C * HW * 4, 0x00020000);
-                const int x = wide ? tx * 16 + n : tx * 16 + 8 * (sub & 1) + (n & 7);
-                const int y = wide ? ty * 4 + sub : ty * 4 + 2 * (sub >> 1) + (n >> 3);
+                const int x = (xy0 & 0xffff) + (wide ? n : (n & 7));
+                const int y = (xy0 >> 16) + (wide ? 0 : (n >> 3));
                 xlive = x < W && y < H;
                 p = min(y, H - 1) * W + min(x, W - 1);
                 if (PF) {
@@ -356,6 +398,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                     }
                 }
             }
+            if (EARLY) { resolve_next(); record_next(); }   // (thread 0: under the latency of the loads above)
             DSTAMP(1)   // item set-up, pixel loads issued
             // (the pixel loads above are in flight while the tables of a new batch item are built: where every workgroup runs ONE
             //  item -- the model-real shapes -- that is a memory round trip off a 13 us launch)
@@ -447,11 +490,11 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                     // (the item's first block marks it and counts ALL its blocks for the diagnostics: the count is merged into
                     //  the workspace by a compare-and-swap chain per workgroup at the end of the kernel -- one per pixel block was
                     //  0.9 ms of serialised atomics on a routed launch)
-                    if (opaque_v((int)threadIdx.x) == 0 && tx == 0 && ty == 0 && sub == 0) {
+                    if (opaque_v((int)threadIdx.x) == 0 && (recfl & REC_FIRST)) {
                         reinterpret_cast<int*>(const_cast<float*>(KARG(const float*, stats)) + (size_t)b * STATS_STRIDE + STATS_FLAGS)[1] = 1;
                         n_direct += KARG(int, tiles_x) * (wide ? H : 2 * ((H + 1) >> 1));
                     }
-                    resolve_next();
+                    if (!EARLY) resolve_next();
                     publish_next();
                     PDEPTH_LDS_BARRIER();
                     PDEPTH_POP_WAIT(0);
@@ -891,7 +934,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             // (buffer stores: one 32-bit lane offset, the plane as the scalar offset: plane 64 h + 16 wave + 4 kq + j)
             // (the planes' scalar offsets are formed here, from a value the optimiser cannot trace back: hoisted to the top of
             //  the item they were four spilled scalars, read back lane by lane with five wait states each in front of a store)
-            resolve_next();
+            if (!EARLY) resolve_next();
             const int HW4 = KARG(int, a.H) * KARG(int, a.W) * 4;   // (re-read: HW * 4 kept from the top of the block was a spilled scalar)
             const int ovoff = xlive ? 4 * kq * HW4 + p * 4 : OOB;
             const int pl0 = 16 * wave * HW4;

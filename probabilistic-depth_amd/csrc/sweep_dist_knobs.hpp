@@ -24,7 +24,10 @@
 #define DIST_QSTRIDE 64    // ints between the queue counters of two XCDs: memory-side atomics on one line are served one by one, ~13 ns each
 #endif
 #ifndef DIST_PREFETCH
-#define DIST_PREFETCH 0    // 1: the next pixel block's rays and reference features by LDS-DMA behind the current one's last barrier (bit-identical, 5 % slower: profiles/r07_ab/)
+#define DIST_PREFETCH 0    // 1: the next pixel block's rays and reference features by LDS-DMA behind the current one's last barrier (bit-identical; 1.6 % slower on the item record, 5 % before it: profiles/r10_item_record/, r07_ab/)
+#endif
+#ifndef DIST_DECODE_EARLY
+#define DIST_DECODE_EARLY 1   // thread 0 decodes the next item and pops the one after it at the top of the current block, under its pixel loads (0: in front of the block's last barrier; headline alike, --pose stereo 1 % slower: profiles/r10_item_record/)
 #endif
 #ifndef DIST_ONE_EACH_X
 #define DIST_ONE_EACH_X 6  // a workgroup per item, no queue, up to this many items per resident workgroup (2 .. 24: the large shapes are indifferent; profiles/r06_ab/)
