@@ -57,7 +57,7 @@ extern "C" {
                                 *    library must be re-packed; PDEPTH_ALGO_CORR is refused (PDEPTH_E_ARG; since retired with CELLS and MFMA);
                                 *    backward-compatible additions within 6: pdepth_sweep_backward_f32, pdepth_dpv_reduce_backward_f32,
                                 *    pdepth_dpv_expect_backward_f32; pdepth_dpv_soft_ce_workspace_bytes, pdepth_dpv_soft_ce_f32,
-                                *    pdepth_dpv_soft_ce_backward_f32 */
+                                *    pdepth_dpv_soft_ce_backward_f32; pdepth_depth_metrics_workspace_bytes, pdepth_depth_metrics_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -448,6 +448,37 @@ int pdepth_dpv_soft_ce_f32(const float *logp, const float *d_candi, const float 
 int pdepth_dpv_soft_ce_backward_f32(const float *logp, const float *d_candi, const float *label, const float *depth_gt,
                                     float variance, float pow, const float *mask, const float *count, int32_t B, int32_t D,
                                     int32_t H, int32_t W, const float *g_loss, const float *g_depth, float *g_logp, void *stream);
+
+/*
+ * Evaluation metrics: the KITTI devkit's nine depth errors per item of a batch, on the device (the tail of the evaluation loop,
+ * trainer/default_trainer.py:247-256, composed with img_utils.depth_error, utils/img_utils.py:17-22, and depthError,
+ * external/deval_lib/src/evaluate_depth.h:20-121; no copy of a depth map to the host).
+ *   Exactly one of the two predictions is non-NULL:
+ *   pred     [B,H,W] depth maps (any shape), or
+ *   logp     [B,D,H,W] contiguous fp32 log-probabilities with d_candi [D]: the prediction is the expectation
+ *            sum_d d_d exp(logp[b,d,y,x]), formed in registers from one read of the volume, the bits of
+ *            pdepth_dpv_expect_f32(bv_log = 1); depth [B,H,W] (or NULL = not wanted; volume form only) receives it from the same pass;
+ *   truth    [B,H,W];  mask [B,H,W] or NULL;  clamp_max <= 0: no clamp (the trainer passes the last depth candidate).
+ *     p = pred[b,y,x] mask[b,y,x]                          (no mask: p = pred)
+ *     t = truth[b,y,x];  t = clamp_max where t >= clamp_max;  t = -1 where t == 0
+ *     valid <=> p > 0                                       (p == 0 is invalid, a NaN is invalid); n = number of valid pixels
+ *     e = |p - t|, ei = |1/p - 1/t|, s = log p - log t, el = |s|, sums over the valid pixels:
+ *     metrics[b] = { mae = S e / n, rmse = sqrt(S e^2 / n), inverse mae = S ei / n, inverse rmse = sqrt(S ei^2 / n),
+ *                    log mae = S el / n, log rmse = sqrt(S el^2 / n), scale invariant log = sqrt(S el^2 / n - (S s)^2 / n^2),
+ *                    abs relative = S (e / p) / n, squared relative = S (e^2 / p^2) / n }
+ *   The reference's argument order is kept: depth_error(predicted, truth) hands its arguments to depthError(D_gt, D_ipol) in
+ *   that order, so validity is decided by the masked prediction and the two relative errors have the prediction as denominator
+ *   (not the ground truth).  A valid pixel whose truth is 0 or negative makes the log and inverse metrics of its item NaN, as in
+ *   the reference.  Where the reference throws (n == 0) the nine values of that item are NaN and count[b] = 0.
+ *   metrics [B,9], count [B] (float, = n).  The per-pixel terms are fp32, their sums fp64; reproducible bit for bit: one record
+ *   (nine sums and the count) per workgroup of 256 pixels in the workspace, added in a fixed order by a second launch -- no atomics.
+ *   workspace: pdepth_depth_metrics_workspace_bytes(B, H, W) bytes (80 bytes per 256 pixels), 256-byte aligned; 0 for
+ *   non-positive sizes.
+ */
+size_t pdepth_depth_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_depth_metrics_f32(const float *logp, const float *pred, const float *d_candi, const float *truth, const float *mask,
+                             float clamp_max, int32_t B, int32_t D, int32_t H, int32_t W, float *metrics, float *count,
+                             float *depth, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "pdepth_pack_views_f32", "pdepth_sweep_centres_source", "pdepth_sweep_source_layout",
     "pdepth_sweep_backward_f32", "pdepth_dpv_reduce_backward_f32", "pdepth_dpv_expect_backward_f32",
     "pdepth_dpv_soft_ce_workspace_bytes", "pdepth_dpv_soft_ce_f32", "pdepth_dpv_soft_ce_backward_f32",
+    "pdepth_depth_metrics_workspace_bytes", "pdepth_depth_metrics_f32",
 )
 
 
@@ -157,6 +158,12 @@ def load():
         lib.pdepth_dpv_soft_ce_backward_f32.argtypes = [c_void_p] * 4 + [c_float, c_float, c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 4
         for fn in ("pdepth_dpv_soft_ce_f32", "pdepth_dpv_soft_ce_backward_f32"):
             getattr(lib, fn).restype = c_int
+    # ... and so do the evaluation metrics (csrc/metrics.hip)
+    if hasattr(lib, "pdepth_depth_metrics_f32") or path == LIB_PATH:
+        lib.pdepth_depth_metrics_workspace_bytes.restype = c_size_t
+        lib.pdepth_depth_metrics_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+        lib.pdepth_depth_metrics_f32.restype = c_int
+        lib.pdepth_depth_metrics_f32.argtypes = [c_void_p] * 5 + [c_float] + [c_int32] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
     for fn in ("pdepth_sweep_cost_f32", "pdepth_sweep_dpv_f32", "pdepth_dpv_reduce_f32",
                "pdepth_dpv_expect_f32", "pdepth_warp_feature_f32", "pdepth_sample_coords_f32",
                "pdepth_dpv_fuse_f32", "pdepth_correlation_forward_f32", "pdepth_inverse_warp_f32",
@@ -924,3 +931,60 @@ def dpv_soft_ce_backward(logp, d_candi, count, label=None, depth_gt=None, varian
                                                  _stream(logp.device))
     _check(rc, lib)
     return out
+
+
+# ---- evaluation metrics (ops.depth_metrics) -----------------------------------------------------------------------------------
+def _metrics_entry(lib, name):
+    """A metrics entry of the loaded library; a library linked without csrc/metrics.o is an error here, there is no other path."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{name}: the loaded library was linked without csrc/metrics.hip; there is no fallback")
+    return fn
+
+
+def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_max=None, want_depth=False):
+    """truth [B,H,W] + (pred [B,H,W] | logp [B,D,H,W], d_candi [D]) [+ mask [B,H,W]] -> (metrics [B,9], count [B], depth [B,H,W] |
+    None): pdepth_depth_metrics_f32 on the current stream, no host synchronisation.  clamp_max None or <= 0: no clamp."""
+    who = "depth_metrics"
+    lib = load()
+    _no_autograd(who, truth, pred, logp, mask)
+    if (pred is None) == (logp is None):
+        raise RuntimeError(f"{who}: give exactly one prediction, pred [B,H,W] or logp [B,D,H,W]")
+    if truth.dim() != 3:
+        raise RuntimeError(f"{who}: truth must be [B,H,W]")
+    B, H, W = truth.shape
+    D = 0
+    if logp is not None:
+        if logp.dim() != 4:
+            raise RuntimeError(f"{who}: logp must be [B,D,H,W]")
+        D = logp.shape[1]
+        _shape(logp, (B, D, H, W), "logp", who)
+        if d_candi is None or d_candi.numel() != D:
+            raise RuntimeError(f"{who}: d_candi has {0 if d_candi is None else d_candi.numel()} entries, volume has D={D}")
+    else:
+        _shape(pred, (B, H, W), "pred", who)
+        if want_depth:
+            raise RuntimeError(f"{who}: want_depth belongs to the volume form (the depth map form is given its map)")
+    if mask is not None:
+        _shape(mask, (B, H, W), "mask", who)
+    tensors = []
+    for nm, t in (("truth", truth), ("pred", pred), ("logp", logp), ("d_candi", d_candi if logp is not None else None), ("mask", mask)):
+        if t is not None:
+            if not t.is_cuda:
+                raise RuntimeError(f"{nm}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+            t = t.contiguous().float()
+        tensors.append(t)
+    truth, pred, logp, d_candi, mask = tensors
+    dev = truth.device
+    out = torch.empty(B * 10, dtype=torch.float32, device=dev)
+    metrics, count = out[:B * 9].view(B, 9), out[B * 9:]
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
+    ws_bytes = _metrics_entry(lib, "pdepth_depth_metrics_workspace_bytes")(B, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _metrics_entry(lib, "pdepth_depth_metrics_f32")(_ptr(logp), _ptr(pred), _ptr(d_candi), truth.data_ptr(), _ptr(mask),
+                                                             float(clamp_max) if clamp_max is not None else 0.0, B, D, H, W,
+                                                             metrics.data_ptr(), count.data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
+                                                             _stream(dev))
+    _check(rc, lib)
+    return metrics, count, depth

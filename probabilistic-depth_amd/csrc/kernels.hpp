@@ -154,6 +154,13 @@ hipError_t launch_dpv_soft_ce_backward(const float* logp, const float* d_candi, 
                                        float variance, float pw, const float* mask, const float* count, int B, int D, int H, int W,
                                        const float* g_loss, const float* g_depth, float* g_logp, hipStream_t stream);
 
+// metrics.hip: the devkit's nine depth errors per item of a batch.  Exactly one of logp [B,D,H,W] / pred [B,H,W] is non-null;
+// mask and depth may be nullptr, clamp_max <= 0 = no clamp
+size_t depth_metrics_workspace_bytes(int B, int H, int W);
+hipError_t launch_depth_metrics(const float* logp, const float* pred, const float* d_candi, const float* truth, const float* mask,
+                                float clamp_max, int B, int D, int H, int W, float* metrics, float* count, float* depth,
+                                void* workspace, hipStream_t stream);
+
 // sweep_bwd.hip: gradient of the cost volume with respect to the NCHW features (either output may be nullptr, not both;
 // grad_src [B,V,C,H,W] contiguous, zeroed by the launcher; grad_ref [B,C,H,W] contiguous)
 hipError_t launch_sweep_backward(const SweepArgs& a, const float* grad_cost, float* grad_ref, float* grad_src, hipStream_t stream);

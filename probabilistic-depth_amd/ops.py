@@ -177,6 +177,32 @@ def dpv_soft_ce(logp, d_candi, label=None, depth_gt=None, variance=None, mask=No
     return loss, depth
 
 
+# the devkit's names in its order (external/deval_lib/src/evaluate_depth.h:125-133): the columns of depth_metrics
+DEPTH_METRIC_NAMES = ("mae", "rmse", "inverse mae", "inverse rmse", "log mae", "log rmse", "scale invariant log", "abs relative",
+                      "squared relative")
+
+
+def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_max=None, want_depth=False):
+    """The KITTI devkit's nine depth errors per item, on the device: (metrics [B,9] in the order of DEPTH_METRIC_NAMES, count [B]
+    = the number of valid pixels, depth [B,H,W] | None).  The tail of the evaluation loop (trainer/default_trainer.py:247-256)
+    composed with img_utils.depth_error (utils/img_utils.py:17-22) and depthError (external/deval_lib/src/evaluate_depth.h:20-121)
+    for the whole batch, without copying a depth map to the host.
+
+    The prediction is `pred` [B,H,W] or, given `logp` [B,D,H,W] and `d_candi`, the expectation of the log-DPV, formed from one
+    read of the volume (the bits of dpv_expect(logp, d_candi, BV_log=True); want_depth returns that map from the same pass).
+    truth [B,H,W]; mask [B,H,W] | [B,1,H,W] | None multiplies the prediction; clamp_max (the trainer: d_candi[-1]) replaces every
+    truth >= clamp_max, None = no clamp; a truth of 0 becomes -1.
+
+    The reference's argument order is kept: depth_error(predicted, truth) hands its arguments to depthError(D_gt, D_ipol) in
+    that order, so a pixel is valid where the masked PREDICTION is > 0 (0 and NaN are not) and the two relative errors divide by
+    the PREDICTION, not by the ground truth.  A valid pixel whose truth is 0 or negative makes the log and inverse metrics of its
+    item NaN; an item without a valid pixel (the reference throws) has nine NaNs and count 0.  Not differentiable."""
+    if mask is not None and mask.dim() == 4:
+        mask = mask[:, 0]
+    dc = d_candi_tensor(d_candi, logp.device) if (logp is not None and d_candi is not None) else None
+    return _native.depth_metrics(truth, pred=pred, logp=logp, d_candi=dc, mask=mask, clamp_max=clamp_max, want_depth=want_depth)
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)

@@ -13,6 +13,51 @@ def dpv_to_depthmap(dpv, d_candi, BV_log=False):
     return ops.dpv_expect(dpv, d_candi, BV_log=BV_log)
 
 
+def depth_error(predicted, truth):
+    """The KITTI devkit's nine depth errors of one depth map against its ground truth -> list of nine floats in the order of
+    ops.DEPTH_METRIC_NAMES (utils/img_utils.py:17-22 -> depthError, external/deval_lib/src/evaluate_depth.h:20-121).
+
+    predicted, truth: [H,W] float arrays as the reference's evaluation loop passes them (uploaded to the current device), or
+    tensors (device tensors are used where they are).  A zero in either map stands for "no value".  As in the reference the
+    arguments reach depthError(D_gt, D_ipol) in this order: a pixel counts where `predicted` is > 0, and the two relative errors
+    divide by `predicted`.  Computed by ops.depth_metrics; the only host work is reading the ten numbers back.  Raises
+    RuntimeError where the reference throws: no valid pixel."""
+    def dev(a):
+        if isinstance(a, torch.Tensor):
+            return a.float()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    predicted, truth = dev(predicted), dev(truth)
+    if predicted.dim() != 2 or predicted.shape != truth.shape:
+        raise RuntimeError("depth_error: predicted and truth must be [H,W] maps of one size")   # (the reference: "Wrong file size!")
+    metrics, count, _ = ops.depth_metrics(truth.unsqueeze(0), pred=predicted.unsqueeze(0))
+    row = torch.cat((metrics[0], count)).tolist()
+    if row[9] == 0:
+        raise RuntimeError("depth_error: no valid pixel (the prediction is nowhere > 0)")
+    return row[:9]
+
+
+def eval_errors(errors):
+    """{name: [mean, min, max]} over a list of depth_error results (utils/img_utils.py:14-15 -> evaluateErrors,
+    external/deval_lib/src/evaluate_depth.h:123-142; external/deval_lib/src/utils.h:24-53).  Plain host code.  As in the
+    reference the mean is accumulated in float32 in list order, the minimum starts at 1 and the maximum at 0: a metric whose
+    values all exceed 1 reports a minimum of 1, and a NaN never replaces either."""
+    if len(errors) == 0:
+        raise RuntimeError("eval_errors: no errors to evaluate")
+    f32 = np.float32
+    results = {}
+    for i, name in enumerate(ops.DEPTH_METRIC_NAMES[:len(errors[0])]):
+        mean, lo, hi = f32(0), f32(1), f32(0)
+        for e in errors:
+            v = f32(e[i])
+            mean = f32(mean + v)
+            if v < lo:
+                lo = v
+            if v > hi:
+                hi = v
+        results[name] = [float(f32(mean / f32(len(errors)))), float(lo), float(hi)]
+    return results
+
+
 def gaussian_torch(x, mu, sig, pow=2.):
     """exp(-|x - mu|^pow / (2 sig^pow)) (utils/img_utils.py:24-25); sig is a tensor."""
     return torch.exp(-torch.pow(torch.abs(x - mu), pow) / (2 * torch.pow(sig, pow)))
@@ -91,8 +136,8 @@ def compute_unc_rmse(unc_field_truth, unc_field_predicted, d_candi, plot=False):
     import torch
     truth_depth = dpv_to_depthmap(unc_field_truth.unsqueeze(2), d_candi, BV_log=False).squeeze(0).squeeze(0)
     pred_depth = dpv_to_depthmap(unc_field_predicted.unsqueeze(2), d_candi, BV_log=False).squeeze(0).squeeze(0)
-    pred_depth[0] = 0
-    pred_depth[-1] = 0
+    pred_depth[0].zero_()    # (in place on the views: `pred_depth[0] = 0` uploads its scalar and waits for the device)
+    pred_depth[-1].zero_()
     usable = ~torch.isnan(truth_depth) & ~torch.isnan(pred_depth)
     truth_depth = torch.where(usable, truth_depth, torch.zeros_like(truth_depth))
     pred_depth = torch.where(usable, pred_depth, torch.zeros_like(pred_depth))
