@@ -19,26 +19,9 @@ LIB_PATH = os.path.join(_HERE, "libpdepth_hip.so")
 METRIC_L2, METRIC_L1 = 0, 1
 ALGO_AUTO, ALGO_DIRECT, ALGO_TILED_1, ALGO_TILED_2, ALGO_CELLS, ALGO_MFMA, ALGO_CORR, ALGO_DIST = 0, 1, 2, 3, 4, 5, 6, 7
 LAYOUT_NONE, LAYOUT_C4, LAYOUT_DIST16 = 0, 1, 3   # (2: a retired layout; pdepth_sweep_source_layout never answers it)
-# workspace ints behind the tile flags that the diagnostics below read (csrc/kernels.hpp; tests/test_capi_symbols.py compares them)
+# workspace ints behind the tile flags that the diagnostics below read (csrc/sweep_workspace.hpp; tests/test_capi_symbols.py compares them)
 NONCENTRED_SLOT, LAYOUT_SLOT, DIST_DIRECT_LAST_SLOT, DIST_NONCE_SLOT = 51, 56, 59, 60
 BLAS_FMA, BLAS_SEPARATE = 0, 1
-
-# every symbol include/pdepth.h declares (tests check the library exports all of them)
-EXPORTED_SYMBOLS = (
-    "pdepth_abi_version", "pdepth_last_error", "pdepth_sweep_workspace_bytes",
-    "pdepth_sweep_cost_f32", "pdepth_sweep_dpv_f32", "pdepth_dpv_reduce_f32",
-    "pdepth_dpv_expect_f32", "pdepth_warp_feature_f32", "pdepth_sample_coords_f32",
-    "pdepth_dpv_fuse_f32", "pdepth_correlation_forward_f32", "pdepth_inverse_warp_f32", "pdepth_inverse_warp_backward_f32",
-    "pdepth_dpv_moments_f32", "pdepth_correlation_backward_f32",
-    "pdepth_pack_source_f32", "pdepth_sweep_dpv_packed_f32", "pdepth_dpv_reduce_ex_f32",
-    "pdepth_ufield_workspace_bytes", "pdepth_ufield_f32",
-    "pdepth_correlation_output_size", "pdepth_correlation_forward_f16", "pdepth_correlation_backward_f16",
-    "pdepth_pack_views_f32", "pdepth_sweep_centres_source", "pdepth_sweep_source_layout",
-    "pdepth_sweep_backward_f32", "pdepth_dpv_reduce_backward_f32", "pdepth_dpv_expect_backward_f32",
-    "pdepth_dpv_soft_ce_workspace_bytes", "pdepth_dpv_soft_ce_f32", "pdepth_dpv_soft_ce_backward_f32",
-    "pdepth_depth_metrics_workspace_bytes", "pdepth_depth_metrics_f32",
-)
-
 
 class SweepDesc(Structure):
     _fields_ = [
@@ -50,6 +33,52 @@ class SweepDesc(Structure):
 
 class Camera(Structure):
     _fields_ = [("K", c_void_p), ("R", c_void_p), ("t", c_void_p), ("rays", c_void_p), ("cxcy", c_void_p)]
+
+
+_P, _I, _F, _Z = c_void_p, c_int32, c_float, c_size_t
+_DESC, _CAM = POINTER(SweepDesc), POINTER(Camera)
+# every entry include/pdepth.h declares: name -> (restype, argtypes).  load() applies it; tests check it against the header
+_SIGNATURES = {
+    "pdepth_abi_version": (c_int, []),
+    "pdepth_last_error": (c_char_p, []),
+    "pdepth_sweep_workspace_bytes": (_Z, [_DESC]),
+    "pdepth_sweep_source_layout": (c_int, [_DESC]),
+    "pdepth_sweep_centres_source": (c_int, [_DESC]),
+    "pdepth_sweep_cost_f32": (c_int, [_DESC, _CAM] + [_P] * 5 + [_Z, _P]),
+    "pdepth_sweep_dpv_f32": (c_int, [_DESC, _CAM] + [_P] * 7 + [_Z, _P]),
+    "pdepth_pack_source_f32": (c_int, [_DESC, _P, _P, _Z, _P]),
+    "pdepth_pack_views_f32": (c_int, [_DESC, _P, _P, _I, _P, _P, _Z, _P]),
+    "pdepth_sweep_dpv_packed_f32": (c_int, [_DESC, _CAM] + [_P] * 6 + [_Z, _P]),
+    "pdepth_sweep_backward_f32": (c_int, [_DESC, _CAM] + [_P] * 7),
+    "pdepth_warp_feature_f32": (c_int, [_DESC, _CAM] + [_P] * 4),
+    "pdepth_sample_coords_f32": (c_int, [_DESC, _CAM] + [_P] * 4),
+    "pdepth_dpv_reduce_f32": (c_int, [_P, _P] + [_I] * 4 + [_P] * 3),
+    "pdepth_dpv_reduce_ex_f32": (c_int, [_P] * 3 + [_I] * 4 + [_P] * 6),
+    "pdepth_dpv_reduce_backward_f32": (c_int, [_P, _P] + [_I] * 4 + [_P] * 5),
+    "pdepth_dpv_expect_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 2),
+    "pdepth_dpv_expect_backward_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 3),
+    "pdepth_dpv_moments_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 3),
+    "pdepth_dpv_fuse_f32": (c_int, [_P] * 4 + [_I] * 4 + [_F, _F] + [_P] * 3),
+    "pdepth_ufield_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_ufield_f32": (c_int, [_P] * 4 + [_I] * 5 + [_F] * 4 + [_I, _F] + [_P] * 3 + [_Z, _P]),
+    "pdepth_correlation_output_size": (c_int, [_I] * 7 + [POINTER(c_int32)] * 3),
+    "pdepth_correlation_forward_f32": (c_int, [_P] * 2 + [_I] * 10 + [_P] * 2),
+    "pdepth_correlation_backward_f32": (c_int, [_P] * 3 + [_I] * 10 + [_P] * 3),
+    "pdepth_correlation_forward_f16": (c_int, [_P] * 2 + [_I] * 10 + [_P] * 2),
+    "pdepth_correlation_backward_f16": (c_int, [_P] * 3 + [_I] * 10 + [_P] * 3),
+    "pdepth_inverse_warp_f32": (c_int, [_P] * 4 + [_I] * 5 + [_P] * 3),
+    "pdepth_inverse_warp_backward_f32": (c_int, [_P] * 5 + [_I] * 5 + [_P] * 3),
+    "pdepth_dpv_soft_ce_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_dpv_soft_ce_f32": (c_int, [_P] * 4 + [_F, _F, _P] + [_I] * 4 + [_P] * 4 + [_Z, _P]),
+    "pdepth_dpv_soft_ce_backward_f32": (c_int, [_P] * 4 + [_F, _F, _P, _P] + [_I] * 4 + [_P] * 4),
+    "pdepth_depth_metrics_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_depth_metrics_f32": (c_int, [_P] * 5 + [_F] + [_I] * 4 + [_P] * 4 + [_Z, _P]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# The loss and metrics entries live in objects of their own (csrc/loss.hip, csrc/metrics.hip).  The product library must have
+# them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it loads, and a loss or metrics
+# call on it raises (_loss_entry, _metrics_entry)
+_ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if "_soft_ce_" in n or "_depth_metrics_" in n)
 
 
 _lib = None
@@ -109,72 +138,11 @@ def load():
             f"{path} not found: build the HIP extension first "
             "(python -c 'import __graft_entry__ as g; g.build()' or make -C probabilistic-depth_amd/csrc)")
     lib = ctypes.CDLL(path)
-    lib.pdepth_abi_version.restype = c_int
-    lib.pdepth_last_error.restype = c_char_p
-    lib.pdepth_sweep_workspace_bytes.restype = c_size_t
-    lib.pdepth_sweep_workspace_bytes.argtypes = [POINTER(SweepDesc)]
-    lib.pdepth_sweep_cost_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera), c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.pdepth_sweep_dpv_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera), c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.pdepth_pack_source_f32.argtypes = [POINTER(SweepDesc), c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.pdepth_sweep_dpv_packed_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera), c_void_p, c_void_p, c_void_p,
-                                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.pdepth_dpv_reduce_f32.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
-                                          c_void_p, c_void_p]
-    lib.pdepth_dpv_reduce_ex_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.pdepth_ufield_workspace_bytes.restype = c_size_t
-    lib.pdepth_ufield_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-    lib.pdepth_ufield_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                      c_float, c_float, c_float, c_float, c_int32, c_float, c_void_p, c_void_p, c_void_p,
-                                      c_size_t, c_void_p]
-    lib.pdepth_dpv_expect_f32.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                          c_void_p, c_void_p]
-    lib.pdepth_dpv_moments_f32.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                           c_void_p, c_void_p, c_void_p]
-    lib.pdepth_warp_feature_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera), c_void_p, c_void_p, c_void_p,
-                                            c_void_p]
-    lib.pdepth_sample_coords_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera), c_void_p, c_void_p, c_void_p,
-                                             c_void_p]
-    lib.pdepth_dpv_fuse_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
-                                        c_float, c_float, c_void_p, c_void_p, c_void_p]
-    lib.pdepth_correlation_forward_f32.argtypes = [c_void_p, c_void_p] + [c_int32] * 10 + [c_void_p, c_void_p]
-    lib.pdepth_correlation_backward_f32.argtypes = [c_void_p] * 3 + [c_int32] * 10 + [c_void_p] * 3
-    lib.pdepth_correlation_forward_f16.argtypes = [c_void_p, c_void_p] + [c_int32] * 10 + [c_void_p, c_void_p]
-    lib.pdepth_correlation_backward_f16.argtypes = [c_void_p] * 3 + [c_int32] * 10 + [c_void_p] * 3
-    lib.pdepth_correlation_output_size.argtypes = [c_int32] * 7 + [POINTER(c_int32)] * 3
-    lib.pdepth_inverse_warp_f32.argtypes = [c_void_p] * 4 + [c_int32] * 5 + [c_void_p] * 3
-    lib.pdepth_inverse_warp_backward_f32.argtypes = [c_void_p] * 5 + [c_int32] * 5 + [c_void_p] * 3
-    lib.pdepth_sweep_backward_f32.argtypes = [POINTER(SweepDesc), POINTER(Camera)] + [c_void_p] * 7
-    lib.pdepth_dpv_reduce_backward_f32.argtypes = [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 5
-    lib.pdepth_dpv_expect_backward_f32.argtypes = [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p] * 3
-    # the loss entries live in their own object (csrc/loss.hip).  The product library must have them; an experiment library
-    # named by PDEPTH_LIB may be linked from a subset of the objects: it loads, and a loss call on it raises (_loss_entry)
-    if hasattr(lib, "pdepth_dpv_soft_ce_f32") or path == LIB_PATH:
-        lib.pdepth_dpv_soft_ce_workspace_bytes.restype = c_size_t
-        lib.pdepth_dpv_soft_ce_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-        lib.pdepth_dpv_soft_ce_f32.argtypes = [c_void_p] * 4 + [c_float, c_float, c_void_p] + [c_int32] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
-        lib.pdepth_dpv_soft_ce_backward_f32.argtypes = [c_void_p] * 4 + [c_float, c_float, c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 4
-        for fn in ("pdepth_dpv_soft_ce_f32", "pdepth_dpv_soft_ce_backward_f32"):
-            getattr(lib, fn).restype = c_int
-    # ... and so do the evaluation metrics (csrc/metrics.hip)
-    if hasattr(lib, "pdepth_depth_metrics_f32") or path == LIB_PATH:
-        lib.pdepth_depth_metrics_workspace_bytes.restype = c_size_t
-        lib.pdepth_depth_metrics_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
-        lib.pdepth_depth_metrics_f32.restype = c_int
-        lib.pdepth_depth_metrics_f32.argtypes = [c_void_p] * 5 + [c_float] + [c_int32] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
-    for fn in ("pdepth_sweep_cost_f32", "pdepth_sweep_dpv_f32", "pdepth_dpv_reduce_f32",
-               "pdepth_dpv_expect_f32", "pdepth_warp_feature_f32", "pdepth_sample_coords_f32",
-               "pdepth_dpv_fuse_f32", "pdepth_correlation_forward_f32", "pdepth_inverse_warp_f32",
-               "pdepth_dpv_moments_f32", "pdepth_correlation_backward_f32", "pdepth_correlation_output_size",
-               "pdepth_correlation_forward_f16", "pdepth_correlation_backward_f16", "pdepth_sweep_backward_f32",
-               "pdepth_dpv_reduce_backward_f32", "pdepth_dpv_expect_backward_f32"):
-        getattr(lib, fn).restype = c_int
-    lib.pdepth_sweep_centres_source.restype = c_int
-    lib.pdepth_sweep_centres_source.argtypes = [POINTER(SweepDesc)]
-    lib.pdepth_sweep_source_layout.restype = c_int
-    lib.pdepth_sweep_source_layout.argtypes = [POINTER(SweepDesc)]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        if path != LIB_PATH and name in _ABSENT_FROM_EXPERIMENT_LIBS and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.pdepth_abi_version() != 6:
         raise RuntimeError("libpdepth_hip.so ABI version mismatch")
     _lib = lib
@@ -332,8 +300,6 @@ def pack_views(feat, rgb, n_views, n_planes=64):
     ws_bytes = lib.pdepth_sweep_workspace_bytes(ctypes.byref(desc))
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=feat.device)
     ref = torch.empty((B, C, h, w), dtype=torch.float32, device=feat.device)
-    lib.pdepth_pack_views_f32.argtypes = [POINTER(SweepDesc), c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.pdepth_pack_views_f32.restype = c_int
     with torch.cuda.device(feat.device):
         rc = lib.pdepth_pack_views_f32(ctypes.byref(desc), feat.data_ptr(), rgb.data_ptr(), rate, ref.data_ptr(), ws.data_ptr(),
                                        ws_bytes, _stream(feat.device))
@@ -416,15 +382,20 @@ def sweep(ref, src, K, R, t, rays, cxcy, d_candi, sigma, metric=METRIC_L2, algo=
 _last_workspace = None
 
 
-def _queue_slot(B, H, W, slot):
+def _tiles_and_queue_offset(B, H, W):
+    """(tile flags of a workspace, byte offset of the 64 queue ints behind them): csrc/sweep_workspace.hpp."""
     n = B * ((W + 15) // 16) * ((H + 3) // 4)
-    flag_only = (4 * n + 255) & ~255
-    return int(_last_workspace[flag_only + 4 * slot: flag_only + 4 * slot + 4].view(torch.int32).item())
+    return n, (4 * n + 255) & ~255
+
+
+def _queue_slot(B, H, W, slot):
+    at = _tiles_and_queue_offset(B, H, W)[1] + 4 * slot
+    return int(_last_workspace[at: at + 4].view(torch.int32).item())
 
 
 def noncentred_guard(B, H, W):
     """Diagnostics: did the pre-pass of the last sweep on a NOT centred source (LDS-tiled kernel) find channel offsets larger
-    than the spread of the features -- the tiled kernel then evaluated every plane directly (csrc/sweep_pack.hip)."""
+    than the spread of the features -- the tiled kernel then evaluated every plane directly (csrc/sweep_workspace.hpp)."""
     return None if _last_workspace is None else _queue_slot(B, H, W, NONCENTRED_SLOT) != 0
 
 
@@ -435,9 +406,9 @@ def fallback_tiles(B, H, W, gather_flag=1):
     is 1)."""
     if _last_workspace is None:
         return 0
-    n = B * ((W + 15) // 16) * ((H + 3) // 4)
+    n = _tiles_and_queue_offset(B, H, W)[0]
     direct = 0
-    if _queue_slot(B, H, W, LAYOUT_SLOT) == LAYOUT_DIST16:   # (nonce << 20) | count; a count tagged by another call's nonce is stale (kernels.hpp: DIST_NONCE_SLOT)
+    if _queue_slot(B, H, W, LAYOUT_SLOT) == LAYOUT_DIST16:   # (nonce << 20) | count; a count tagged by another call's nonce is stale (sweep_workspace.hpp: DIST_NONCE_SLOT)
         tagged, nonce = _queue_slot(B, H, W, DIST_DIRECT_LAST_SLOT), _queue_slot(B, H, W, DIST_NONCE_SLOT)
         direct = (tagged & 0xFFFFF) if nonce != 0 and (tagged >> 20) == nonce else 0
     return int((_last_workspace[: 4 * n].view(torch.int32) == gather_flag).sum().item()) + direct

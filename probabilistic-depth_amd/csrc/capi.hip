@@ -7,6 +7,7 @@
 
 #include "../../include/pdepth.h"
 #include "kernels.hpp"
+#include "sweep_workspace.hpp"
 
 namespace {
 
@@ -20,11 +21,30 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// every dimension positive: of a descriptor, of the entries that take B, D (or C), H, W as plain arguments
+bool dims_positive(const pdepth_sweep_desc* d) { return d->B > 0 && d->V > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0; }
+int check_dims(const char* who, const pdepth_sweep_desc* d) {
+    if (dims_positive(d)) return PDEPTH_OK;
+    return fail(PDEPTH_E_ARG, "%s: non-positive dimension B=%d V=%d C=%d D=%d H=%d W=%d", who, d->B, d->V, d->C, d->D, d->H, d->W);
+}
+int check_dims(const char* who, int32_t B, int32_t D, int32_t H, int32_t W) {
+    if (B > 0 && D > 0 && H > 0 && W > 0) return PDEPTH_OK;
+    return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+}
+
+// a sweep workspace: present, large enough, 256-byte aligned
+int check_workspace(const char* who, const void* workspace, size_t bytes, size_t need) {
+    if (!workspace || bytes < need)
+        return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu); query pdepth_sweep_workspace_bytes()", who, need, bytes);
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+        return fail(PDEPTH_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+    return PDEPTH_OK;
+}
+size_t workspace_bytes_of(const pdepth_sweep_desc* d) { return pdepth::sweep_workspace_bytes(d->B, d->V, d->C, d->H, d->W); }
+
 int check_desc(const pdepth_sweep_desc* d, const pdepth_camera* cam, const char* who) {
     if (!d || !cam) return fail(PDEPTH_E_ARG, "%s: null descriptor", who);
-    if (d->B <= 0 || d->V <= 0 || d->C <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0)
-        return fail(PDEPTH_E_ARG, "%s: non-positive dimension B=%d V=%d C=%d D=%d H=%d W=%d", who,
-                    d->B, d->V, d->C, d->D, d->H, d->W);
+    if (int rc = check_dims(who, d)) return rc;
     if ((long long)d->H * d->W > (1ll << 30))
         return fail(PDEPTH_E_ARG, "%s: H*W too large", who);
     if (!cam->K || !cam->R || !cam->t || !cam->rays || !cam->cxcy)
@@ -37,11 +57,12 @@ int check_desc(const pdepth_sweep_desc* d, const pdepth_camera* cam, const char*
     return PDEPTH_OK;
 }
 
-pdepth::SweepArgs make_args(const pdepth_sweep_desc* d, const pdepth_camera* cam, const float* ref,
-                            const float* src, const float* d_candi) {
+// the one place a SweepArgs is filled from a descriptor (cam == nullptr: the entries that launch no sampling kernel)
+pdepth::SweepArgs make_args(const pdepth_sweep_desc* d, const pdepth_camera* cam = nullptr, const float* ref = nullptr,
+                            const float* src = nullptr, const float* d_candi = nullptr) {
     pdepth::SweepArgs a{};
     a.ref = ref; a.src = src; a.packed_src = nullptr;
-    a.K = cam->K; a.R = cam->R; a.t = cam->t; a.rays = cam->rays; a.cxcy = cam->cxcy;
+    if (cam) { a.K = cam->K; a.R = cam->R; a.t = cam->t; a.rays = cam->rays; a.cxcy = cam->cxcy; }
     a.d_candi = d_candi;
     a.B = d->B; a.V = d->V; a.C = d->C; a.D = d->D; a.H = d->H; a.W = d->W;
     a.metric = d->metric; a.sigma = d->sigma; a.blas_mode = d->blas_mode;
@@ -62,22 +83,10 @@ int launched(hipError_t e, const char* who) {
     return PDEPTH_OK;
 }
 
-// The tiled kernel needs one int per 16x4 tile (flags of tiles left to the gather kernel) plus the
-// channel-group-planar copy of the source views it stages from.
-size_t tiled_ws_bytes(const pdepth_sweep_desc* d) {
-    return pdepth::sweep_tiled_workspace_bytes(d->B, d->V, d->C, d->H, d->W);
-}
-
 // does ALGO_AUTO run on a packed copy of the source for this shape?
 bool uses_packed_source(const pdepth_sweep_desc* d) {
     return d->algo != PDEPTH_ALGO_DIRECT && d->D <= pdepth::sweep_tiled_max_planes() && d->W <= 32767 && d->H <= 32767 &&
            (long long)((d->C + 3) / 4 + 2) * d->H * d->W * 16 < (1ll << 31);
-}
-
-pdepth::SweepArgs shape_args(const pdepth_sweep_desc* d) {
-    pdepth::SweepArgs a{};
-    a.B = d->B; a.V = d->V; a.C = d->C; a.D = d->D; a.H = d->H; a.W = d->W; a.metric = d->metric;
-    return a;
 }
 
 // Which sweep kernel family -- and with it which staging layout of the source -- a descriptor selects.  A pure function of
@@ -86,7 +95,7 @@ pdepth::SweepArgs shape_args(const pdepth_sweep_desc* d) {
 bool uses_dist(const pdepth_sweep_desc* d) {
     if (!uses_packed_source(d) || d->metric != PDEPTH_METRIC_L2) return false;
     if (d->algo != PDEPTH_ALGO_DIST && d->algo != PDEPTH_ALGO_AUTO) return false;
-    return pdepth::sweep_dist_supports(shape_args(d));
+    return pdepth::sweep_dist_supports(make_args(d));
 }
 //   LDS-tiled kernel (sweep_tiled.hip; channel-group-planar layout): every other shape that fits a packed layout (L1 has no
 //   distance form; wider features; more planes), and TILED_1 / TILED_2 on request
@@ -128,12 +137,7 @@ int sweep_common(const pdepth_sweep_desc* d, const pdepth_camera* cam, const flo
     // the tiled kernel addresses one view through a 32-bit buffer descriptor (C*H*W*4 bytes < 2^31)
     // (the tiled kernels also pack a footprint as two 16-bit coordinates)
     if (uses_packed_source(d)) {
-        const size_t need = tiled_ws_bytes(d);
-        if (!workspace || workspace_bytes < need)
-            return fail(PDEPTH_E_WORKSPACE, "%s: ALGO_AUTO needs %zu bytes of workspace (got %zu); "
-                        "query pdepth_sweep_workspace_bytes()", who, need, workspace_bytes);
-        if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-            return fail(PDEPTH_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+        if (int rc = check_workspace(who, workspace, workspace_bytes, workspace_bytes_of(d))) return rc;
         if (d->algo == PDEPTH_ALGO_TILED_1)
             return launched(pdepth::launch_sweep_tiled_n1(a, workspace, (hipStream_t)stream, packed_ready), who);
         if (d->algo == PDEPTH_ALGO_TILED_2)
@@ -154,11 +158,11 @@ const char* pdepth_last_error(void) { return g_err; }
 size_t pdepth_sweep_workspace_bytes(const pdepth_sweep_desc* desc) {
     if (!desc || desc->algo == PDEPTH_ALGO_DIRECT) return 0;
     if (desc->B <= 0 || desc->D <= 0 || desc->H <= 0 || desc->W <= 0) return 0;
-    return tiled_ws_bytes(desc);
+    return workspace_bytes_of(desc);
 }
 
 int pdepth_sweep_source_layout(const pdepth_sweep_desc* desc) {
-    if (!desc || desc->B <= 0 || desc->V <= 0 || desc->C <= 0 || desc->D <= 0 || desc->H <= 0 || desc->W <= 0) return PDEPTH_LAYOUT_NONE;
+    if (!desc || !dims_positive(desc)) return PDEPTH_LAYOUT_NONE;
     return source_layout(desc);
 }
 
@@ -186,21 +190,13 @@ int pdepth_pack_source_f32(const pdepth_sweep_desc* desc, const float* src, void
                            void* stream) {
     const char* who = "pdepth_pack_source_f32";
     if (!desc || !src) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    if (desc->B <= 0 || desc->V <= 0 || desc->C <= 0 || desc->D <= 0 || desc->H <= 0 || desc->W <= 0)
-        return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+    if (int rc = check_dims(who, desc)) return rc;
     if (desc->src_vstride < (long long)desc->C * desc->H * desc->W || desc->src_bstride < 0)
         return fail(PDEPTH_E_ARG, "%s: bad strides", who);
     if (!uses_packed_source(desc))
         return fail(PDEPTH_E_ARG, "%s: this shape / algorithm does not run on a packed source", who);
-    const size_t need = tiled_ws_bytes(desc);
-    if (!workspace || workspace_bytes < need)
-        return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu)", who, need, workspace_bytes);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-        return fail(PDEPTH_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
-    pdepth::SweepArgs a{};
-    a.src = src;
-    a.B = desc->B; a.V = desc->V; a.C = desc->C; a.D = desc->D; a.H = desc->H; a.W = desc->W;
-    a.src_bstride = desc->src_bstride; a.src_vstride = desc->src_vstride;
+    if (int rc = check_workspace(who, workspace, workspace_bytes, workspace_bytes_of(desc))) return rc;
+    const pdepth::SweepArgs a = make_args(desc, nullptr, nullptr, src);
     if (uses_dist(desc)) return launched(pdepth::launch_pack_dist(a, workspace, (hipStream_t)stream), who);
     return launched(pdepth::launch_pack_c4(a, workspace, (hipStream_t)stream), who);
 }
@@ -209,19 +205,14 @@ int pdepth_pack_views_f32(const pdepth_sweep_desc* desc, const float* feat, cons
                           void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "pdepth_pack_views_f32";
     if (!desc || !feat || !rgb || !ref_out) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    if (desc->B <= 0 || desc->V <= 0 || desc->C <= 3 || desc->D <= 0 || desc->H <= 0 || desc->W <= 0 || pool_rate < 1)
+    if (!dims_positive(desc) || desc->C <= 3 || pool_rate < 1)
         return fail(PDEPTH_E_ARG, "%s: bad dimension (C must count the 3 pooled image channels)", who);
     if (!uses_packed_source(desc))
         return fail(PDEPTH_E_ARG, "%s: this shape / algorithm does not run on a packed source", who);
     if ((long long)desc->H * pool_rate * desc->W * pool_rate * 3 >= (1ll << 31))
         return fail(PDEPTH_E_ARG, "%s: image too large", who);
-    const size_t need = tiled_ws_bytes(desc);
-    if (!workspace || workspace_bytes < need)
-        return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu)", who, need, workspace_bytes);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-        return fail(PDEPTH_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
-    pdepth::SweepArgs a{};
-    a.B = desc->B; a.V = desc->V; a.C = desc->C; a.D = desc->D; a.H = desc->H; a.W = desc->W;
+    if (int rc = check_workspace(who, workspace, workspace_bytes, workspace_bytes_of(desc))) return rc;
+    const pdepth::SweepArgs a = make_args(desc);
     if (uses_dist(desc))
         return launched(pdepth::launch_pack_views_dist(a, feat, rgb, pool_rate, desc->H * pool_rate, desc->W * pool_rate, ref_out, workspace,
                                                        (hipStream_t)stream), who);
@@ -240,8 +231,7 @@ int pdepth_dpv_reduce_f32(const float* logits, const float* d_candi, int32_t B, 
                           int32_t W, float* logp, float* depth, void* stream) {
     if (!logits || !d_candi) return fail(PDEPTH_E_ARG, "pdepth_dpv_reduce_f32: null input");
     if (!logp && !depth) return fail(PDEPTH_E_ARG, "pdepth_dpv_reduce_f32: no output requested");
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0)
-        return fail(PDEPTH_E_ARG, "pdepth_dpv_reduce_f32: non-positive dimension");
+    if (int rc = check_dims("pdepth_dpv_reduce_f32", B, D, H, W)) return rc;
     return launched(pdepth::launch_dpv_reduce(logits, d_candi, B, D, H, W, logp, depth,
                                               (hipStream_t)stream), "pdepth_dpv_reduce_f32");
 }
@@ -252,7 +242,7 @@ int pdepth_dpv_reduce_ex_f32(const float* logits, const float* addend, const flo
     const char* who = "pdepth_dpv_reduce_ex_f32";
     if (!logits || !d_candi) return fail(PDEPTH_E_ARG, "%s: null input", who);
     if (!logp && !prob && !depth && !variance && !logp_quarter) return fail(PDEPTH_E_ARG, "%s: no output requested", who);
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+    if (int rc = check_dims(who, B, D, H, W)) return rc;
     if (logp_quarter && (H < 4 || W < 4)) return fail(PDEPTH_E_ARG, "%s: quarter output needs H, W >= 4", who);
     if (prob == logits || variance == logits || (addend && (logp == addend || prob == addend)))
         return fail(PDEPTH_E_ARG, "%s: only logp may alias logits", who);
@@ -263,8 +253,7 @@ int pdepth_dpv_reduce_ex_f32(const float* logits, const float* addend, const flo
 int pdepth_dpv_expect_f32(const float* dpv, const float* d_candi, int32_t B, int32_t D, int32_t H,
                           int32_t W, int32_t bv_log, float* depth, void* stream) {
     if (!dpv || !d_candi || !depth) return fail(PDEPTH_E_ARG, "pdepth_dpv_expect_f32: null pointer");
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0)
-        return fail(PDEPTH_E_ARG, "pdepth_dpv_expect_f32: non-positive dimension");
+    if (int rc = check_dims("pdepth_dpv_expect_f32", B, D, H, W)) return rc;
     return launched(pdepth::launch_dpv_expect(dpv, d_candi, B, D, H, W, bv_log, depth,
                                               (hipStream_t)stream), "pdepth_dpv_expect_f32");
 }
@@ -272,8 +261,7 @@ int pdepth_dpv_expect_f32(const float* dpv, const float* d_candi, int32_t B, int
 int pdepth_dpv_moments_f32(const float* dpv, const float* d_candi, int32_t B, int32_t D, int32_t H,
                            int32_t W, int32_t bv_log, float* mean, float* variance, void* stream) {
     if (!dpv || !d_candi || !variance) return fail(PDEPTH_E_ARG, "pdepth_dpv_moments_f32: null pointer");
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0)
-        return fail(PDEPTH_E_ARG, "pdepth_dpv_moments_f32: non-positive dimension");
+    if (int rc = check_dims("pdepth_dpv_moments_f32", B, D, H, W)) return rc;
     return launched(pdepth::launch_dpv_moments(dpv, d_candi, B, D, H, W, bv_log, mean, variance,
                                                (hipStream_t)stream), "pdepth_dpv_moments_f32");
 }
@@ -323,7 +311,7 @@ int pdepth_dpv_fuse_f32(const float* logp, const float* dmaps, const float* mask
                         float* logfused, void* stream) {
     if (!logp || !dmaps || !masks || !d_candi) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: null input");
     if (!fused && !logfused) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: no output requested");
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: non-positive dimension");
+    if (int rc = check_dims("pdepth_dpv_fuse_f32", B, D, H, W)) return rc;
     if (!(var > 0.0f)) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: var must be positive");
     return launched(pdepth::launch_dpv_fuse(logp, dmaps, masks, d_candi, B, D, H, W, var, eps, fused, logfused,
                                             (hipStream_t)stream), "pdepth_dpv_fuse_f32");
@@ -335,7 +323,7 @@ namespace {
 // kernel_size odd, strides >= 1, and no index of the reference's kernel outside its padded buffers
 int check_corr(const char* who, int32_t B, int32_t C, int32_t H, int32_t W, int32_t pad, int32_t k, int32_t md, int32_t s1, int32_t s2,
                int* oH, int* oW) {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+    if (int rc = check_dims(who, B, C, H, W)) return rc;
     if (pad < 0 || k < 1 || (k & 1) == 0 || md < 0 || s1 < 1 || s2 < 1)
         return fail(PDEPTH_E_ARG, "%s: bad configuration (pad %d, kernel %d, max_displacement %d, stride1 %d, stride2 %d)", who, pad, k, md, s1, s2);
     if (md - (md / s2) * s2 - (k - 1) / 2 < 0)
@@ -474,7 +462,7 @@ int pdepth_dpv_reduce_backward_f32(const float* logp, const float* d_candi, int3
     const char* who = "pdepth_dpv_reduce_backward_f32";
     if (!logp || !d_candi || !g_logits) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     if (!g_logp && !g_prob && !g_depth) return fail(PDEPTH_E_ARG, "%s: no incoming gradient", who);
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+    if (int rc = check_dims(who, B, D, H, W)) return rc;
     if ((long long)H * W > (1ll << 30)) return fail(PDEPTH_E_ARG, "%s: H*W too large", who);
     if ((const float*)g_logits == logp || (g_prob && (const float*)g_logits == g_prob))
         return fail(PDEPTH_E_ARG, "%s: only g_logp may alias g_logits", who);
@@ -487,7 +475,7 @@ int pdepth_dpv_expect_backward_f32(const float* dpv, const float* d_candi, int32
                                    int32_t bv_log, const float* g_depth, float* g_dpv, void* stream) {
     const char* who = "pdepth_dpv_expect_backward_f32";
     if (!dpv || !d_candi || !g_depth || !g_dpv) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
+    if (int rc = check_dims(who, B, D, H, W)) return rc;
     if ((long long)H * W > (1ll << 30)) return fail(PDEPTH_E_ARG, "%s: H*W too large", who);
     if ((const float*)g_dpv == dpv || (const float*)g_dpv == g_depth) return fail(PDEPTH_E_ARG, "%s: g_dpv may not alias an input", who);
     return launched(pdepth::launch_dpv_expect_backward(dpv, d_candi, B, D, H, W, bv_log, g_depth, g_dpv, (hipStream_t)stream), who);

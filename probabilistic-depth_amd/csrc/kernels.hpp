@@ -40,61 +40,16 @@ struct SweepArgs {
 #ifndef PDEPTH_COND_LIMIT_TILED
 #define PDEPTH_COND_LIMIT_TILED 1.5e-4f
 #endif
-// the 64 workspace ints behind the tile flags.  Slots 50 and 52-55 are reserved and kept zero (they belonged to retired kernels;
-// the pack kernels and the flag clear zero them with the rest), so a workspace packed by an earlier build of ABI 6 stays valid.
-constexpr int NONCENTRED_SLOT = 51;        // set by the pre-pass of a NOT centred source whose channel offsets exceed the spread (sweep_pack.hip)
-// channel statistics of the source (workspace tail, sweep_pack.hip): per batch item mu[c] at +0, var[c] at +STATS_VAR, the
-// squared offset that was NOT subtracted at +STATS_OFF, the largest sampled |x| at +STATS_AMAX, half the mean squared
-// difference of samples STATS_LAG_PX texels apart at +STATS_LAG (the spread of a channel at the distance of a plane sweep:
-// equal to var[c] for white features, smaller for smooth ones), and STATS_NFLAG ints at +STATS_FLAGS: [1] != 0 = the item was left to the gather kernel (sweep_dist.hip: routing); [0] != 0 = a feature
-// of the item did not fit the fp16 range of the distance-form layout (pack_dist.hip)
-constexpr int STATS_VAR = 80, STATS_OFF = 160, STATS_AMAX = 240, STATS_LAG = 320, STATS_FLAGS = 400, STATS_NFLAG = 16, STATS_STRIDE = 496;
-// (the 80 ints at +416 of a row are reserved: a retired pre-pass kept per-channel tags there; the stride is what ABI 6 callers sized
-// their workspaces by)
-constexpr int STATS_LAG_PX = 16;
-// which staging layout the packed-source region holds (written by the pack kernels, checked by the sweep kernels: a sweep on
-// another family's layout fills its outputs with NaN instead of returning numbers computed from the wrong bytes)
-constexpr int LAYOUT_SLOT = 56;
-constexpr int LAYOUT_C4 = 1, LAYOUT_DIST16 = 3;   // (0: nothing packed yet; 2: reserved, a retired layout)
-// sweep_dist.hip: workgroups that have left (the last one zeroes the queue counters); pixel blocks evaluated directly, this call
-// so far / of the last finished call
-constexpr int DIST_DONE_SLOT = 57, DIST_DIRECT_SLOT = 58, DIST_DIRECT_LAST_SLOT = 59;
-// DIST_DIRECT_LAST_SLOT holds (nonce << 20) | count, DIST_NONCE_SLOT the nonce of the last call: a count whose nonce is another
-// call's reads as 0 (where every workgroup runs one item there is no counter of finished workgroups to reset anything by: 2 048
-// returning atomics on one address were a quarter of such a launch)
-constexpr int DIST_NONCE_SLOT = 60;
-
-// First statement of a sweep kernel on a packed source: does the workspace hold the layout this kernel reads?  If not (a C
-// caller swept a workspace packed for another kernel family: include/pdepth.h, pdepth_sweep_source_layout) every output of
-// the call is filled with NaN by the whole grid and the kernel leaves: loud numbers instead of costs computed from the
-// wrong bytes.  (The packing entry points write the tag; the Python binding refuses the mismatch before it gets here.)
-__device__ __forceinline__ bool poison_on_foreign_layout(const SweepArgs& a, const int* __restrict__ queue, int expected) {
-    if (queue[LAYOUT_SLOT] == expected) return false;
-    const float nan = __builtin_nanf("");
-    const size_t hw = (size_t)a.H * a.W, nvol = (size_t)a.B * a.D * hw, nmap = (size_t)a.B * hw;
-    const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = i0; i < nvol; i += step) {
-        if (a.cost_out) a.cost_out[i] = nan;
-        if (a.logp_out) a.logp_out[i] = nan;
-    }
-    if (a.depth_out)
-        for (size_t i = i0; i < nmap; i += step) a.depth_out[i] = nan;
-    return true;
-}
-
 // sweep_direct.hip
 hipError_t launch_sweep_direct(const SweepArgs& a, hipStream_t stream);
-// Workspace counter (an int of the 64 queue ints behind the tile flags) of the tiles handed to the gather kernel:
-// every writer of a gather flag increments it, the gather kernel's blocks leave at once while it is zero.
-constexpr int GATHER_COUNT_SLOT = 48;
+// the tiles whose flag == flag_value; gather_count: the workspace's GATHER_COUNT_SLOT (sweep_workspace.hpp)
 hipError_t launch_sweep_direct_flagged(const SweepArgs& a, const int* tile_flags, const int* gather_count, int tiles_x,
                                        int tiles, hipStream_t stream, int flag_value = 1);
 // ... the whole batch items b with item_flags[b * item_stride] != 0 (the distance-form kernel's routed items: STATS_FLAGS + 1)
-hipError_t launch_sweep_direct_items(const SweepArgs& a, const int* item_flags, int item_stride, hipStream_t stream);  // runs the tiles whose flag == flag_value
+hipError_t launch_sweep_direct_items(const SweepArgs& a, const int* item_flags, int item_stride, hipStream_t stream);
 int sweep_direct_max_planes(int C);
 
-// sweep_tiled.hip
-size_t sweep_tiled_workspace_bytes(int B, int V, int C, int H, int W);
+// sweep_tiled.hip (the workspace of every launcher below that takes one: sweep_workspace.hpp)
 int sweep_tiled_max_planes();
 // packed_ready: the workspace already holds the packed source of exactly these views (pdepth_pack_source_f32)
 hipError_t launch_sweep_tiled(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready = false);     // picks a variant
@@ -109,10 +64,6 @@ hipError_t clear_sweep_flags(const SweepArgs& a, void* workspace, hipStream_t st
 hipError_t launch_pack_views(const SweepArgs& a, const float* feat, const float* rgb, int rate, int img_h, int img_w, float* ref_out,
                              void* workspace, hipStream_t stream);
 int sweep_device_cus();
-// workspace head shared by the packed-source kernels: tile flags (+ the 64 queue / counter ints behind them); its tail
-size_t sweep_ws_flag_only_bytes(int B, int H, int W);
-size_t sweep_ws_flag_bytes(int B, int H, int W);
-size_t sweep_ws_stats_offset(int B, int V, int C, int H, int W);
 
 // sweep_pack.hip: the channel statistics alone (mean-centring on), for the pack kernels of pack_dist.hip
 hipError_t launch_feature_stats(const SweepArgs& a, float* stats, hipStream_t stream);

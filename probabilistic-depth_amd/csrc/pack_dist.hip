@@ -13,6 +13,7 @@
 
 #include "dist_layout.hpp"
 #include "kernels.hpp"
+#include "sweep_workspace.hpp"
 
 namespace pdepth {
 
@@ -378,17 +379,13 @@ __global__ __launch_bounds__(256) void pack_views_dist_kernel(const float* __res
 
 // statistics + packed source of the distance-form kernel (what launch_pack_c4 is for the other two)
 hipError_t launch_pack_dist(const SweepArgs& a, void* workspace, hipStream_t stream) {
-    int* flags = reinterpret_cast<int*>(workspace);
-    char* packed = static_cast<char*>(workspace) + sweep_ws_flag_bytes(a.B, a.H, a.W);
-    float* stats = reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
-    int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + sweep_ws_flag_only_bytes(a.B, a.H, a.W));
-    const int nflags = (int)(sweep_ws_flag_only_bytes(a.B, a.H, a.W) / sizeof(int));
+    const SweepWorkspace ws = SweepWorkspace::of(workspace, a);
     const bool split = pack_dist_split(a.H, a.W);
     dim3 grid(split ? pack_dist_waves(a.H, a.W, PACK_ROWS) : (pack_dist_waves(a.H, a.W, PACK_ROWS) + 3) / 4, a.B * a.V);
-    hipError_t e = launch_feature_stats(a, stats, stream);
+    hipError_t e = launch_feature_stats(a, ws.stats, stream);
     if (e != hipSuccess) return e;
 #define PDEPTH_PACK_DIST(N, R) hipLaunchKernelGGL((pack_dist_kernel<N, R, SPLIT_>), grid, dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, a.V, a.C, \
-                                                  a.H, a.W, packed, flags, nflags, queue, stats)
+                                                  a.H, a.W, ws.packed, ws.flags, ws.nflags, ws.queue, ws.stats)
 #define PDEPTH_PACK_DIST_R(N) do { if (split) { constexpr bool SPLIT_ = true; PDEPTH_PACK_DIST(N, PACK_ROWS); } else { constexpr bool SPLIT_ = false; PDEPTH_PACK_DIST(N, PACK_ROWS); } } while (0)
     switch (dist::nchk(a.C)) {
         case 0: PDEPTH_PACK_DIST_R(0); break;
@@ -402,19 +399,15 @@ hipError_t launch_pack_dist(const SweepArgs& a, void* workspace, hipStream_t str
 
 hipError_t launch_pack_views_dist(const SweepArgs& a, const float* feat, const float* rgb, int rate, int img_h, int img_w, float* ref_out,
                                   void* workspace, hipStream_t stream) {
-    int* flags = reinterpret_cast<int*>(workspace);
-    char* packed = static_cast<char*>(workspace) + sweep_ws_flag_bytes(a.B, a.H, a.W);
-    float* stats = reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
-    int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + sweep_ws_flag_only_bytes(a.B, a.H, a.W));
-    hipError_t e = launch_view_stats(a, feat, rgb, rate, img_h, img_w, stats, stream);
+    const SweepWorkspace ws = SweepWorkspace::of(workspace, a);
+    hipError_t e = launch_view_stats(a, feat, rgb, rate, img_h, img_w, ws.stats, stream);
     if (e != hipSuccess) return e;
-    const int nflags = (int)(sweep_ws_flag_only_bytes(a.B, a.H, a.W) / sizeof(int));
     // (source views: 4 waves of 64 x ROWS texels per block; the reference view: 256 pixels per block)
     const bool split = pack_dist_split(a.H, a.W);
     dim3 grid(std::max(split ? pack_dist_waves(a.H, a.W, PACK_ROWS) : (pack_dist_waves(a.H, a.W, PACK_ROWS) + 3) / 4, (a.H * a.W + 255) / 256),
               a.B * (a.V + 1));
 #define PDEPTH_PACK_VIEWS_DIST(N, R) hipLaunchKernelGGL((pack_views_dist_kernel<N, R, SPLIT_>), grid, dim3(256), 0, stream, feat, rgb, a.V, a.C - 3, a.H, a.W, \
-                                                        rate, img_h, img_w, packed, ref_out, flags, nflags, queue, stats)
+                                                        rate, img_h, img_w, ws.packed, ref_out, ws.flags, ws.nflags, ws.queue, ws.stats)
 #define PDEPTH_PACK_VIEWS_DIST_R(N) do { if (split) { constexpr bool SPLIT_ = true; PDEPTH_PACK_VIEWS_DIST(N, PACK_ROWS); } else { constexpr bool SPLIT_ = false; PDEPTH_PACK_VIEWS_DIST(N, PACK_ROWS); } } while (0)
     switch (dist::nchk(a.C)) {
         case 0: PDEPTH_PACK_VIEWS_DIST_R(0); break;

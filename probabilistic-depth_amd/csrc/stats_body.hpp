@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "kernels.hpp"
+#include "sweep_workspace.hpp"
 
 namespace pdepth {
 namespace stats_body {

@@ -42,6 +42,7 @@
 #include "epipolar_probe.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "sweep_workspace.hpp"
 #include "wave_util.hpp"
 
 #include "sweep_dist_knobs.hpp"
@@ -67,7 +68,7 @@ struct DistArgs {
     int tiles_x, ntile;
     int one_each;   // no queue: workgroup i runs item i (launch_inst says when)
     int nblk;       // workgroups of the launch
-    int nonce;  // 1 .. 2047, another one per launch: tags the diagnostics count of this call (kernels.hpp: DIST_NONCE_SLOT)
+    int nonce;  // 1 .. 2047, another one per launch: tags the diagnostics count of this call (sweep_workspace.hpp: DIST_NONCE_SLOT)
 };
 #define KARG(type, field) kernarg_at<type>(offsetof(DistArgs, field))
 
@@ -1047,14 +1048,14 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     }
 }
 
-// 1 .. 2047, another one per launch of any instantiation (kernels.hpp: DIST_NONCE_SLOT)
+// 1 .. 2047, another one per launch of any instantiation (sweep_workspace.hpp: DIST_NONCE_SLOT)
 inline int next_nonce() {
     static std::atomic<unsigned> launches{0};
     return (int)(launches.fetch_add(1) % 2047u) + 1;
 }
 
 template <int NCHK, int NH>
-hipError_t launch_inst(const SweepArgs& a, const char* packed, const float* stats, int* queue, int tiles_x, int tiles, hipStream_t stream) {
+hipError_t launch_inst(const SweepArgs& a, const SweepWorkspace& ws, int tiles_x, int tiles, hipStream_t stream) {
     auto kern = sweep_dist_kernel<NCHK, NH>;
     // persistent grid: as many workgroups as the chip holds at once (registers and LDS decide: asked once per
     // instantiation and device), a multiple of 8; fewer when there is less work
@@ -1068,16 +1069,13 @@ hipError_t launch_inst(const SweepArgs& a, const char* packed, const float* stat
     }
     long long nblk = ((long long)sweep_device_cus() * per_cu[dev] + 7) & ~7ll;
     DistArgs da;
-    da.a = a; da.packed = packed; da.stats = stats; da.queue = queue; da.tiles_x = tiles_x; da.ntile = tiles;
+    da.a = a; da.packed = ws.packed; da.stats = ws.stats; da.queue = ws.queue; da.tiles_x = tiles_x; da.ntile = tiles;
     // The queue counters: memory-side atomics on ONE line are served one after the other (~13 ns each: 32 768 pops of the
     // headline launch on eight neighbouring ints took 0.42 ms whatever the kernel did in between); 256 bytes apart they are not.
-    {
-        const int nflags = (int)(sweep_ws_flag_only_bytes(a.B, a.H, a.W) / sizeof(int));   // >= 64
-        int qs = DIST_QSTRIDE;
-        while (qs * 8 > nflags) qs >>= 1;
-        da.qcnt = queue - nflags;
-        da.qstride = qs;
-    }
+    int qs = DIST_QSTRIDE;
+    while (qs * 8 > ws.nflags) qs >>= 1;   // (nflags >= 64)
+    da.qcnt = ws.dist_queue_counters();
+    da.qstride = qs;
     da.nonce = next_nonce();
     // up to DIST_ONE_EACH_X items per resident workgroup there is no queue: a workgroup per item (sweep_dist_knobs.hpp)
     const long long need = 8ll * ((tiles + 7) / 8) * 4 * a.B;   // a workgroup per pixel block of the largest XCD band, times 8
@@ -1100,9 +1098,7 @@ bool sweep_dist_supports(const SweepArgs& a) {
 // NCHW entry: channel statistics + pack kernel (launch_pack_dist), then the sweep kernel.  Packed entry: the sweep kernel alone.
 hipError_t launch_sweep_dist(const SweepArgs& a, void* workspace, hipStream_t stream, bool packed_ready) {
     const int tiles_x = (a.W + 15) / 16, tiles_y = (a.H + 3) / 4, tiles = tiles_x * tiles_y;
-    const char* packed = static_cast<const char*>(workspace) + sweep_ws_flag_bytes(a.B, a.H, a.W);
-    int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + sweep_ws_flag_only_bytes(a.B, a.H, a.W));
-    const float* stats = reinterpret_cast<const float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
+    const SweepWorkspace ws = SweepWorkspace::of(workspace, a);
     if (!packed_ready) {
         hipError_t e = launch_pack_dist(a, workspace, stream);
         if (e != hipSuccess) return e;
@@ -1110,16 +1106,16 @@ hipError_t launch_sweep_dist(const SweepArgs& a, void* workspace, hipStream_t st
     const int nck = dist::nchk(a.C);
     hipError_t e;
     if (a.D <= 64)
-        e = nck == 0 ? launch_inst<0, 1>(a, packed, stats, queue, tiles_x, tiles, stream)
-                     : (nck == 1 ? launch_inst<1, 1>(a, packed, stats, queue, tiles_x, tiles, stream) : launch_inst<2, 1>(a, packed, stats, queue, tiles_x, tiles, stream));
+        e = nck == 0 ? launch_inst<0, 1>(a, ws, tiles_x, tiles, stream)
+                     : (nck == 1 ? launch_inst<1, 1>(a, ws, tiles_x, tiles, stream) : launch_inst<2, 1>(a, ws, tiles_x, tiles, stream));
     else
-        e = nck == 0 ? launch_inst<0, 2>(a, packed, stats, queue, tiles_x, tiles, stream)
-                     : (nck == 1 ? launch_inst<1, 2>(a, packed, stats, queue, tiles_x, tiles, stream) : launch_inst<2, 2>(a, packed, stats, queue, tiles_x, tiles, stream));
+        e = nck == 0 ? launch_inst<0, 2>(a, ws, tiles_x, tiles, stream)
+                     : (nck == 1 ? launch_inst<1, 2>(a, ws, tiles_x, tiles, stream) : launch_inst<2, 2>(a, ws, tiles_x, tiles, stream));
     if (e != hipSuccess || a.src == nullptr) return e;
     // NCHW entry: the items the kernel left alone (fp16 overflow, guard, conditioning: flag 1 of their statistics row) are
     // evaluated by the gather kernel on the caller's tensor, in the reference's own rounding; on the usual input every block
     // of this launch reads one flag and leaves
-    return launch_sweep_direct_items(a, reinterpret_cast<const int*>(stats + STATS_FLAGS) + 1, STATS_STRIDE, stream);
+    return launch_sweep_direct_items(a, reinterpret_cast<const int*>(ws.stats + STATS_FLAGS) + 1, STATS_STRIDE, stream);
 }
 
 }  // namespace pdepth

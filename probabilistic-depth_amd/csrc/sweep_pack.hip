@@ -1,32 +1,18 @@
 // Pre-pass of the packed-source sweep kernels: channel statistics of the source view, then the source views in the
 // staging layout the sweep kernels load 16 bytes at a time, plus the workspace bookkeeping they share.
-//
-// Workspace of a sweep call (pdepth_sweep_workspace_bytes):
-//     [tile flags: one int per (batch item, 16x4 tile)]      tiles handed to the gather kernel (LDS-tiled kernel only)
-//     [64 ints]                                              queue counters of the persistent kernels + the slots of kernels.hpp
-//     [packed source: B*V x (ceil(C/4) + 2) x H x W float4]  planes g < ceil(C/4): channels 4g..4g+3 of every texel, minus
-//                                                            mu[c]; then the two Gram planes
-//     [reserved: as many bytes as the tile flags]            (a retired kernel's tile list; keeps the statistics where they were)
-//     [statistics: B x STATS_STRIDE floats]                  mu[c] (the constant subtracted per channel; zeros = not centred)
-//                                                            at +0, var[c] at +STATS_VAR
-//
-// Mean-centring: mu[b][c] = mean of channel c over a sample of 8 rows of source view 0 of item b -- an estimate is all it
-// takes, what matters is that the residual offset is small against the spread.  The distance-form layout is centred
-// (pack_dist.hip reads these statistics).  The layout packed here is not (the LDS-tiled kernel: direct form on the near
-// planes): mu = 0, and the pre-pass raises NONCENTRED_SLOT when the squared channel offsets exceed half the summed
-// variances; the tiled kernel then evaluates every plane directly.
+// The workspace they write into, and the mean-centring rule, are described in sweep_workspace.hpp.
 #include <hip/hip_runtime.h>
 
 #include "dist_layout.hpp"
 #include "kernels.hpp"
 #include "pack_body.hpp"
 #include "stats_body.hpp"
+#include "sweep_workspace.hpp"
 
 namespace pdepth {
 
 namespace {
 
-constexpr int TW = 16, TH = 4;
 using namespace stats_body;
 
 __global__ __launch_bounds__(256) void feature_stats_kernel(const float* __restrict__ src, long long bstride, long long vstride, int V,
@@ -258,44 +244,19 @@ __global__ __launch_bounds__(256) void clear_flags_kernel(int* flags, int nflags
     if (blockIdx.x == 0 && pa.d_candi != nullptr) route_ill_conditioned_items(stats, pa);
 }
 
-size_t flag_only_bytes(int B, int H, int W) {
-    const size_t tiles = (size_t)((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-    return ((size_t)B * tiles * sizeof(int) + 255) & ~(size_t)255;
-}
-size_t flag_bytes(int B, int H, int W) { return flag_only_bytes(B, H, W) + 256; }
-// (the larger of the two staging layouts: channel-group-planar float4 + Gram planes | the distance-form kernel's fp16 planes, dist_layout.hpp)
-size_t packed_bytes(int B, int V, int C, int H, int W) {
-    const size_t c4 = (size_t)B * V * ((C + 3) / 4 + 2) * H * W * sizeof(float4);
-    const size_t d16 = C <= dist::MAX_C ? (((size_t)B * V * (size_t)dist::view_bytes(C, H, W) + 255) & ~(size_t)255) : 0;
-    return c4 > d16 ? c4 : d16;
-}
-
 }  // namespace
-
-size_t sweep_ws_flag_only_bytes(int B, int H, int W) { return flag_only_bytes(B, H, W); }
-size_t sweep_ws_flag_bytes(int B, int H, int W) { return flag_bytes(B, H, W); }
-size_t sweep_ws_stats_offset(int B, int V, int C, int H, int W) {
-    // flags + queue counters, packed source, then the reserved bytes a retired kernel's tile list occupied (header)
-    return flag_bytes(B, H, W) + packed_bytes(B, V, C, H, W) + flag_only_bytes(B, H, W);
-}
-size_t sweep_tiled_workspace_bytes(int B, int V, int C, int H, int W) {
-    return sweep_ws_stats_offset(B, V, C, H, W) + (((size_t)B * STATS_STRIDE * sizeof(float) + 255) & ~(size_t)255);
-}
 
 // pre-pass of a call: channel statistics, packed source + Gram planes, tile flags and queue counters cleared
 hipError_t launch_pack_c4(const SweepArgs& a, void* workspace, hipStream_t stream) {
-    int* flags = reinterpret_cast<int*>(workspace);
-    float4* packed = reinterpret_cast<float4*>(static_cast<char*>(workspace) + flag_bytes(a.B, a.H, a.W));
-    float* stats = reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
+    const SweepWorkspace ws = SweepWorkspace::of(workspace, a);
     const int HW = a.H * a.W;
     hipLaunchKernelGGL(feature_stats_kernel, dim3(a.C < STATS_VAR ? a.C : STATS_VAR, a.B), dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, 1,
-                       (const float*)nullptr, 0ll, a.C, a.H, a.W, stats, 0);
+                       (const float*)nullptr, 0ll, a.C, a.H, a.W, ws.stats, 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     dim3 pgrid((HW + 255) / 256, a.B * a.V);
-    int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
-    hipLaunchKernelGGL(pack_c4_kernel, pgrid, dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, a.V, a.C, a.H, a.W, packed,
-                       flags, (int)(flag_only_bytes(a.B, a.H, a.W) / sizeof(int)), a, queue, stats);
+    hipLaunchKernelGGL(pack_c4_kernel, pgrid, dim3(256), 0, stream, a.src, a.src_bstride, a.src_vstride, a.V, a.C, a.H, a.W,
+                       reinterpret_cast<float4*>(ws.packed), ws.flags, ws.nflags, a, ws.queue, ws.stats);
     return hipGetLastError();
 }
 
@@ -313,28 +274,24 @@ hipError_t launch_view_stats(const SweepArgs& a, const float* feat, const float*
 // the encoder epilogue (pack_views_kernel): a.C = Cf + 3, a.V source views, views V+1 per item in feat / rgb
 hipError_t launch_pack_views(const SweepArgs& a, const float* feat, const float* rgb, int rate, int img_h, int img_w, float* ref_out,
                              void* workspace, hipStream_t stream) {
-    int* flags = reinterpret_cast<int*>(workspace);
-    float4* packed = reinterpret_cast<float4*>(static_cast<char*>(workspace) + flag_bytes(a.B, a.H, a.W));
-    float* stats = reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
-    int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
+    const SweepWorkspace ws = SweepWorkspace::of(workspace, a);
     const int HW = a.H * a.W;
     hipLaunchKernelGGL(view_stats_kernel, dim3(a.C < STATS_VAR ? a.C : STATS_VAR, a.B), dim3(256), 0, stream, feat, rgb, a.V, a.C - 3, a.H,
-                       a.W, rate, img_h, img_w, stats, 0);
+                       a.W, rate, img_h, img_w, ws.stats, 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     dim3 pgrid((HW + 255) / 256, a.B * (a.V + 1));
-    hipLaunchKernelGGL(pack_views_kernel, pgrid, dim3(256), 0, stream, feat, rgb, a.V, a.C - 3, a.H, a.W, rate, img_h, img_w, packed, ref_out,
-                       flags, (int)(flag_only_bytes(a.B, a.H, a.W) / sizeof(int)), queue, stats, a.B);
+    hipLaunchKernelGGL(pack_views_kernel, pgrid, dim3(256), 0, stream, feat, rgb, a.V, a.C - 3, a.H, a.W, rate, img_h, img_w,
+                       reinterpret_cast<float4*>(ws.packed), ref_out, ws.flags, ws.nflags, ws.queue, ws.stats, a.B);
     return hipGetLastError();
 }
 
 // The pre-pass also clears the tile flags and queue counters; a call of the LDS-tiled kernel on an already packed source
 // clears them itself (the guard slot the pre-pass wrote stays).
 hipError_t clear_sweep_flags(const SweepArgs& a, void* workspace, hipStream_t stream) {
-    int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
-    const int nflags = (int)(flag_bytes(a.B, a.H, a.W) / sizeof(int));
-    hipLaunchKernelGGL(clear_flags_kernel, dim3((nflags + 2047) / 2048), dim3(256), 0, stream, reinterpret_cast<int*>(workspace), nflags, queue, a,
-                       reinterpret_cast<float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W)));
+    const SweepWorkspace ws = SweepWorkspace::of(workspace, a);
+    const int nflags = ws.nflags + QUEUE_INTS;   // (the queue ints too, but for the two slots the kernel keeps)
+    hipLaunchKernelGGL(clear_flags_kernel, dim3((nflags + 2047) / 2048), dim3(256), 0, stream, ws.flags, nflags, ws.queue, a, ws.stats);
     return hipGetLastError();
 }
 

@@ -54,6 +54,7 @@
 
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "sweep_workspace.hpp"
 
 namespace pdepth {
 
@@ -911,16 +912,10 @@ static size_t tiled_lds_bytes(int D) {
            (size_t)(D + 2 * (D / 8 + 1)) * sizeof(float);
 }
 
-// Largest D whose cost tile fits LDS next to the window (2 blocks per CU).
-
 #if PDEPTH_NSUB == 1
 // Largest D whose cost tile fits LDS next to the window buffers (2 blocks per CU).
 int sweep_tiled_max_planes() { return 160; }
-#endif
 
-static size_t flag_only_bytes(int B, int H, int W) { return sweep_ws_flag_only_bytes(B, H, W); }
-static size_t flag_bytes(int B, int H, int W) { return sweep_ws_flag_bytes(B, H, W); }
-#if PDEPTH_NSUB == 1
 // Two tiles per block pay off when two such blocks fit a CU (the cost tiles of both sub-tiles live in LDS: D <= 64)
 // and the image is large enough for the wider windows not to dominate; measured on the BASELINE configurations.
 // (PDEPTH_ALGO_TILED_1 / _2 force a variant.)
@@ -951,12 +946,11 @@ hipError_t PDEPTH_CAT(launch_sweep_tiled_n, PDEPTH_NSUB)(const SweepArgs& a, voi
     const int tiles16_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;  // the gather kernel's (and the flags') tiles
     const int tiles_x = (a.W + TW * NSUB - 1) / (TW * NSUB);                  // this kernel's work items per row
     const int tiles = tiles_x * tiles_y;
-    int* flags = reinterpret_cast<int*>(workspace);
-    float4* packed = reinterpret_cast<float4*>(static_cast<char*>(workspace) + flag_bytes(a.B, a.H, a.W));
+    const SweepWorkspace ws = SweepWorkspace::of(workspace, a);
+    const float4* packed = reinterpret_cast<const float4*>(ws.packed);
     hipError_t e = packed_ready ? clear_sweep_flags(a, workspace, stream) : launch_pack_c4(a, workspace, stream);
     if (e != hipSuccess) return e;
     const size_t lds = tiled_lds_bytes(a.D);
-    int* queue = reinterpret_cast<int*>(static_cast<char*>(workspace) + flag_only_bytes(a.B, a.H, a.W));
     // persistent grid: as many blocks as the device holds at once (3 per CU at D <= 64), a multiple of 8
     const int n_cu = sweep_device_cus();
     const int per_cu = (int)((160 * 1024) / (lds + 640));
@@ -967,17 +961,16 @@ hipError_t PDEPTH_CAT(launch_sweep_tiled_n, PDEPTH_NSUB)(const SweepArgs& a, voi
     if (full <= nblk) nblk = (int)full;
     dim3 grid(nblk);
     // (routing: the pre-pass / the flag clear of this call has set flag 1 of the statistics row of every ill-conditioned item)
-    const float* route_stats = reinterpret_cast<const float*>(static_cast<char*>(workspace) + sweep_ws_stats_offset(a.B, a.V, a.C, a.H, a.W));
     if (a.metric == 0 && a.D == 64 && a.C == 67 && a.V == 1)
-        e = launch_tiled_kernel<0, true>(a, grid, lds, stream, packed, flags, queue, tiles_x, tiles, route_stats);
+        e = launch_tiled_kernel<0, true>(a, grid, lds, stream, packed, ws.flags, ws.queue, tiles_x, tiles, ws.stats);
     else if (a.metric == 0)
-        e = launch_tiled_kernel<0, false>(a, grid, lds, stream, packed, flags, queue, tiles_x, tiles, route_stats);
+        e = launch_tiled_kernel<0, false>(a, grid, lds, stream, packed, ws.flags, ws.queue, tiles_x, tiles, ws.stats);
     else
-        e = launch_tiled_kernel<1, false>(a, grid, lds, stream, packed, flags, queue, tiles_x, tiles, route_stats);
+        e = launch_tiled_kernel<1, false>(a, grid, lds, stream, packed, ws.flags, ws.queue, tiles_x, tiles, ws.stats);
     if (e != hipSuccess) return e;
     SweepArgs ag = a;
     ag.packed_src = packed;   // (the gather kernel's source when the caller passed a packed source only)
-    return launch_sweep_direct_flagged(ag, flags, queue + GATHER_COUNT_SLOT, tiles16_x, tiles16_x * tiles_y, stream);
+    return launch_sweep_direct_flagged(ag, ws.flags, ws.queue + GATHER_COUNT_SLOT, tiles16_x, tiles16_x * tiles_y, stream);
 }
 
 }  // namespace pdepth

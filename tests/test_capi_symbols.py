@@ -165,9 +165,9 @@ def test_product_library_carries_no_lab_bench():
 
 def test_binding_reads_the_workspace_slots_the_kernels_write():
     """_native.py reads diagnostics out of the 64 workspace ints behind the tile flags; the slot numbers and layout tags are
-    those of csrc/kernels.hpp."""
+    those of csrc/sweep_workspace.hpp."""
     import re
-    hpp = open(os.path.join(REPO, "probabilistic-depth_amd", "csrc", "kernels.hpp")).read()
+    hpp = open(os.path.join(REPO, "probabilistic-depth_amd", "csrc", "sweep_workspace.hpp")).read()
     consts = {k: int(v) for k, v in re.findall(r"\b([A-Z][A-Z0-9_]*)\s*=\s*(\d+)\s*[,;]", hpp)}
     for name in ("NONCENTRED_SLOT", "LAYOUT_SLOT", "DIST_DIRECT_LAST_SLOT", "DIST_NONCE_SLOT", "LAYOUT_C4", "LAYOUT_DIST16"):
         assert name in consts, name
