@@ -57,7 +57,8 @@ extern "C" {
                                 *    library must be re-packed; PDEPTH_ALGO_CORR is refused (PDEPTH_E_ARG; since retired with CELLS and MFMA);
                                 *    backward-compatible additions within 6: pdepth_sweep_backward_f32, pdepth_dpv_reduce_backward_f32,
                                 *    pdepth_dpv_expect_backward_f32; pdepth_dpv_soft_ce_workspace_bytes, pdepth_dpv_soft_ce_f32,
-                                *    pdepth_dpv_soft_ce_backward_f32; pdepth_depth_metrics_workspace_bytes, pdepth_depth_metrics_f32 */
+                                *    pdepth_dpv_soft_ce_backward_f32; pdepth_depth_metrics_workspace_bytes, pdepth_depth_metrics_f32;
+                                *    pdepth_dpv_fuse_backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -315,6 +316,22 @@ int pdepth_ufield_f32(const float *dpv, const float *d_candi, const float *intr,
 int pdepth_dpv_fuse_f32(const float *logp, const float *dmaps, const float *masks, const float *d_candi,
                         int32_t B, int32_t D, int32_t H, int32_t W, float var, float eps, float *fused,
                         float *logfused, void *stream);
+
+/*
+ * Backward of pdepth_dpv_fuse_f32 with respect to logp (what autograd does behind models/models.py:666-672 for BV_cur; the
+ * prior of gen_dpv_withmask, utils/img_utils.py:360-375, is built from data and is constant).  Per pixel, with m the clamped
+ * prior the forward builds:
+ *     u = exp(logp + log m),  q = u / sum_k u_k             (fused = clamp(q, eps, 1), logfused = log fused)
+ *     c = pass (g_fused q + g_logfused),  pass = (eps <= q <= 1), torch.clamp's rule
+ *     g_logp = c - q sum_k c_k
+ *   logp, dmaps, masks, d_candi, B, D, H, W, var, eps as in the forward: m and q are recomputed from them with the forward's
+ *   arithmetic, neither output volume is needed;
+ *   g_fused, g_logfused [B,D,H,W] contiguous, either may be NULL (= zero, and not read), not both;
+ *   g_logp [B,D,H,W], may not alias an input.  No atomics: reproducible bit for bit.  H*W <= 2^30, B <= 65535.
+ */
+int pdepth_dpv_fuse_backward_f32(const float *logp, const float *dmaps, const float *masks, const float *d_candi,
+                                 const float *g_fused, const float *g_logfused, int32_t B, int32_t D, int32_t H, int32_t W,
+                                 float var, float eps, float *g_logp, void *stream);
 
 /*
  * The reference's native correlation operator, forward and backward: replaces correlation_forward_cuda /

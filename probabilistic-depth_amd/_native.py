@@ -59,6 +59,7 @@ _SIGNATURES = {
     "pdepth_dpv_expect_backward_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 3),
     "pdepth_dpv_moments_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 3),
     "pdepth_dpv_fuse_f32": (c_int, [_P] * 4 + [_I] * 4 + [_F, _F] + [_P] * 3),
+    "pdepth_dpv_fuse_backward_f32": (c_int, [_P] * 6 + [_I] * 4 + [_F, _F] + [_P] * 2),
     "pdepth_ufield_workspace_bytes": (_Z, [_I] * 3),
     "pdepth_ufield_f32": (c_int, [_P] * 4 + [_I] * 5 + [_F] * 4 + [_I, _F] + [_P] * 3 + [_Z, _P]),
     "pdepth_correlation_output_size": (c_int, [_I] * 7 + [POINTER(c_int32)] * 3),
@@ -75,10 +76,10 @@ _SIGNATURES = {
     "pdepth_depth_metrics_f32": (c_int, [_P] * 5 + [_F] + [_I] * 4 + [_P] * 4 + [_Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss and metrics entries live in objects of their own (csrc/loss.hip, csrc/metrics.hip).  The product library must have
-# them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it loads, and a loss or metrics
-# call on it raises (_loss_entry, _metrics_entry)
-_ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if "_soft_ce_" in n or "_depth_metrics_" in n)
+# The loss, metrics and fusion-backward entries live in objects of their own (csrc/loss.hip, csrc/metrics.hip,
+# csrc/dpv_fuse_bwd.hip).  The product library must have them; an experiment library named by PDEPTH_LIB may be linked from a
+# subset of the objects: it loads, and a call of such an entry on it raises (_loss_entry, _metrics_entry, _fuse_bwd_entry)
+_ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if "_soft_ce_" in n or "_depth_metrics_" in n or "_fuse_backward_" in n)
 
 
 _lib = None
@@ -810,6 +811,43 @@ def dpv_expect_backward(dpv, d_candi, bv_log, g_depth):
     with _on_device(dpv.device):
         rc = lib.pdepth_dpv_expect_backward_f32(dpv.data_ptr(), d_candi.data_ptr(), B, D, H, W, int(bool(bv_log)), g_depth.data_ptr(),
                                                 out.data_ptr(), _stream(dpv.device))
+    _check(rc, lib)
+    return out
+
+
+def _fuse_bwd_entry(lib, name):
+    """The fusion-backward entry of the loaded library; a library linked without csrc/dpv_fuse_bwd.o is an error here."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise RuntimeError(f"{name}: the loaded library was linked without csrc/dpv_fuse_bwd.hip; there is no fallback")
+    return fn
+
+
+def dpv_fuse_backward(logp, dmaps, masks, d_candi, var, eps, g_fused=None, g_logfused=None):
+    """The inputs of dpv_fuse + any of g_fused, g_logfused [B,D,H,W] -> g_logp [B,D,H,W] (pdepth_dpv_fuse_backward_f32)."""
+    who = "dpv_fuse_backward"
+    if g_fused is None and g_logfused is None:
+        raise RuntimeError(f"{who}: no incoming gradient")
+    if logp.dim() != 4:
+        raise RuntimeError(f"{who}: logp must be [B,D,H,W]")
+    B, D, H, W = logp.shape
+    if tuple(dmaps.shape) != (B, H, W) or tuple(masks.shape) != (B, H, W) or d_candi.numel() != D:
+        raise RuntimeError(f"{who}: dmaps/masks must be [B,H,W] and d_candi [D]")
+    for nm, g in (("g_fused", g_fused), ("g_logfused", g_logfused)):
+        if g is not None:
+            _shape(g, (B, D, H, W), nm, who)
+    lib = load()
+    _dev(logp, "logp"), _dev(dmaps, "dmaps"), _dev(masks, "masks"), _dev(d_candi, "d_candi")
+    logp, dmaps, masks, d_candi = (t.contiguous() for t in (logp, dmaps, masks, d_candi))
+    gs = [None if g is None else g.contiguous().float() for g in (g_fused, g_logfused)]
+    for nm, g in zip(("g_fused", "g_logfused"), gs):
+        if g is not None:
+            _dev(g, nm)
+    out = torch.empty_like(logp)
+    with _on_device(logp.device):
+        rc = _fuse_bwd_entry(lib, "pdepth_dpv_fuse_backward_f32")(logp.data_ptr(), dmaps.data_ptr(), masks.data_ptr(),
+                                                                  d_candi.data_ptr(), _ptr(gs[0]), _ptr(gs[1]), B, D, H, W,
+                                                                  float(var), float(eps), out.data_ptr(), _stream(logp.device))
     _check(rc, lib)
     return out
 

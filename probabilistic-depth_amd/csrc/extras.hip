@@ -4,12 +4,14 @@
 //               Gaussian soft label of a sparse depth map over the depth candidates, blend it with the
 //               uniform DPV by the validity mask, multiply it into the network's DPV, renormalise, clamp,
 //               take the log -- one kernel, one read of the log-DPV, two writes, instead of ~12 passes.
+//               Its backward with respect to the log-DPV is csrc/dpv_fuse_bwd.hip (same lane layout, same helpers).
 // correlation -- forward of the reference's only native operator (models/correlation_package/
 //               correlation_cuda_kernel.cu:41-114; semantics pinned by models/correlation_native.py:13-23):
 //               out[b, (dy+r)*(2r+1) + (dx+r), y, x] = mean_c x1[b,c,y,x] * x2[b,c,y+dy*s2,x+dx*s2] (zero padded).
 //               It is dead code w.r.t. get_model (only PWCLite uses it), provided for completeness.
 #include <hip/hip_runtime.h>
 
+#include "dpv_fuse_math.hpp"
 #include "geometry.hpp"
 #include "kernels.hpp"
 
@@ -19,21 +21,7 @@ namespace pdepth {
 // and its sum; fused product and its sum; normalise + write), so the log-DPV is read once and each output written
 // once: 4*HW*(D*(1+outputs)+2) bytes.  DREG = planes held in registers (64 or 128); deeper volumes take the
 // re-reading kernel below.
-// exp / log / divide of the fusion kernels: hardware exp2 / log2 with an exact-argument reduction (exp_nonpos, geometry.hpp:
-// ~1.5 ulp), log2 x ln 2 (~2 ulp, absolute 1e-7 near 1) and a refined reciprocal -- the libm forms cost ~20 instructions
-// each, five per element, and made the kernel VALU bound (127 us for 402 MB).  -DPDEPTH_LIBM_FUSE restores them.
-#ifdef PDEPTH_LIBM_FUSE
-__device__ __forceinline__ float fuse_exp(float x) { return expf(x); }
-__device__ __forceinline__ float fuse_log(float x) { return logf(x); }
-__device__ __forceinline__ float fuse_div(float a, float b, float) { return a / b; }
-__device__ __forceinline__ float fuse_rcp(float) { return 0.0f; }
-#else
-__device__ __forceinline__ float fuse_exp(float x) { return exp_nonpos(x); }
-__device__ __forceinline__ float fuse_log(float x) { return __builtin_amdgcn_logf(x) * 0.693147180559945309417f; }
-__device__ __forceinline__ float fuse_div(float a, float, float rb) { return a * rb; }
-__device__ __forceinline__ float fuse_rcp(float b) { return refined_rcp(b); }
-#endif
-
+// exp / log / divide: fuse_exp / fuse_log / fuse_div / fuse_rcp of dpv_fuse_math.hpp, shared with the backward.
 template <int DREG>
 __global__ __launch_bounds__(256) void dpv_fuse_reg_kernel(const float* __restrict__ logp,
                                                            const float* __restrict__ dmaps,

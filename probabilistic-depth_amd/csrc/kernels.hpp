@@ -92,6 +92,12 @@ hipError_t launch_dpv_reduce_backward(const float* logp, const float* d_candi, i
 hipError_t launch_dpv_expect_backward(const float* dpv, const float* d_candi, int B, int D, int H, int W, int bv_log,
                                       const float* g_depth, float* g_dpv, hipStream_t stream);
 
+// dpv_fuse_bwd.hip: gradient of launch_dpv_fuse (extras.hip) with respect to logp, recomputed from the forward's inputs; g_fused
+// (into fused) / g_logfused (into logfused) may be nullptr, not both
+hipError_t launch_dpv_fuse_backward(const float* logp, const float* dmaps, const float* masks, const float* d_candi,
+                                    const float* g_fused, const float* g_logfused, int B, int D, int H, int W, float var, float eps,
+                                    float* g_logp, hipStream_t stream);
+
 // capi.hip: sets the message pdepth_last_error() returns on this thread, returns code
 int api_error(int code, const char* msg);
 

@@ -236,12 +236,13 @@ class _SweepFeatures:
 
 
 class BaseModel(nn.Module):
-    """Host model.  nmode "default" trains: with grad mode on, the sweep and the DPV reductions run through their HIP backward
-    passes (ops: gradients with respect to the feature maps and the volumes; the sweep then takes the concatenated NCHW
-    features), so forward + loss.backward() work as in the reference's training loop (trainer/default_trainer.py:87-169).
-    The other nmodes are inference-only: dpv_fuse ("default_upsample") and warp_feature ("default_feedback") have no
-    backward and raise if an input requires grad while grad mode is on; wrap those calls in torch.no_grad() as the
-    reference's evaluation loop does (trainer/default_trainer.py:171)."""
+    """Host model.  nmodes "default" and "default_upsample" train: with grad mode on, the sweep, the DPV reductions and the
+    DPV fusion run through their HIP backward passes (ops: gradients with respect to the feature maps and the volumes; the
+    sweep then takes the concatenated NCHW features; the sparse depth maps and masks of the fusion are data), so forward +
+    loss.backward() work as in the reference's training loop (trainer/default_trainer.py:87-169).
+    nmode "default_feedback" is inference-only: warp_feature has no backward and raises if an input requires grad while
+    grad mode is on; wrap that call in torch.no_grad() as the reference's evaluation loop does
+    (trainer/default_trainer.py:171)."""
 
     def __init__(self, cfg, id):
         super().__init__()

@@ -224,12 +224,17 @@ def dpv_fuse(logp, dmaps, masks, d_candi, var=0.3, eps=None, want_fused=True, wa
 
     utils/img_utils.py:360-375 (gen_dpv_withmask) + models/models.py:666-672 in one kernel.
     masks may be [B,1,H,W] (reference layout, channel 0 is used) or [B,H,W].
-    Returns (fused probabilities | None, log fused | None).
+    Returns (fused probabilities | None, log fused | None).  Differentiable with respect to logp only (csrc/dpv_fuse_bwd.hip);
+    the depth maps, the masks and the candidates are data.
     """
     if eps is None:
         eps = torch.finfo(float).eps  # reference: utils/img_utils.py:12
     if masks.dim() == 4:
         masks = masks[:, 0]
+    if _wants_grad(logp):
+        _refuse_grad("dpv_fuse", dmaps=dmaps, masks=masks, d_candi=d_candi)
+        return _DpvFuseFn.apply(logp, dmaps.float(), masks.float(), d_candi_tensor(d_candi, logp.device), float(var), float(eps),
+                                bool(want_fused), bool(want_log))
     return _native.dpv_fuse(logp, dmaps.float(), masks.float(), d_candi_tensor(d_candi, logp.device), var, eps,
                             want_fused, want_log)
 
@@ -237,8 +242,9 @@ def dpv_fuse(logp, dmaps, masks, d_candi, var=0.3, eps=None, want_fused=True, wa
 # ---- autograd ---------------------------------------------------------------------------------------------------------------
 # The public functions above take the autograd path only when grad mode is on and a feature / volume input requires grad;
 # every other call runs the no-grad code unchanged.  The Functions' forwards call the same _native forwards (same algo), so
-# values are bit-identical to the no-grad call; their backwards are the HIP kernels of csrc/sweep_bwd.hip and csrc/dpv_bwd.hip.
-# Differentiable: the feature maps (ref, NCHW src), logits, addend, the DPV of dpv_expect.  Not differentiable: the geometry
+# values are bit-identical to the no-grad call; their backwards are the HIP kernels of csrc/sweep_bwd.hip, csrc/dpv_bwd.hip and
+# csrc/dpv_fuse_bwd.hip.
+# Differentiable: the feature maps (ref, NCHW src), logits, addend, the DPV of dpv_expect, the log-DPV of dpv_fuse.  Not differentiable: the geometry
 # (K, R, t, rays, cxcy, d_candi -- the reference's training takes them from the data loader), which is refused when it
 # requires grad.
 
@@ -323,6 +329,28 @@ class _DpvReduceFn(torch.autograd.Function):
         if g_logp is not None or g_prob is not None or g_depth is not None:
             g = _native.dpv_reduce_backward(logp, dc, g_logp=g_logp, g_prob=g_prob, g_depth=g_depth)
         return (g if ctx.needs_input_grad[0] else None, g if ctx.needs_input_grad[1] else None) + (None,) * 7
+
+
+class _DpvFuseFn(torch.autograd.Function):
+    """dpv_fuse under autograd: (fused | None, log fused | None).  Nothing but the inputs is saved: the backward recomputes the
+    prior and the unclamped posterior (a clamped plane's output no longer holds it)."""
+
+    @staticmethod
+    def forward(ctx, logp, dmaps, masks, dc, var, eps, want_fused, want_log):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logp, dmaps, masks, dc)
+        ctx.cfg = (var, eps)
+        return _native.dpv_fuse(logp, dmaps, masks, dc, var, eps, want_fused, want_log)
+
+    @staticmethod
+    def backward(ctx, g_fused, g_logfused):
+        if g_fused is None and g_logfused is None:
+            return (None,) * 8
+        logp, dmaps, masks, dc = ctx.saved_tensors
+        g = _native.dpv_fuse_backward(logp, dmaps, masks, dc, ctx.cfg[0], ctx.cfg[1],
+                                      None if g_fused is None else g_fused.contiguous(),
+                                      None if g_logfused is None else g_logfused.contiguous())
+        return (g,) + (None,) * 7
 
 
 class _DpvExpectFn(torch.autograd.Function):
