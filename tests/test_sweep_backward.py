@@ -14,6 +14,7 @@ import pdepth_amd
 from pdepth_amd import _native, ops, synth
 from oracle import ref_cpu as O
 from util import golden
+from util_sweep_backward import hip_grads, l1_allowance, oracle_grads, rel_err, to_dev
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,87 +24,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def dev():
     assert torch.cuda.is_available(), "GPU suite needs a GPU"
     return torch.device("cuda:0")
-
-
-def to_dev(b, dev):
-    return {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
-
-
-def oracle_cost(ref, src, b, sigma, metric, dtype):
-    """est_swp_volume_v4 restated on device tensors of `dtype` (grid from oracle.ref_cpu.plane_coords, fp32, cast) -> [B,D,H,W]."""
-    B, V, C, H, W = src.shape
-    d32 = torch.from_numpy(np.asarray(b["d_candi"]).astype(np.float32))
-    D = d32.numel()
-    out = []
-    for i in range(B):
-        K = b["K"][i].cpu()
-        cx, cy = K.numpy()[0, 2], K.numpy()[1, 2]
-        cost = 0
-        for v in range(V):
-            grid = O.plane_coords(K, b["R"][i, v].cpu(), b["t"][i, v].cpu(), b["rays"][i].cpu(), d32, cx, cy).reshape(D, H, W, 2)
-            grid = grid.to(device=src.device, dtype=dtype)
-            warped = F.grid_sample(src[i, v].unsqueeze(0).expand(D, C, H, W), grid, mode="bilinear", padding_mode="zeros",
-                                   align_corners=False)
-            diff = warped - ref[i].unsqueeze(0)
-            dist = (diff ** 2).sum(1) if metric == "L2" else diff.abs().sum(1)
-            cost = cost + dist / sigma
-        out.append(cost)
-    return torch.stack(out)
-
-
-def oracle_grads(b, gup, sigma, metric, dtype, dev):
-    ref = b["ref"].to(dev, dtype).detach().clone().requires_grad_(True)
-    src = b["src"].to(dev, dtype).detach().clone().requires_grad_(True)
-    (oracle_cost(ref, src, b, sigma, metric, dtype) * gup.to(dtype)).sum().backward()
-    return ref.grad, src.grad
-
-
-def hip_grads(d, gup, sigma, metric, algo="auto"):
-    ref = d["ref"].clone().requires_grad_(True)
-    src = d["src"].clone().requires_grad_(True)
-    cost = ops.sweep_cost(ref, src, d["K"], d["R"], d["t"], d["rays"], d["cxcy"], d["d_candi"], sigma, feat_dist=metric, algo=algo)
-    (cost * gup).sum().backward()
-    return ref.grad, src.grad, cost
-
-
-def rel_err(g, g64, allow=None):
-    """max |g - g64| / max |g64|; with `allow`, the excess over the per-element allowance (see l1_allowance)."""
-    d = (g.double() - g64).abs()
-    if allow is not None:
-        d = (d - allow).clamp_min(0)
-    return float(d.max() / g64.abs().max())
-
-
-def l1_allowance(b, gup, sigma, dev, tau=1e-5):
-    """(allow_ref, allow_src): how far a correct fp32 evaluation of the L1 gradient may be from the float64 one.
-
-    d|e|/de = sign(e) jumps at e = 0.  Where the float64 difference e of a (view, plane, pixel, channel) sample is within
-    fp32 rounding of zero (|e| <= tau (1 + |ref|): some ten times the fp32 error of e), an fp32 evaluation may take the other
-    branch -- sign +-1 or 0 instead of the float64 one --, a change of up to 2 g / sigma in g_ref and 2 g w_t / sigma in g_src
-    at the sample's taps (about one sample in 1e5 at the shapes below).  The allowance is exactly that bound, summed over the
-    ambiguous samples; every other element is held to the plain criterion."""
-    dt = torch.float64
-    ref = b["ref"].to(dev, dt)
-    src = b["src"].to(dev, dt).detach().clone().requires_grad_(True)
-    B, V, C, H, W = src.shape
-    d32 = torch.from_numpy(np.asarray(b["d_candi"]).astype(np.float32))
-    D = d32.numel()
-    g = gup.to(dev, dt).abs() * (2.0 / sigma)
-    allow_ref = torch.zeros_like(ref)
-    total = 0
-    for i in range(B):
-        K = b["K"][i].cpu()
-        cx, cy = K.numpy()[0, 2], K.numpy()[1, 2]
-        for v in range(V):
-            grid = O.plane_coords(K, b["R"][i, v].cpu(), b["t"][i, v].cpu(), b["rays"][i].cpu(), d32, cx, cy).reshape(D, H, W, 2)
-            warped = F.grid_sample(src[i, v].unsqueeze(0).expand(D, C, H, W), grid.to(dev, dt), mode="bilinear",
-                                   padding_mode="zeros", align_corners=False)
-            amb = ((warped.detach() - ref[i].unsqueeze(0)).abs() <= tau * (1 + ref[i].abs().unsqueeze(0))).to(dt)
-            w = amb * g[i].unsqueeze(1)                                     # [D,C,H,W]
-            allow_ref[i] += w.sum(0)
-            total = total + (w * warped).sum()                              # d/dsrc = the taps' weights times w
-    total.backward()
-    return allow_ref, src.grad
 
 
 CASES = [  # metric, V, C, D, pose, cx_off
