@@ -76,10 +76,11 @@ _SIGNATURES = {
     "pdepth_depth_metrics_f32": (c_int, [_P] * 5 + [_F] + [_I] * 4 + [_P] * 4 + [_Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, metrics and fusion-backward entries live in objects of their own (csrc/loss.hip, csrc/metrics.hip,
-# csrc/dpv_fuse_bwd.hip).  The product library must have them; an experiment library named by PDEPTH_LIB may be linked from a
-# subset of the objects: it loads, and a call of such an entry on it raises (_loss_entry, _metrics_entry, _fuse_bwd_entry)
-_ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if "_soft_ce_" in n or "_depth_metrics_" in n or "_fuse_backward_" in n)
+# The loss, metrics and fusion-backward entries live in objects of their own: part of an entry's name -> the source file.  The
+# product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
+# loads, and a call of such an entry on it raises (_entry)
+_SOURCE_OF_ENTRY = {"_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip"}
+_ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if any(part in n for part in _SOURCE_OF_ENTRY))
 
 
 _lib = None
@@ -161,6 +162,26 @@ def _check(rc, lib):
         if rc == 1 and "does not run on a packed source" in msg:   # PDEPTH_E_ARG of the packing entry points for such a shape
             raise UnsupportedShape(msg)
         raise RuntimeError(msg)
+
+
+def _entry(lib, name):
+    """An entry of the loaded library that lives in an object of its own (_SOURCE_OF_ENTRY); a library linked without that
+    object is an error here, there is no other path."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        source = next(src for part, src in _SOURCE_OF_ENTRY.items() if part in name)
+        raise RuntimeError(f"{name}: the loaded library was linked without {source}; there is no fallback")
+    return fn
+
+
+def _volume_dims(who, volume, d_candi, name):
+    """(B, D, H, W) of a [B,D,H,W] volume (`name` in the message) with one depth candidate per plane."""
+    if volume.dim() != 4:
+        raise RuntimeError(f"{who}: {name} must be [B,D,H,W]")
+    D = volume.shape[1]
+    if d_candi.numel() != D:
+        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    return tuple(volume.shape)
 
 
 def _dev(t: torch.Tensor, name: str) -> int:
@@ -420,13 +441,8 @@ def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
     lib = load()
     _no_autograd("dpv_reduce", logits)   # (in place it would also overwrite a tensor that carries a grad_fn)
     _dev(logits, "logits")
-    if logits.dim() != 4:
-        raise RuntimeError("dpv_reduce: logits must be [B,D,H,W]")
-    logits = logits.contiguous()
-    B, D, H, W = logits.shape
-    d_candi = d_candi.contiguous()
-    if d_candi.numel() != D:
-        raise RuntimeError(f"dpv_reduce: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    B, D, H, W = _volume_dims("dpv_reduce", logits, d_candi, "logits")
+    logits, d_candi = logits.contiguous(), d_candi.contiguous()
     dev = logits.device
     logp = (logits if inplace else torch.empty_like(logits)) if want_logp else None
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
@@ -445,18 +461,13 @@ def dpv_reduce_ex(logits, d_candi, addend=None, want_logp=True, want_prob=False,
     lib = load()
     _no_autograd("dpv_reduce_ex", logits, addend)
     _dev(logits, "logits")
-    if logits.dim() != 4:
-        raise RuntimeError("dpv_reduce_ex: logits must be [B,D,H,W]")
-    logits = logits.contiguous()
-    B, D, H, W = logits.shape
-    if addend is not None:
+    if addend is not None and logits.dim() == 4:   # (the addend's shape before the candidates: the order these checks have had)
         _dev(addend, "addend")
-        if tuple(addend.shape) != (B, D, H, W):
+        if addend.shape != logits.shape:
             raise RuntimeError(f"dpv_reduce_ex: addend shape {tuple(addend.shape)} != logits {tuple(logits.shape)}")
         addend = addend.contiguous()
-    d_candi = d_candi.contiguous()
-    if d_candi.numel() != D:
-        raise RuntimeError(f"dpv_reduce_ex: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    B, D, H, W = _volume_dims("dpv_reduce_ex", logits, d_candi, "logits")
+    logits, d_candi = logits.contiguous(), d_candi.contiguous()
     dev = logits.device
     out = {}
     if want_logp:
@@ -519,13 +530,8 @@ def dpv_expect(dpv, d_candi, bv_log):
     lib = load()
     _no_autograd("dpv_expect", dpv)
     _dev(dpv, "dpv")
-    if dpv.dim() != 4:
-        raise RuntimeError("dpv_expect: dpv must be [B,D,H,W]")
-    dpv = dpv.contiguous()
-    B, D, H, W = dpv.shape
-    d_candi = d_candi.contiguous()
-    if d_candi.numel() != D:
-        raise RuntimeError(f"dpv_expect: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    B, D, H, W = _volume_dims("dpv_expect", dpv, d_candi, "dpv")
+    dpv, d_candi = dpv.contiguous(), d_candi.contiguous()
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dpv.device)
     with torch.cuda.device(dpv.device):
         rc = lib.pdepth_dpv_expect_f32(_dev(dpv, "dpv"), _dev(d_candi, "d_candi"), B, D, H, W, int(bool(bv_log)),
@@ -539,13 +545,8 @@ def dpv_moments(dpv, d_candi, bv_log=True):
     lib = load()
     _no_autograd("dpv_moments", dpv)
     _dev(dpv, "dpv")
-    if dpv.dim() != 4:
-        raise RuntimeError("dpv_moments: dpv must be [B,D,H,W]")
-    dpv = dpv.contiguous()
-    B, D, H, W = dpv.shape
-    d_candi = d_candi.contiguous()
-    if d_candi.numel() != D:
-        raise RuntimeError(f"dpv_moments: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    B, D, H, W = _volume_dims("dpv_moments", dpv, d_candi, "dpv")
+    dpv, d_candi = dpv.contiguous(), d_candi.contiguous()
     mean = torch.empty((B, H, W), dtype=torch.float32, device=dpv.device)
     var = torch.empty_like(mean)
     with torch.cuda.device(dpv.device):
@@ -770,11 +771,7 @@ def dpv_reduce_backward(logp, d_candi, g_logp=None, g_prob=None, g_depth=None):
     who = "dpv_reduce_backward"
     if g_logp is None and g_prob is None and g_depth is None:
         raise RuntimeError(f"{who}: no incoming gradient")
-    if logp.dim() != 4:
-        raise RuntimeError(f"{who}: logp must be [B,D,H,W]")
-    B, D, H, W = logp.shape
-    if d_candi.numel() != D:
-        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    B, D, H, W = _volume_dims(who, logp, d_candi, "logp")
     for nm, g, shp in (("g_logp", g_logp, (B, D, H, W)), ("g_prob", g_prob, (B, D, H, W)), ("g_depth", g_depth, (B, H, W))):
         if g is not None:
             _shape(g, shp, nm, who)
@@ -797,11 +794,7 @@ def dpv_reduce_backward(logp, d_candi, g_logp=None, g_prob=None, g_depth=None):
 def dpv_expect_backward(dpv, d_candi, bv_log, g_depth):
     """dpv [B,D,H,W], g_depth [B,H,W] -> g_dpv [B,D,H,W] (pdepth_dpv_expect_backward_f32)."""
     who = "dpv_expect_backward"
-    if dpv.dim() != 4:
-        raise RuntimeError(f"{who}: dpv must be [B,D,H,W]")
-    B, D, H, W = dpv.shape
-    if d_candi.numel() != D:
-        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    B, D, H, W = _volume_dims(who, dpv, d_candi, "dpv")
     _shape(g_depth, (B, H, W), "g_depth", who)
     lib = load()
     _dev(dpv, "dpv"), _dev(d_candi, "d_candi")
@@ -813,14 +806,6 @@ def dpv_expect_backward(dpv, d_candi, bv_log, g_depth):
                                                 out.data_ptr(), _stream(dpv.device))
     _check(rc, lib)
     return out
-
-
-def _fuse_bwd_entry(lib, name):
-    """The fusion-backward entry of the loaded library; a library linked without csrc/dpv_fuse_bwd.o is an error here."""
-    fn = getattr(lib, name, None)
-    if fn is None:
-        raise RuntimeError(f"{name}: the loaded library was linked without csrc/dpv_fuse_bwd.hip; there is no fallback")
-    return fn
 
 
 def dpv_fuse_backward(logp, dmaps, masks, d_candi, var, eps, g_fused=None, g_logfused=None):
@@ -845,9 +830,9 @@ def dpv_fuse_backward(logp, dmaps, masks, d_candi, var, eps, g_fused=None, g_log
             _dev(g, nm)
     out = torch.empty_like(logp)
     with _on_device(logp.device):
-        rc = _fuse_bwd_entry(lib, "pdepth_dpv_fuse_backward_f32")(logp.data_ptr(), dmaps.data_ptr(), masks.data_ptr(),
-                                                                  d_candi.data_ptr(), _ptr(gs[0]), _ptr(gs[1]), B, D, H, W,
-                                                                  float(var), float(eps), out.data_ptr(), _stream(logp.device))
+        rc = _entry(lib, "pdepth_dpv_fuse_backward_f32")(logp.data_ptr(), dmaps.data_ptr(), masks.data_ptr(), d_candi.data_ptr(),
+                                                         _ptr(gs[0]), _ptr(gs[1]), B, D, H, W, float(var), float(eps),
+                                                         out.data_ptr(), _stream(logp.device))
     _check(rc, lib)
     return out
 
@@ -855,11 +840,7 @@ def dpv_fuse_backward(logp, dmaps, masks, d_candi, var, eps, g_fused=None, g_log
 # ---- training loss (ops.dpv_soft_ce) ------------------------------------------------------------------------------------------
 def _soft_ce_args(who, logp, d_candi, label, depth_gt, variance, mask, pow):
     """Shape checks (before any device check) and the contiguous fp32 tensors of the two cross-entropy entries."""
-    if logp.dim() != 4:
-        raise RuntimeError(f"{who}: logp must be [B,D,H,W]")
-    B, D, H, W = logp.shape
-    if d_candi.numel() != D:
-        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, volume has D={D}")
+    B, D, H, W = _volume_dims(who, logp, d_candi, "logp")
     if (label is None) == (depth_gt is None):
         raise RuntimeError(f"{who}: give exactly one label source, label [B,D,H,W] or depth_gt [B,H,W]")
     if label is not None:
@@ -886,14 +867,6 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _loss_entry(lib, name):
-    """A loss entry of the loaded library; a library linked without csrc/loss.o is an error here, there is no other path."""
-    fn = getattr(lib, name, None)
-    if fn is None:
-        raise RuntimeError(f"{name}: the loaded library was linked without csrc/loss.hip; there is no fallback")
-    return fn
-
-
 def dpv_soft_ce(logp, d_candi, label=None, depth_gt=None, variance=None, mask=None, want_depth=False, pow=2.0):
     """logp [B,D,H,W] + (label [B,D,H,W] | depth_gt [B,H,W], variance) [+ mask [B,H,W]] -> (loss [B], count [B], depth [B,H,W] |
     None): pdepth_dpv_soft_ce_f32 on the current stream, no host synchronisation."""
@@ -904,12 +877,12 @@ def dpv_soft_ce(logp, d_candi, label=None, depth_gt=None, variance=None, mask=No
     dev = logp.device
     out = torch.empty((2, B), dtype=torch.float32, device=dev)
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
-    ws_bytes = _loss_entry(lib, "pdepth_dpv_soft_ce_workspace_bytes")(B, H, W)
+    ws_bytes = _entry(lib, "pdepth_dpv_soft_ce_workspace_bytes")(B, H, W)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     with _on_device(dev):
-        rc = _loss_entry(lib, "pdepth_dpv_soft_ce_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw, _ptr(mask),
-                                        B, D, H, W, out[0].data_ptr(), out[1].data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
-                                        _stream(dev))
+        rc = _entry(lib, "pdepth_dpv_soft_ce_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw, _ptr(mask),
+                                                   B, D, H, W, out[0].data_ptr(), out[1].data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
+                                                   _stream(dev))
     _check(rc, lib)
     return out[0], out[1], depth
 
@@ -935,22 +908,14 @@ def dpv_soft_ce_backward(logp, d_candi, count, label=None, depth_gt=None, varian
     lib = load()
     out = torch.empty_like(logp)
     with _on_device(logp.device):
-        rc = _loss_entry(lib, "pdepth_dpv_soft_ce_backward_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw, _ptr(mask),
-                                                 count.data_ptr(), B, D, H, W, _ptr(g_loss), _ptr(g_depth), out.data_ptr(),
-                                                 _stream(logp.device))
+        rc = _entry(lib, "pdepth_dpv_soft_ce_backward_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw,
+                                                            _ptr(mask), count.data_ptr(), B, D, H, W, _ptr(g_loss), _ptr(g_depth),
+                                                            out.data_ptr(), _stream(logp.device))
     _check(rc, lib)
     return out
 
 
 # ---- evaluation metrics (ops.depth_metrics) -----------------------------------------------------------------------------------
-def _metrics_entry(lib, name):
-    """A metrics entry of the loaded library; a library linked without csrc/metrics.o is an error here, there is no other path."""
-    fn = getattr(lib, name, None)
-    if fn is None:
-        raise RuntimeError(f"{name}: the loaded library was linked without csrc/metrics.hip; there is no fallback")
-    return fn
-
-
 def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_max=None, want_depth=False):
     """truth [B,H,W] + (pred [B,H,W] | logp [B,D,H,W], d_candi [D]) [+ mask [B,H,W]] -> (metrics [B,9], count [B], depth [B,H,W] |
     None): pdepth_depth_metrics_f32 on the current stream, no host synchronisation.  clamp_max None or <= 0: no clamp."""
@@ -988,12 +953,12 @@ def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_ma
     out = torch.empty(B * 10, dtype=torch.float32, device=dev)
     metrics, count = out[:B * 9].view(B, 9), out[B * 9:]
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
-    ws_bytes = _metrics_entry(lib, "pdepth_depth_metrics_workspace_bytes")(B, H, W)
+    ws_bytes = _entry(lib, "pdepth_depth_metrics_workspace_bytes")(B, H, W)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     with _on_device(dev):
-        rc = _metrics_entry(lib, "pdepth_depth_metrics_f32")(_ptr(logp), _ptr(pred), _ptr(d_candi), truth.data_ptr(), _ptr(mask),
-                                                             float(clamp_max) if clamp_max is not None else 0.0, B, D, H, W,
-                                                             metrics.data_ptr(), count.data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
-                                                             _stream(dev))
+        rc = _entry(lib, "pdepth_depth_metrics_f32")(_ptr(logp), _ptr(pred), _ptr(d_candi), truth.data_ptr(), _ptr(mask),
+                                                     float(clamp_max) if clamp_max is not None else 0.0, B, D, H, W,
+                                                     metrics.data_ptr(), count.data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
+                                                     _stream(dev))
     _check(rc, lib)
     return metrics, count, depth

@@ -2,49 +2,34 @@
 // No torch types, no allocation, no host synchronisation.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 
-#include "../../include/pdepth.h"
+#include "capi_util.hpp"
 #include "kernels.hpp"
 #include "sweep_workspace.hpp"
 
 namespace {
 
+using namespace pdepth::capi;
+
 thread_local char g_err[512] = "";
 
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// every dimension positive: of a descriptor, of the entries that take B, D (or C), H, W as plain arguments
+// every dimension positive of a descriptor
 bool dims_positive(const pdepth_sweep_desc* d) { return d->B > 0 && d->V > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0; }
-int check_dims(const char* who, const pdepth_sweep_desc* d) {
+int check_desc_dims(const char* who, const pdepth_sweep_desc* d) {
     if (dims_positive(d)) return PDEPTH_OK;
     return fail(PDEPTH_E_ARG, "%s: non-positive dimension B=%d V=%d C=%d D=%d H=%d W=%d", who, d->B, d->V, d->C, d->D, d->H, d->W);
 }
-int check_dims(const char* who, int32_t B, int32_t D, int32_t H, int32_t W) {
-    if (B > 0 && D > 0 && H > 0 && W > 0) return PDEPTH_OK;
-    return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
-}
-
-// a sweep workspace: present, large enough, 256-byte aligned
-int check_workspace(const char* who, const void* workspace, size_t bytes, size_t need) {
-    if (!workspace || bytes < need)
-        return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu); query pdepth_sweep_workspace_bytes()", who, need, bytes);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-        return fail(PDEPTH_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
-    return PDEPTH_OK;
-}
 size_t workspace_bytes_of(const pdepth_sweep_desc* d) { return pdepth::sweep_workspace_bytes(d->B, d->V, d->C, d->H, d->W); }
+// a sweep workspace: present, large enough, 256-byte aligned
+int check_sweep_workspace(const char* who, const pdepth_sweep_desc* d, const void* workspace, size_t bytes) {
+    return check_workspace(who, workspace, bytes, workspace_bytes_of(d),
+                           "; query pdepth_sweep_workspace_bytes()");
+}
 
 int check_desc(const pdepth_sweep_desc* d, const pdepth_camera* cam, const char* who) {
     if (!d || !cam) return fail(PDEPTH_E_ARG, "%s: null descriptor", who);
-    if (int rc = check_dims(who, d)) return rc;
+    if (int rc = check_desc_dims(who, d)) return rc;
     if ((long long)d->H * d->W > (1ll << 30))
         return fail(PDEPTH_E_ARG, "%s: H*W too large", who);
     if (!cam->K || !cam->R || !cam->t || !cam->rays || !cam->cxcy)
@@ -73,15 +58,13 @@ pdepth::SweepArgs make_args(const pdepth_sweep_desc* d, const pdepth_camera* cam
 
 }  // namespace
 
-// for C entries defined beside their kernels (loss.hip): the message pdepth_last_error() returns on this thread
-int pdepth::api_error(int code, const char* msg) { return fail(code, "%s", msg); }
+// where every fail() of capi_util.hpp ends: the message pdepth_last_error() returns on this thread
+int pdepth::api_error(int code, const char* msg) {
+    snprintf(g_err, sizeof(g_err), "%s", msg);
+    return code;
+}
 
 namespace {
-
-int launched(hipError_t e, const char* who) {
-    if (e != hipSuccess) return fail(PDEPTH_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
-    return PDEPTH_OK;
-}
 
 // does ALGO_AUTO run on a packed copy of the source for this shape?
 bool uses_packed_source(const pdepth_sweep_desc* d) {
@@ -137,7 +120,7 @@ int sweep_common(const pdepth_sweep_desc* d, const pdepth_camera* cam, const flo
     // the tiled kernel addresses one view through a 32-bit buffer descriptor (C*H*W*4 bytes < 2^31)
     // (the tiled kernels also pack a footprint as two 16-bit coordinates)
     if (uses_packed_source(d)) {
-        if (int rc = check_workspace(who, workspace, workspace_bytes, workspace_bytes_of(d))) return rc;
+        if (int rc = check_sweep_workspace(who, d, workspace, workspace_bytes)) return rc;
         if (d->algo == PDEPTH_ALGO_TILED_1)
             return launched(pdepth::launch_sweep_tiled_n1(a, workspace, (hipStream_t)stream, packed_ready), who);
         if (d->algo == PDEPTH_ALGO_TILED_2)
@@ -190,12 +173,12 @@ int pdepth_pack_source_f32(const pdepth_sweep_desc* desc, const float* src, void
                            void* stream) {
     const char* who = "pdepth_pack_source_f32";
     if (!desc || !src) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    if (int rc = check_dims(who, desc)) return rc;
+    if (int rc = check_desc_dims(who, desc)) return rc;
     if (desc->src_vstride < (long long)desc->C * desc->H * desc->W || desc->src_bstride < 0)
         return fail(PDEPTH_E_ARG, "%s: bad strides", who);
     if (!uses_packed_source(desc))
         return fail(PDEPTH_E_ARG, "%s: this shape / algorithm does not run on a packed source", who);
-    if (int rc = check_workspace(who, workspace, workspace_bytes, workspace_bytes_of(desc))) return rc;
+    if (int rc = check_sweep_workspace(who, desc, workspace, workspace_bytes)) return rc;
     const pdepth::SweepArgs a = make_args(desc, nullptr, nullptr, src);
     if (uses_dist(desc)) return launched(pdepth::launch_pack_dist(a, workspace, (hipStream_t)stream), who);
     return launched(pdepth::launch_pack_c4(a, workspace, (hipStream_t)stream), who);
@@ -211,7 +194,7 @@ int pdepth_pack_views_f32(const pdepth_sweep_desc* desc, const float* feat, cons
         return fail(PDEPTH_E_ARG, "%s: this shape / algorithm does not run on a packed source", who);
     if ((long long)desc->H * pool_rate * desc->W * pool_rate * 3 >= (1ll << 31))
         return fail(PDEPTH_E_ARG, "%s: image too large", who);
-    if (int rc = check_workspace(who, workspace, workspace_bytes, workspace_bytes_of(desc))) return rc;
+    if (int rc = check_sweep_workspace(who, desc, workspace, workspace_bytes)) return rc;
     const pdepth::SweepArgs a = make_args(desc);
     if (uses_dist(desc))
         return launched(pdepth::launch_pack_views_dist(a, feat, rgb, pool_rate, desc->H * pool_rate, desc->W * pool_rate, ref_out, workspace,

@@ -6,31 +6,98 @@
 // volume (log_softmax read+write, exp, mul, sum); here the logits are read once, held in
 // registers, and logp + depth are written once: 4*HW*(2D+1) bytes per item.
 //
-// Layout of a wave (vec4 kernel): lane = (plane group g = lane>>4, pixel quad q = lane&15).
-// A quad is 4 consecutive pixels (one 16-byte load); the 16 quads of a wave cover 256
-// contiguous bytes of every plane row, and the 4 plane groups interleave the D planes
-// (k = g + 4*i).  The per-pixel max / sum-exp / sum d*exp are combined across the 4 plane
-// groups with two xor-shuffles each (lanes l, l^16, l^32, l^48).
+// The vec4 kernels use the wave layout of dpv_lanes.hpp: lane = (plane group, pixel quad), the column of a pixel spread over
+// 4 lanes, per-pixel max / sum-exp / sum d*exp combined across the plane groups.
 #include <hip/hip_runtime.h>
 
+#include "dpv_lanes.hpp"
 #include "kernels.hpp"
 
 namespace pdepth {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
+// Extras of the extended reduction (pdepth_dpv_reduce_ex_f32): the same single pass with optional outputs, all from the
+// registers that already hold the column --
+//   addend   : x = logits + addend before the softmax   (feedback update log_softmax(BV_cur + BV_resi), models.py:694)
+//   prob     : exp(logp), the decoder's input            (models.py:697 torch.exp(BV_cur_upd), :651)
+//   variance : sum_k (d_k - E[d])^2 p_k                   (trainer/default_trainer.py:333-336)
+//   quarter  : logp at every 4th row and column, [B,D,H/4,W/4] = F.interpolate(logp, scale_factor=0.25,
+//              mode='nearest'), the next frame's prev_output (trainer/default_trainer.py:221)
+struct DpvExtras {
+    const float* addend;
+    float* prob;
+    float* variance;
+    float* quarter;
+    int W;
+};
 
-// streaming (non-temporal) 16-byte accesses: the volume is read once and written once (+5 % measured)
-__device__ __forceinline__ float4 load_nt(const float* p) {
-    const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void store_nt(float* p, float4 v) {
-    __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f*>(p));
-}
-
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-    return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m),
-                       __shfl_xor(v.w, m));
+// The log-softmax sweep of a lane's RPL planes + the expectation; EX: with the extras (compiled out of the plain kernel).
+template <int RPL, bool EX>
+__device__ __forceinline__ void dpv_reduce_lanes(const float* __restrict__ x, const float* __restrict__ dc, int D, int HW,
+                                                 float* logp, float* __restrict__ depth, const DpvExtras& ex) {
+    const QuadLane L = quad_lane(D, HW);
+    const int g = L.g, b = L.b;
+    const bool live = L.live;
+    float4 v[RPL];
+    load_planes(v, x, L, 0, D, HW, -INFINITY, true, EX ? ex.addend : nullptr);
+    float4 m = v[0];
+#pragma unroll
+    for (int i = 1; i < RPL; ++i) {
+        m.x = fmaxf(m.x, v[i].x); m.y = fmaxf(m.y, v[i].y); m.z = fmaxf(m.z, v[i].z); m.w = fmaxf(m.w, v[i].w);
+    }
+    m = group_max(m);
+    float4 sum = splat4(0.f);
+#pragma unroll
+    for (int i = 0; i < RPL; ++i) {
+        if (g + 4 * i < D) {
+            v[i].x -= m.x; v[i].y -= m.y; v[i].z -= m.z; v[i].w -= m.w;
+            sum.x += expf(v[i].x); sum.y += expf(v[i].y); sum.z += expf(v[i].z); sum.w += expf(v[i].w);
+        }
+    }
+    sum = group_sum(sum);
+    const float4 ls = make_float4(logf(sum.x), logf(sum.y), logf(sum.z), logf(sum.w));
+    float4 e = splat4(0.f);
+    // quarter-resolution copy: this lane's first pixel, when its row is a multiple of 4 (W % 4 == 0: a quad never
+    // straddles rows and starts at a column that is a multiple of 4)
+    int py = 0, pxq = 0, Wq = 0, Hq = 0;
+    bool qrow = false;
+    if (EX) {
+        const int pix = L.q * 4;
+        py = pix / ex.W, pxq = (pix - py * ex.W) >> 2;
+        Wq = ex.W >> 2, Hq = (HW / ex.W) >> 2;
+        qrow = ex.quarter && live && (py & 3) == 0 && (py >> 2) < Hq && pxq < Wq;
+    }
+#pragma unroll
+    for (int i = 0; i < RPL; ++i) {
+        const int k = g + 4 * i;
+        if (k < D) {
+            const float4 lp = make_float4(v[i].x - ls.x, v[i].y - ls.y, v[i].z - ls.z, v[i].w - ls.w);
+            const float4 p = make_float4(expf(lp.x), expf(lp.y), expf(lp.z), expf(lp.w));
+            if (EX) v[i] = p;   // (kept for the variance sweep)
+            if (live) {
+                if (logp) store_nt(logp + L.off + (size_t)k * HW, lp);
+                if (EX && ex.prob) store_nt(ex.prob + L.off + (size_t)k * HW, p);
+                if (EX && qrow) ex.quarter[((size_t)b * D + k) * Hq * Wq + (size_t)(py >> 2) * Wq + pxq] = lp.x;
+            }
+            expect_add<false>(e, dc[k], p);
+        }
+    }
+    e = group_sum(e);
+    if (depth && live && g == 0) *reinterpret_cast<float4*>(depth + L.poff) = e;
+    if (EX && ex.variance) {   // second sweep over the registers: sum_k (d_k - mean)^2 p_k with the mean just formed
+        float4 var = splat4(0.f);
+#pragma unroll
+        for (int i = 0; i < RPL; ++i) {
+            const int k = g + 4 * i;
+            if (k < D) {
+                const float dk = dc[k];
+                const float4 dd = make_float4(dk - e.x, dk - e.y, dk - e.z, dk - e.w);
+                var.x += (dd.x * dd.x) * v[i].x; var.y += (dd.y * dd.y) * v[i].y;
+                var.z += (dd.z * dd.z) * v[i].z; var.w += (dd.w * dd.w) * v[i].w;
+            }
+        }
+        var = group_sum(var);
+        if (live && g == 0) *reinterpret_cast<float4*>(ex.variance + L.poff) = var;
+    }
 }
 
 template <int RPL>
@@ -38,70 +105,7 @@ __global__ __launch_bounds__(256) void dpv_reduce_vec4_kernel(const float* __res
                                                               const float* __restrict__ dc,
                                                               int D, int HW, float* logp,
                                                               float* __restrict__ depth) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int g = lane >> 4;
-    const int quads = HW >> 2;
-    const int q = wave * 16 + (lane & 15);
-    const bool live = q < quads;
-    const int b = blockIdx.y;
-    const float* xb = x + (size_t)b * D * HW + (size_t)(live ? q : 0) * 4;
-
-    float4 v[RPL];
-    const float ninf = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        v[i] = (k < D && live) ? load_nt(xb + (size_t)k * HW)
-                               : make_float4(ninf, ninf, ninf, ninf);
-    }
-    float4 m = v[0];
-#pragma unroll
-    for (int i = 1; i < RPL; ++i) {
-        m.x = fmaxf(m.x, v[i].x); m.y = fmaxf(m.y, v[i].y);
-        m.z = fmaxf(m.z, v[i].z); m.w = fmaxf(m.w, v[i].w);
-    }
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = shfl_xor4(m, s);
-        m.x = fmaxf(m.x, o.x); m.y = fmaxf(m.y, o.y); m.z = fmaxf(m.z, o.z); m.w = fmaxf(m.w, o.w);
-    }
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        if (k < D) {
-            v[i].x -= m.x; v[i].y -= m.y; v[i].z -= m.z; v[i].w -= m.w;
-            sum.x += expf(v[i].x); sum.y += expf(v[i].y);
-            sum.z += expf(v[i].z); sum.w += expf(v[i].w);
-        }
-    }
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = shfl_xor4(sum, s);
-        sum.x += o.x; sum.y += o.y; sum.z += o.z; sum.w += o.w;
-    }
-    const float4 ls = make_float4(logf(sum.x), logf(sum.y), logf(sum.z), logf(sum.w));
-    float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-    float* lb = logp ? logp + (size_t)b * D * HW + (size_t)(live ? q : 0) * 4 : nullptr;
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        if (k < D) {
-            const float4 lp = make_float4(v[i].x - ls.x, v[i].y - ls.y, v[i].z - ls.z, v[i].w - ls.w);
-            if (lb && live) store_nt(lb + (size_t)k * HW, lp);
-            const float dk = dc[k];
-            e.x += dk * expf(lp.x); e.y += dk * expf(lp.y);
-            e.z += dk * expf(lp.z); e.w += dk * expf(lp.w);
-        }
-    }
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = shfl_xor4(e, s);
-        e.x += o.x; e.y += o.y; e.z += o.z; e.w += o.w;
-    }
-    if (depth && live && g == 0)
-        *reinterpret_cast<float4*>(depth + (size_t)b * HW + (size_t)q * 4) = e;
+    dpv_reduce_lanes<RPL, false>(x, dc, D, HW, logp, depth, DpvExtras{});
 }
 
 // Any D / any HW: one pixel per thread, three sweeps over the column (re-reads hit L2).
@@ -128,118 +132,11 @@ __global__ __launch_bounds__(256) void dpv_reduce_scalar_kernel(const float* x,
     if (depth) depth[(size_t)b * HW + pix] = e;
 }
 
-// Extended reduction (pdepth_dpv_reduce_ex_f32): the same single pass with optional extras, all from the registers
-// that already hold the column --
-//   addend   : x = logits + addend before the softmax   (feedback update log_softmax(BV_cur + BV_resi), models.py:694)
-//   prob     : exp(logp), the decoder's input            (models.py:697 torch.exp(BV_cur_upd), :651)
-//   variance : sum_k (d_k - E[d])^2 p_k                   (trainer/default_trainer.py:333-336)
-//   quarter  : logp at every 4th row and column, [B,D,H/4,W/4] = F.interpolate(logp, scale_factor=0.25,
-//              mode='nearest'), the next frame's prev_output (trainer/default_trainer.py:221)
-struct DpvExtras {
-    const float* addend;
-    float* prob;
-    float* variance;
-    float* quarter;
-    int W;
-};
-
 template <int RPL>
 __global__ __launch_bounds__(256) void dpv_reduce_ex_vec4_kernel(const float* __restrict__ x, const float* __restrict__ dc,
                                                                  int D, int HW, float* logp, float* __restrict__ depth,
                                                                  DpvExtras ex) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int g = lane >> 4;
-    const int quads = HW >> 2;
-    const int q = wave * 16 + (lane & 15);
-    const bool live = q < quads;
-    const int b = blockIdx.y;
-    const size_t off = (size_t)b * D * HW + (size_t)(live ? q : 0) * 4;
-    float4 v[RPL];
-    const float ninf = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        v[i] = make_float4(ninf, ninf, ninf, ninf);
-        if (k < D && live) {
-            v[i] = load_nt(x + off + (size_t)k * HW);
-            if (ex.addend) {
-                const float4 a = load_nt(ex.addend + off + (size_t)k * HW);
-                v[i].x += a.x; v[i].y += a.y; v[i].z += a.z; v[i].w += a.w;
-            }
-        }
-    }
-    float4 m = v[0];
-#pragma unroll
-    for (int i = 1; i < RPL; ++i) {
-        m.x = fmaxf(m.x, v[i].x); m.y = fmaxf(m.y, v[i].y); m.z = fmaxf(m.z, v[i].z); m.w = fmaxf(m.w, v[i].w);
-    }
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = shfl_xor4(m, s);
-        m.x = fmaxf(m.x, o.x); m.y = fmaxf(m.y, o.y); m.z = fmaxf(m.z, o.z); m.w = fmaxf(m.w, o.w);
-    }
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        if (g + 4 * i < D) {
-            v[i].x -= m.x; v[i].y -= m.y; v[i].z -= m.z; v[i].w -= m.w;
-            sum.x += expf(v[i].x); sum.y += expf(v[i].y); sum.z += expf(v[i].z); sum.w += expf(v[i].w);
-        }
-    }
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = shfl_xor4(sum, s);
-        sum.x += o.x; sum.y += o.y; sum.z += o.z; sum.w += o.w;
-    }
-    const float4 ls = make_float4(logf(sum.x), logf(sum.y), logf(sum.z), logf(sum.w));
-    float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-    // quarter-resolution copy: this lane's first pixel, when its row is a multiple of 4 (W % 4 == 0: a quad never
-    // straddles rows and starts at a column that is a multiple of 4)
-    const int pix = q * 4, py = pix / ex.W, pxq = (pix - py * ex.W) >> 2;
-    const int Wq = ex.W >> 2, Hq = (HW / ex.W) >> 2;
-    const bool qrow = ex.quarter && live && (py & 3) == 0 && (py >> 2) < Hq && pxq < Wq;
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        if (k < D) {
-            const float4 lp = make_float4(v[i].x - ls.x, v[i].y - ls.y, v[i].z - ls.z, v[i].w - ls.w);
-            const float4 p = make_float4(expf(lp.x), expf(lp.y), expf(lp.z), expf(lp.w));
-            v[i] = p;   // (kept for the variance sweep)
-            if (live) {
-                if (logp) store_nt(logp + off + (size_t)k * HW, lp);
-                if (ex.prob) store_nt(ex.prob + off + (size_t)k * HW, p);
-                if (qrow) ex.quarter[((size_t)b * D + k) * Hq * Wq + (size_t)(py >> 2) * Wq + pxq] = lp.x;
-            }
-            const float dk = dc[k];
-            e.x += dk * p.x; e.y += dk * p.y; e.z += dk * p.z; e.w += dk * p.w;
-        }
-    }
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = shfl_xor4(e, s);
-        e.x += o.x; e.y += o.y; e.z += o.z; e.w += o.w;
-    }
-    if (depth && live && g == 0) *reinterpret_cast<float4*>(depth + (size_t)b * HW + (size_t)q * 4) = e;
-    if (ex.variance) {   // second sweep over the registers: sum_k (d_k - mean)^2 p_k with the mean just formed
-        float4 var = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < RPL; ++i) {
-            const int k = g + 4 * i;
-            if (k < D) {
-                const float dk = dc[k];
-                const float4 dd = make_float4(dk - e.x, dk - e.y, dk - e.z, dk - e.w);
-                var.x += (dd.x * dd.x) * v[i].x; var.y += (dd.y * dd.y) * v[i].y;
-                var.z += (dd.z * dd.z) * v[i].z; var.w += (dd.w * dd.w) * v[i].w;
-            }
-        }
-#pragma unroll
-        for (int s = 16; s <= 32; s <<= 1) {
-            const float4 o = shfl_xor4(var, s);
-            var.x += o.x; var.y += o.y; var.z += o.z; var.w += o.w;
-        }
-        if (live && g == 0) *reinterpret_cast<float4*>(ex.variance + (size_t)b * HW + (size_t)q * 4) = var;
-    }
+    dpv_reduce_lanes<RPL, true>(x, dc, D, HW, logp, depth, ex);
 }
 
 // any D / any H, W: one pixel per thread (re-reads hit L2)
@@ -276,42 +173,24 @@ __global__ __launch_bounds__(256) void dpv_reduce_ex_scalar_kernel(const float* 
     if (ex.variance) ex.variance[(size_t)b * HW + pix] = var;
 }
 
-// Expectation with the wave layout of dpv_reduce_vec4_kernel: lane = (plane group g, pixel quad q), all loads of a
-// lane issued up front (RPL 16-byte non-temporal loads in flight per lane), partial sums combined by xor-shuffles.
+// Expectation in the wave layout: all loads of a lane issued up front (RPL 16-byte non-temporal loads in flight per lane).
+// The load loop is written out: through load_planes, whose optional arguments are all constant here, the log-DPV instantiations
+// were allocated and scheduled differently and ran 12 % (D = 64) and 48 % (D = 128) slower (profiles/r11_dpv_lanes/README.md).
 template <bool BV_LOG, int RPL>
 __global__ __launch_bounds__(256) void dpv_expect_vec4_kernel(const float* __restrict__ x,
                                                               const float* __restrict__ dc, int D, int HW,
                                                               float* __restrict__ depth) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int g = lane >> 4;
-    const int quads = HW >> 2;
-    const int q = wave * 16 + (lane & 15);
-    const bool live = q < quads;
-    const int b = blockIdx.y;
-    const float* xb = x + (size_t)b * D * HW + (size_t)(live ? q : 0) * 4;
+    const QuadLane L = quad_lane(D, HW);
     float4 v[RPL];
 #pragma unroll
     for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        v[i] = (k < D && live) ? load_nt(xb + (size_t)k * HW) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int k = L.g + 4 * i;
+        v[i] = (k < D && L.live) ? load_nt(x + L.off + (size_t)k * HW) : splat4(0.f);
     }
-    float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        if (k < D) {
-            const float dk = dc[k];
-            e.x += dk * (BV_LOG ? expf(v[i].x) : v[i].x); e.y += dk * (BV_LOG ? expf(v[i].y) : v[i].y);
-            e.z += dk * (BV_LOG ? expf(v[i].z) : v[i].z); e.w += dk * (BV_LOG ? expf(v[i].w) : v[i].w);
-        }
-    }
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = shfl_xor4(e, s);
-        e.x += o.x; e.y += o.y; e.z += o.z; e.w += o.w;
-    }
-    if (live && g == 0) *reinterpret_cast<float4*>(depth + (size_t)b * HW + (size_t)q * 4) = e;
+    float4 e = splat4(0.f);
+    expect_planes<BV_LOG>(e, v, dc, L.g, 0, D);
+    e = group_sum(e);
+    if (L.live && L.g == 0) *reinterpret_cast<float4*>(depth + L.poff) = e;
 }
 
 template <bool BV_LOG, int VEC>
@@ -342,24 +221,17 @@ __global__ __launch_bounds__(256) void dpv_expect_kernel(const float* __restrict
     for (int j = 0; j < VEC; ++j) depth[(size_t)b * HW + (size_t)i * VEC + j] = e[j];
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 hipError_t launch_dpv_reduce(const float* logits, const float* d_candi, int B, int D, int H,
                              int W, float* logp, float* depth, hipStream_t stream) {
     const int HW = H * W;
     const bool vec = (HW % 4 == 0) && aligned16(logits) && (!logp || aligned16(logp)) &&
                      (!depth || aligned16(depth)) && D <= 128;
+    const dim3 grid(n_blocks(H, W), B);
     if (vec) {
-        const int quads = HW / 4;
-        dim3 grid((quads + 63) / 64, B);
-        if (D <= 32)
-            hipLaunchKernelGGL(dpv_reduce_vec4_kernel<8>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth);
-        else if (D <= 64)
-            hipLaunchKernelGGL(dpv_reduce_vec4_kernel<16>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth);
-        else
-            hipLaunchKernelGGL(dpv_reduce_vec4_kernel<32>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth);
+        for_planes_per_lane(D, [&](auto rpl) {
+            hipLaunchKernelGGL(dpv_reduce_vec4_kernel<decltype(rpl)::value>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth);
+        });
     } else {
-        dim3 grid((HW + 255) / 256, B);
         hipLaunchKernelGGL(dpv_reduce_scalar_kernel, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth);
     }
     return hipGetLastError();
@@ -372,16 +244,12 @@ hipError_t launch_dpv_reduce_ex(const float* logits, const float* addend, const 
     const bool vec = (W % 4 == 0) && aligned16(logits) && (!addend || aligned16(addend)) && (!logp || aligned16(logp)) &&
                      (!prob || aligned16(prob)) && (!depth || aligned16(depth)) && (!variance || aligned16(variance)) &&
                      D <= 128 && !(logp == logits && addend);   // (in place with an addend: the scalar kernel's order)
+    const dim3 grid(n_blocks(H, W), B);
     if (vec) {
-        dim3 grid((HW / 4 + 63) / 64, B);
-        if (D <= 32)
-            hipLaunchKernelGGL(dpv_reduce_ex_vec4_kernel<8>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth, ex);
-        else if (D <= 64)
-            hipLaunchKernelGGL(dpv_reduce_ex_vec4_kernel<16>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth, ex);
-        else
-            hipLaunchKernelGGL(dpv_reduce_ex_vec4_kernel<32>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth, ex);
+        for_planes_per_lane(D, [&](auto rpl) {
+            hipLaunchKernelGGL(dpv_reduce_ex_vec4_kernel<decltype(rpl)::value>, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth, ex);
+        });
     } else {
-        dim3 grid((HW + 255) / 256, B);
         hipLaunchKernelGGL(dpv_reduce_ex_scalar_kernel, grid, dim3(256), 0, stream, logits, d_candi, D, HW, logp, depth, ex);
     }
     return hipGetLastError();
@@ -392,18 +260,18 @@ hipError_t launch_dpv_expect(const float* dpv, const float* d_candi, int B, int 
     const int HW = H * W;
     const bool vec = (HW % 4 == 0) && aligned16(dpv) && aligned16(depth);
     if (vec && D <= 128) {
-        dim3 grid((HW / 4 + 63) / 64, B);
-#define PDEPTH_EXPECT(RPL)                                                                                              \
-    if (bv_log) hipLaunchKernelGGL((dpv_expect_vec4_kernel<true, RPL>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth); \
-    else hipLaunchKernelGGL((dpv_expect_vec4_kernel<false, RPL>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth);
-        if (D <= 32) { PDEPTH_EXPECT(8) } else if (D <= 64) { PDEPTH_EXPECT(16) } else { PDEPTH_EXPECT(32) }
-#undef PDEPTH_EXPECT
+        const dim3 grid(n_blocks(H, W), B);
+        for_planes_per_lane(D, [&](auto rpl) {
+            constexpr int RPL = decltype(rpl)::value;
+            if (bv_log) hipLaunchKernelGGL((dpv_expect_vec4_kernel<true, RPL>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth);
+            else hipLaunchKernelGGL((dpv_expect_vec4_kernel<false, RPL>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth);
+        });
     } else if (vec) {
         dim3 grid((HW / 4 + 255) / 256, B);
         if (bv_log) hipLaunchKernelGGL((dpv_expect_kernel<true, 4>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth);
         else hipLaunchKernelGGL((dpv_expect_kernel<false, 4>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth);
     } else {
-        dim3 grid((HW + 255) / 256, B);
+        const dim3 grid(n_blocks(H, W), B);
         if (bv_log) hipLaunchKernelGGL((dpv_expect_kernel<true, 1>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth);
         else hipLaunchKernelGGL((dpv_expect_kernel<false, 1>), grid, dim3(256), 0, stream, dpv, d_candi, D, HW, depth);
     }

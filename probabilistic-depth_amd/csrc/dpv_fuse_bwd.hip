@@ -17,10 +17,7 @@
 // Traffic, V = 4 B D H W, P = 4 B H W bytes: reads V (1 + number of gradients present) + 2 P, writes V.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <cstdio>
-
-#include "../../include/pdepth.h"
+#include "capi_util.hpp"
 #include "dpv_fuse_math.hpp"
 #include "kernels.hpp"
 
@@ -227,15 +224,7 @@ hipError_t launch_dpv_fuse_backward(const float* logp, const float* dmaps, const
 
 // ---- C ABI (include/pdepth.h).  The entry lives here, beside its kernels, like those of loss.hip and metrics.hip: capi.o does
 // not refer to this object, so a library linked from a subset of the objects (tests/test_sweep_prefetch.py) still links. ----
-namespace {
-
-int fail(int code, const char* what) {
-    char msg[256];
-    snprintf(msg, sizeof(msg), "pdepth_dpv_fuse_backward_f32: %s", what);
-    return pdepth::api_error(code, msg);
-}
-
-}  // namespace
+using namespace pdepth::capi;
 
 extern "C" {
 
@@ -243,16 +232,16 @@ extern "C" {
 int pdepth_dpv_fuse_backward_f32(const float* logp, const float* dmaps, const float* masks, const float* d_candi,
                                  const float* g_fused, const float* g_logfused, int32_t B, int32_t D, int32_t H, int32_t W,
                                  float var, float eps, float* g_logp, void* stream) {
-    if (!logp || !dmaps || !masks || !d_candi || !g_logp) return fail(PDEPTH_E_ARG, "null pointer");
-    if (!g_fused && !g_logfused) return fail(PDEPTH_E_ARG, "no incoming gradient");
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "non-positive dimension");
-    if ((long long)H * W > (1ll << 30) || B > 65535) return fail(PDEPTH_E_ARG, "H*W must be at most 2^30 and B at most 65535");
-    if (!(var > 0.0f)) return fail(PDEPTH_E_ARG, "var must be positive");
+    const char* who = "pdepth_dpv_fuse_backward_f32";
+    if (!logp || !dmaps || !masks || !d_candi || !g_logp) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
+    if (!g_fused && !g_logfused) return fail(PDEPTH_E_ARG, "%s: no incoming gradient", who);
+    if (int rc = check_dims(who, B, D, H, W)) return rc;
+    if (int rc = check_launch_limits(who, B, H, W)) return rc;
+    if (!(var > 0.0f)) return fail(PDEPTH_E_ARG, "%s: var must be positive", who);
     if ((const float*)g_logp == logp || (const float*)g_logp == g_fused || (const float*)g_logp == g_logfused)
-        return fail(PDEPTH_E_ARG, "g_logp may not alias an input");
-    const hipError_t e = pdepth::launch_dpv_fuse_backward(logp, dmaps, masks, d_candi, g_fused, g_logfused, B, D, H, W, var, eps,
-                                                          g_logp, (hipStream_t)stream);
-    return e == hipSuccess ? PDEPTH_OK : fail(PDEPTH_E_LAUNCH, hipGetErrorString(e));
+        return fail(PDEPTH_E_ARG, "%s: g_logp may not alias an input", who);
+    return launched(pdepth::launch_dpv_fuse_backward(logp, dmaps, masks, d_candi, g_fused, g_logfused, B, D, H, W, var, eps, g_logp,
+                                                     (hipStream_t)stream), who);
 }
 
 }  // extern "C"

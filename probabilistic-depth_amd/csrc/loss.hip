@@ -16,45 +16,20 @@
 // (+ 4 HW D for the label tensor, + 4 HW D for logp when a depth gradient comes in).  The reference's composition reads or
 // writes [D,H,W] ten times forward.
 //
-// Wave layout of dpv.hip: lane = (plane group g = lane >> 4, pixel quad q = lane & 15), 16-byte non-temporal loads, planes
-// k = g + 4 i, partial sums combined with xor-shuffles over lanes l, l^16, l^32, l^48.  The expectation is summed exactly like
-// dpv_expect_vec4_kernel / dpv_expect_kernel (same products, same order): bit-equal depth maps.  The loads are issued
-// CH planes at a time (the volume and the label: 2 CH 16-byte loads in flight per lane).
+// The vec4 kernels use the wave layout of dpv_lanes.hpp and its expectation (expect_add: the bits of pdepth_dpv_expect_f32).
+// The loads are issued CH planes at a time (the volume and the label: 2 CH 16-byte loads in flight per lane).
 //
 // Pixel reduction: every workgroup (256 pixels) writes one partial sum and one count into the workspace, a second launch
-// of one workgroup per item adds them in a fixed order.  No atomics: two calls give the same bits.
+// of one workgroup per item adds them in a fixed order (wg_sum_put / wg_sum_get).  No atomics: two calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
-#include "../../include/pdepth.h"
+#include "capi_util.hpp"
+#include "dpv_lanes.hpp"
 #include "kernels.hpp"
 
 namespace pdepth {
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 ld_nt(const float* p) {
-    const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void st_nt(float* p, float4 v) {
-    __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f*>(p));
-}
-__device__ __forceinline__ float4 xor4(float4 v, int m) {
-    return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-__device__ __forceinline__ float4 group_sum(float4 v) {   // over the 4 plane groups of a wave
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = xor4(v, s);
-        v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-    }
-    return v;
-}
 
 struct Gauss {   // gaussian_torch (utils/img_utils.py:24-25) with sig = sqrt(variance)
     float den;   // 2 sig^pow
@@ -82,20 +57,16 @@ struct CeArgs {
 
 constexpr int CH = 8;   // planes of a lane in flight together
 
-// sum and count of a workgroup -> its slot of the workspace (fixed order: lanes by xor-shuffles, then the 4 waves)
+// sum and count of a workgroup -> its slot of the workspace
 __device__ __forceinline__ void block_partial(float w, int c, const CeArgs& a, int b) {
     __shared__ float sw[4];
     __shared__ int sc[4];
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        w = w + __shfl_xor(w, sh);
-        c = c + __shfl_xor(c, sh);
-    }
-    if ((threadIdx.x & 63) == 0) { sw[threadIdx.x >> 6] = w; sc[threadIdx.x >> 6] = c; }
+    wg_sum_put(w, sw);
+    wg_sum_put(c, sc);
     __syncthreads();
     if (threadIdx.x == 0) {
-        a.part_sum[(size_t)b * a.nblk + blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
-        a.part_cnt[(size_t)b * a.nblk + blockIdx.x] = (sc[0] + sc[1]) + (sc[2] + sc[3]);
+        a.part_sum[(size_t)b * a.nblk + blockIdx.x] = wg_sum_get(sw);
+        a.part_cnt[(size_t)b * a.nblk + blockIdx.x] = wg_sum_get(sc);
     }
 }
 
@@ -107,40 +78,26 @@ __device__ __forceinline__ void weigh(float ce, float m, float& w, int& c) {
 
 template <bool FROM_DEPTH, int RPL>
 __global__ __launch_bounds__(256) void soft_ce_vec4_kernel(CeArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int g = lane >> 4;
-    const int quads = a.HW >> 2;
-    const int q = wave * 16 + (lane & 15);
-    const bool live = q < quads;
-    const int b = blockIdx.y;
     const int D = a.D, HW = a.HW;
-    const size_t off = (size_t)b * D * HW + (size_t)(live ? q : 0) * 4;
-    const size_t poff = (size_t)b * HW + (size_t)(live ? q : 0) * 4;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const QuadLane L = quad_lane(D, HW);
+    const int g = L.g, b = L.b;
+    const bool live = L.live;
+    const float4 zero = splat4(0.f);
     float4 z = zero;
-    if (FROM_DEPTH) z = *reinterpret_cast<const float4*>(a.depth_gt + poff);
+    if (FROM_DEPTH) z = load_quad(a.depth_gt, L, 0.f);
     const bool want_depth = a.depth != nullptr;
     float4 e = zero, num = zero, S = zero, slp = zero;
 #pragma unroll
     for (int c0 = 0; c0 < RPL; c0 += CH) {
         float4 v[CH], l[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int k = g + 4 * (c0 + u);
-            const bool ok = k < D && live;
-            v[u] = ok ? ld_nt(a.logp + off + (size_t)k * HW) : zero;
-            if (!FROM_DEPTH) l[u] = ok ? ld_nt(a.label + off + (size_t)k * HW) : zero;
-        }
+        load_planes(v, a.logp, L, c0, D, HW, 0.f);
+        if (!FROM_DEPTH) load_planes(l, a.label, L, c0, D, HW, 0.f);
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
             const int k = g + 4 * (c0 + u);
             if (k < D) {
                 const float dk = a.dc[k];
-                if (want_depth) {   // (the products and the order of dpv_expect_vec4_kernel)
-                    e.x += dk * expf(v[u].x); e.y += dk * expf(v[u].y);
-                    e.z += dk * expf(v[u].z); e.w += dk * expf(v[u].w);
-                }
+                if (want_depth) expect_add<true>(e, dk, v[u]);
                 if (FROM_DEPTH) {
                     const float4 w = make_float4(a.gs(dk, z.x), a.gs(dk, z.y), a.gs(dk, z.z), a.gs(dk, z.w));
                     S.x += w.x; S.y += w.y; S.z += w.z; S.w += w.w;
@@ -164,12 +121,12 @@ __global__ __launch_bounds__(256) void soft_ce_vec4_kernel(CeArgs a) {
     }
     if (want_depth) {
         e = group_sum(e);
-        if (live && g == 0) *reinterpret_cast<float4*>(a.depth + poff) = e;
+        if (live && g == 0) *reinterpret_cast<float4*>(a.depth + L.poff) = e;
     }
     float w = 0.0f;
     int cnt = 0;
     if (live && g == 0) {
-        const float4 m = a.mask ? *reinterpret_cast<const float4*>(a.mask + poff) : make_float4(1.f, 1.f, 1.f, 1.f);
+        const float4 m = a.mask ? *reinterpret_cast<const float4*>(a.mask + L.poff) : splat4(1.f);
         float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
         weigh(ce.x, m.x, w0, cnt); weigh(ce.y, m.y, w1, cnt); weigh(ce.z, m.z, w2, cnt); weigh(ce.w, m.w, w3, cnt);
         w = (w0 + w1) + (w2 + w3);
@@ -225,16 +182,12 @@ __global__ __launch_bounds__(256) void soft_ce_final_kernel(const float* __restr
         s += (double)part_sum[(size_t)b * nblk + i];
         c += part_cnt[(size_t)b * nblk + i];
     }
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) {
-        s = s + __shfl_xor(s, sh);
-        c = c + __shfl_xor(c, sh);
-    }
-    if ((threadIdx.x & 63) == 0) { ss[threadIdx.x >> 6] = s; sc[threadIdx.x >> 6] = c; }
+    wg_sum_put(s, ss);
+    wg_sum_put(c, sc);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double tot = (ss[0] + ss[1]) + (ss[2] + ss[3]);
-        const float n = has_mask ? (float)((sc[0] + sc[1]) + (sc[2] + sc[3])) : (float)HW;
+        const double tot = wg_sum_get(ss);
+        const float n = has_mask ? (float)wg_sum_get(sc) : (float)HW;
         count[b] = n;
         loss[b] = n > 0.0f ? (float)tot / n : 0.0f;
     }
@@ -261,26 +214,20 @@ __device__ __forceinline__ float pixel_coef(float gl, float n, float m) {
 
 template <bool FROM_DEPTH, int RPL>
 __global__ __launch_bounds__(256) void soft_ce_bwd_vec4_kernel(CeBwdArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int g = lane >> 4;
-    const int quads = a.HW >> 2;
-    const int q = wave * 16 + (lane & 15);
-    const bool live = q < quads;
-    const int b = blockIdx.y;
     const int D = a.D, HW = a.HW;
-    const size_t off = (size_t)b * D * HW + (size_t)(live ? q : 0) * 4;
-    const size_t poff = (size_t)b * HW + (size_t)(live ? q : 0) * 4;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const QuadLane L = quad_lane(D, HW);
+    const int g = L.g, b = L.b;
+    const bool live = L.live;
+    const float4 zero = splat4(0.f);
     const float gl = a.g_loss ? a.g_loss[b] : 0.0f;
     const float n = a.count[b];
-    const float4 m = a.mask ? *reinterpret_cast<const float4*>(a.mask + poff) : make_float4(1.f, 1.f, 1.f, 1.f);
+    const float4 m = a.mask ? load_quad(a.mask, L, 1.f) : splat4(1.f);
     const float4 c = make_float4(pixel_coef(gl, n, m.x), pixel_coef(gl, n, m.y), pixel_coef(gl, n, m.z), pixel_coef(gl, n, m.w));
     const bool have_gd = a.g_depth != nullptr;
-    const float4 gd = have_gd ? *reinterpret_cast<const float4*>(a.g_depth + poff) : zero;
+    const float4 gd = have_gd ? load_quad(a.g_depth, L, 0.f) : zero;
     float4 z = zero, S = zero;
     if (FROM_DEPTH) {
-        z = *reinterpret_cast<const float4*>(a.depth_gt + poff);
+        z = load_quad(a.depth_gt, L, 0.f);
 #pragma unroll
         for (int i = 0; i < RPL; ++i) {
             const int k = g + 4 * i;
@@ -294,13 +241,8 @@ __global__ __launch_bounds__(256) void soft_ce_bwd_vec4_kernel(CeBwdArgs a) {
 #pragma unroll
     for (int c0 = 0; c0 < RPL; c0 += CH) {
         float4 v[CH], l[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int k = g + 4 * (c0 + u);
-            const bool ok = k < D && live;
-            v[u] = (ok && have_gd) ? ld_nt(a.logp + off + (size_t)k * HW) : zero;
-            if (!FROM_DEPTH) l[u] = ok ? ld_nt(a.label + off + (size_t)k * HW) : zero;
-        }
+        load_planes(v, a.logp, L, c0, D, HW, 0.f, have_gd);
+        if (!FROM_DEPTH) load_planes(l, a.label, L, c0, D, HW, 0.f);
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
             const int k = g + 4 * (c0 + u);
@@ -319,7 +261,7 @@ __global__ __launch_bounds__(256) void soft_ce_bwd_vec4_kernel(CeBwdArgs a) {
                     o.x += (gd.x * dk) * expf(v[u].x); o.y += (gd.y * dk) * expf(v[u].y);
                     o.z += (gd.z * dk) * expf(v[u].z); o.w += (gd.w * dk) * expf(v[u].w);
                 }
-                st_nt(a.g_logp + off + (size_t)k * HW, o);
+                store_nt(a.g_logp + L.off + (size_t)k * HW, o);
             }
         }
     }
@@ -349,8 +291,6 @@ __global__ __launch_bounds__(256) void soft_ce_bwd_scalar_kernel(CeBwdArgs a) {
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 Gauss make_gauss(float variance, float pw) {
     Gauss gs;
     const float sig = sqrtf(variance);
@@ -359,8 +299,6 @@ Gauss make_gauss(float variance, float pw) {
     gs.den = 2.0f * (gs.square ? sig * sig : powf(sig, pw));
     return gs;
 }
-
-int n_blocks(int H, int W) { return (int)(((long long)H * W + 255) / 256); }
 
 }  // namespace
 
@@ -382,17 +320,17 @@ hipError_t launch_dpv_soft_ce(const float* logp, const float* d_candi, const flo
     const bool vec = (HW % 4 == 0) && D <= 128 && aligned16(logp) && (!label || aligned16(label)) &&
                      (!depth_gt || aligned16(depth_gt)) && (!mask || aligned16(mask)) && (!depth || aligned16(depth));
     const dim3 grid(nblk, B);
-#define PDEPTH_CE(RPL)                                                                                    \
-    if (depth_gt) hipLaunchKernelGGL((soft_ce_vec4_kernel<true, RPL>), grid, dim3(256), 0, stream, a);   \
-    else hipLaunchKernelGGL((soft_ce_vec4_kernel<false, RPL>), grid, dim3(256), 0, stream, a);
     if (vec) {
-        if (D <= 32) { PDEPTH_CE(8) } else if (D <= 64) { PDEPTH_CE(16) } else { PDEPTH_CE(32) }
+        for_planes_per_lane(D, [&](auto rpl) {
+            constexpr int RPL = decltype(rpl)::value;
+            if (depth_gt) hipLaunchKernelGGL((soft_ce_vec4_kernel<true, RPL>), grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((soft_ce_vec4_kernel<false, RPL>), grid, dim3(256), 0, stream, a);
+        });
     } else if (depth_gt) {
         hipLaunchKernelGGL(soft_ce_scalar_kernel<true>, grid, dim3(256), 0, stream, a);
     } else {
         hipLaunchKernelGGL(soft_ce_scalar_kernel<false>, grid, dim3(256), 0, stream, a);
     }
-#undef PDEPTH_CE
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(soft_ce_final_kernel, dim3(B), dim3(256), 0, stream, a.part_sum, a.part_cnt, nblk, HW, mask ? 1 : 0, loss,
@@ -413,17 +351,17 @@ hipError_t launch_dpv_soft_ce_backward(const float* logp, const float* d_candi, 
                      (!depth_gt || aligned16(depth_gt)) && (!mask || aligned16(mask)) && (!g_depth || aligned16(g_depth)) &&
                      aligned16(g_logp);
     const dim3 grid(n_blocks(H, W), B);
-#define PDEPTH_CE_BWD(RPL)                                                                                   \
-    if (depth_gt) hipLaunchKernelGGL((soft_ce_bwd_vec4_kernel<true, RPL>), grid, dim3(256), 0, stream, a);  \
-    else hipLaunchKernelGGL((soft_ce_bwd_vec4_kernel<false, RPL>), grid, dim3(256), 0, stream, a);
     if (vec) {
-        if (D <= 32) { PDEPTH_CE_BWD(8) } else if (D <= 64) { PDEPTH_CE_BWD(16) } else { PDEPTH_CE_BWD(32) }
+        for_planes_per_lane(D, [&](auto rpl) {
+            constexpr int RPL = decltype(rpl)::value;
+            if (depth_gt) hipLaunchKernelGGL((soft_ce_bwd_vec4_kernel<true, RPL>), grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((soft_ce_bwd_vec4_kernel<false, RPL>), grid, dim3(256), 0, stream, a);
+        });
     } else if (depth_gt) {
         hipLaunchKernelGGL(soft_ce_bwd_scalar_kernel<true>, grid, dim3(256), 0, stream, a);
     } else {
         hipLaunchKernelGGL(soft_ce_bwd_scalar_kernel<false>, grid, dim3(256), 0, stream, a);
     }
-#undef PDEPTH_CE_BWD
     return hipGetLastError();
 }
 
@@ -433,26 +371,14 @@ hipError_t launch_dpv_soft_ce_backward(const float* logp, const float* d_candi, 
 // library linked from a subset of the objects (tests/test_sweep_prefetch.py) still links. ------------------------------------
 namespace {
 
-int fail(int code, const char* fmt, ...) {
-    char msg[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, sizeof(msg), fmt, ap);
-    va_end(ap);
-    return pdepth::api_error(code, msg);
-}
-
-int launched(hipError_t e, const char* who) {
-    if (e != hipSuccess) return fail(PDEPTH_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
-    return PDEPTH_OK;
-}
+using namespace pdepth::capi;
 
 // what the two cross-entropy entries check alike: the volume, the sizes, the label source
 int check_soft_ce(const char* who, const float* logp, const float* d_candi, const float* label, const float* depth_gt, float variance,
                   float pw, int32_t B, int32_t D, int32_t H, int32_t W) {
     if (!logp || !d_candi) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
-    if ((long long)H * W > (1ll << 30) || B > 65535) return fail(PDEPTH_E_ARG, "%s: H*W too large or B above 65535", who);
+    if (int rc = check_dims(who, B, D, H, W)) return rc;
+    if (int rc = check_launch_limits(who, B, H, W)) return rc;
     if ((label != nullptr) == (depth_gt != nullptr))
         return fail(PDEPTH_E_ARG, "%s: exactly one label source (label or depth_gt) must be given", who);
     if (depth_gt && !(variance > 0.0f)) return fail(PDEPTH_E_ARG, "%s: variance must be positive", who);
@@ -475,11 +401,7 @@ int pdepth_dpv_soft_ce_f32(const float* logp, const float* d_candi, const float*
     const char* who = "pdepth_dpv_soft_ce_f32";
     if (int rc = check_soft_ce(who, logp, d_candi, label, depth_gt, variance, pow, B, D, H, W)) return rc;
     if (!loss || !count) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
-    const size_t need = pdepth::dpv_soft_ce_workspace_bytes(B, H, W);
-    if (!workspace || workspace_bytes < need)
-        return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu)", who, need, workspace_bytes);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-        return fail(PDEPTH_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+    if (int rc = check_workspace(who, workspace, workspace_bytes, pdepth::dpv_soft_ce_workspace_bytes(B, H, W))) return rc;
     return launched(pdepth::launch_dpv_soft_ce(logp, d_candi, label, depth_gt, variance, pow, mask, B, D, H, W, loss, count, depth,
                                                workspace, (hipStream_t)stream), who);
 }

@@ -16,48 +16,27 @@
 //
 // Two forms of the input.  Depth map form: pred [B,H,W], one pixel per thread.  Volume form: logp [B,D,H,W] + d_candi, the
 // expectation sum_d d_d exp(logp_d) formed in registers from one read of the volume (4 HW D bytes per item, + 4 HW for the
-// truth [+ 4 HW mask] [+ 4 HW for the depth map, written from the same pass]), summed exactly like dpv_expect_vec4_kernel /
-// dpv_expect_kernel of dpv.hip (same products, same order): the bits of pdepth_dpv_expect_f32(bv_log = 1).
+// truth [+ 4 HW mask] [+ 4 HW for the depth map, written from the same pass]), with the expectation of dpv_lanes.hpp
+// (expect_planes): the bits of pdepth_dpv_expect_f32(bv_log = 1).
 //
-// Wave layout of dpv.hip / loss.hip in the volume kernel: lane = (plane group g = lane >> 4, pixel quad q = lane & 15), 16-byte
-// non-temporal loads, planes k = g + 4 i, partial sums combined with xor-shuffles over lanes l, l^16, l^32, l^48.  After that
-// every plane group holds the four depths of its quad: lane (g, q) takes pixel 4 q + g of the wave's 64 for the error terms, so
-// each lane evaluates one pixel.  The other two kernels give lane (g, q) the same pixel: the three feed the reduction alike, and
-// the metrics of the volume form equal those of the depth map form on the map it writes bit for bit.
+// The volume kernel uses the wave layout of dpv_lanes.hpp.  After the sum over the plane groups every group holds the four
+// depths of its quad: lane (g, q) takes pixel 4 q + g of the wave's 64 for the error terms, so each lane evaluates one pixel.
+// The other two kernels give lane (g, q) the same pixel (thread_pixel): the three feed the reduction alike, and the metrics of
+// the volume form equal those of the depth map form on the map it writes bit for bit.
 //
 // Pixel reduction: the per-pixel terms are float (as in the reference), their sums double.  Every workgroup (256 pixels) writes
 // one record -- the nine sums (the reference's eight error accumulators and its logSum) and the count -- into the workspace; a
-// second launch of one workgroup per item adds the records in a fixed order and finishes the roots.  No atomics: two calls
-// give the same bits.
+// second launch of one workgroup per item adds the records in a fixed order (that of wg_sum_put / wg_sum_get) and finishes the roots.
+// No atomics: two calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
-#include "../../include/pdepth.h"
+#include "capi_util.hpp"
+#include "dpv_lanes.hpp"
 #include "kernels.hpp"
 
 namespace pdepth {
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 ld_nt(const float* p) {
-    const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ float4 xor4(float4 v, int m) {
-    return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-__device__ __forceinline__ float4 group_sum(float4 v) {   // over the 4 plane groups of a wave
-#pragma unroll
-    for (int s = 16; s <= 32; s <<= 1) {
-        const float4 o = xor4(v, s);
-        v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-    }
-    return v;
-}
 
 constexpr int NSUM = 9;          // sums of a record: e, e^2, ei, ei^2, el, el^2, s, e/p, e^2/p^2
 constexpr int REC = NSUM + 1;    // + the count (a double: exact)
@@ -73,12 +52,6 @@ struct MetArgs {
     float* depth;         // [B,H,W] or nullptr (volume form)
     double* part;         // [B,nblk,REC]
 };
-
-// pixel of this thread within its item: lane (g, q) of wave w takes pixel 64 w + 4 q + g (see the header comment)
-__device__ __forceinline__ int thread_pixel() {
-    const int lane = threadIdx.x & 63;
-    return blockIdx.x * 256 + (threadIdx.x >> 6) * 64 + (lane & 15) * 4 + (lane >> 4);
-}
 
 // the terms of one pixel (evaluate_depth.h:54-88 with D_gt = the masked prediction, D_ipol = the truth), zeros where invalid
 __device__ __forceinline__ void pixel_terms(float pr, int pix, int b, bool live, const MetArgs& a, double (&acc)[REC]) {
@@ -100,7 +73,9 @@ __device__ __forceinline__ void pixel_terms(float pr, int pix, int b, bool live,
     }
 }
 
-// the record of a workgroup -> its slot of the workspace (fixed order: lanes by xor-shuffles, then the 4 waves)
+// the record of a workgroup -> its slot of the workspace, in the order of wg_sum_put / wg_sum_get (dpv_lanes.hpp: lanes by
+// xor-shuffles 32 ... 1, then (w0 + w1) + (w2 + w3)); written out for the ten sums at once: through the helper, one sum at a
+// time, the depth map kernel ran 5 - 7 % slower (profiles/r11_dpv_lanes/README.md)
 __device__ __forceinline__ void block_record(double (&acc)[REC], const MetArgs& a, int b) {
     __shared__ double sw[4][REC];
 #pragma unroll
@@ -123,38 +98,20 @@ __device__ __forceinline__ void block_record(double (&acc)[REC], const MetArgs& 
 template <int RPL>
 __global__ __launch_bounds__(256) void depth_metrics_vec4_kernel(MetArgs a) {
     constexpr int CH = RPL < 16 ? RPL : 16;
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int g = lane >> 4;
-    const int quads = a.HW >> 2;
-    const int q = wave * 16 + (lane & 15);
-    const bool live = q < quads;
-    const int b = blockIdx.y;
     const int D = a.D, HW = a.HW;
-    const size_t off = (size_t)b * D * HW + (size_t)(live ? q : 0) * 4;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 e = zero;
+    const QuadLane L = quad_lane(D, HW);
+    const int g = L.g, b = L.b;
+    const bool live = L.live;
+    float4 e = splat4(0.f);
 #pragma unroll
     for (int c0 = 0; c0 < RPL; c0 += CH) {
         float4 v[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int k = g + 4 * (c0 + u);
-            v[u] = (k < D && live) ? ld_nt(a.logp + off + (size_t)k * HW) : zero;
-        }
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int k = g + 4 * (c0 + u);
-            if (k < D) {   // (the products and the order of dpv_expect_vec4_kernel)
-                const float dk = a.dc[k];
-                e.x += dk * expf(v[u].x); e.y += dk * expf(v[u].y);
-                e.z += dk * expf(v[u].z); e.w += dk * expf(v[u].w);
-            }
-        }
+        load_planes(v, a.logp, L, c0, D, HW, 0.f);
+        expect_planes<true>(e, v, a.dc, g, c0, D);
     }
     e = group_sum(e);
     const float pr = g == 0 ? e.x : g == 1 ? e.y : g == 2 ? e.z : e.w;   // pixel 4 q + g
-    const int pix = q * 4 + g;                                            // (= thread_pixel())
+    const int pix = L.q * 4 + g;                                          // (= thread_pixel())
     if (a.depth && live) a.depth[(size_t)b * HW + pix] = pr;
     double acc[REC];
     pixel_terms(pr, pix, b, live, a, acc);
@@ -202,7 +159,7 @@ __global__ __launch_bounds__(256) void depth_metrics_final_kernel(const double* 
         for (int j = 0; j < REC; ++j) acc[j] += part[((size_t)b * nblk + i) * REC + j];
     }
 #pragma unroll
-    for (int j = 0; j < REC; ++j) {
+    for (int j = 0; j < REC; ++j) {   // (the order of block_record)
 #pragma unroll
         for (int sh = 32; sh >= 1; sh >>= 1) acc[j] = acc[j] + __shfl_xor(acc[j], sh);
     }
@@ -236,10 +193,6 @@ __global__ __launch_bounds__(256) void depth_metrics_final_kernel(const double* 
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-int n_blocks(int H, int W) { return (int)(((long long)H * W + 255) / 256); }
-
 }  // namespace
 
 size_t depth_metrics_workspace_bytes(int B, int H, int W) {
@@ -259,9 +212,9 @@ hipError_t launch_depth_metrics(const float* logp, const float* pred, const floa
     if (pred) {
         hipLaunchKernelGGL(depth_metrics_map_kernel, grid, dim3(256), 0, stream, a);
     } else if ((HW % 4 == 0) && D <= 128 && aligned16(logp) && (!depth || aligned16(depth))) {   // (as launch_dpv_expect decides)
-        if (D <= 32) hipLaunchKernelGGL(depth_metrics_vec4_kernel<8>, grid, dim3(256), 0, stream, a);
-        else if (D <= 64) hipLaunchKernelGGL(depth_metrics_vec4_kernel<16>, grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(depth_metrics_vec4_kernel<32>, grid, dim3(256), 0, stream, a);
+        for_planes_per_lane(D, [&](auto rpl) {
+            hipLaunchKernelGGL(depth_metrics_vec4_kernel<decltype(rpl)::value>, grid, dim3(256), 0, stream, a);
+        });
     } else {
         hipLaunchKernelGGL(depth_metrics_scalar_kernel, grid, dim3(256), 0, stream, a);
     }
@@ -275,18 +228,7 @@ hipError_t launch_depth_metrics(const float* logp, const float* pred, const floa
 
 // ---- C ABI (include/pdepth.h).  The entries live here, beside their kernels: capi.o does not refer to this object, so a
 // library linked from a subset of the objects (tests/test_sweep_prefetch.py) still links. ------------------------------------
-namespace {
-
-int fail(int code, const char* fmt, ...) {
-    char msg[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, sizeof(msg), fmt, ap);
-    va_end(ap);
-    return pdepth::api_error(code, msg);
-}
-
-}  // namespace
+using namespace pdepth::capi;
 
 extern "C" {
 
@@ -302,19 +244,13 @@ int pdepth_depth_metrics_f32(const float* logp, const float* pred, const float* 
     if ((logp != nullptr) == (pred != nullptr))
         return fail(PDEPTH_E_ARG, "%s: exactly one prediction (logp or pred) must be given", who);
     if (logp && !d_candi) return fail(PDEPTH_E_ARG, "%s: null pointer (d_candi): the volume form needs the depth candidates", who);
-    if (B <= 0 || H <= 0 || W <= 0 || (logp && D <= 0)) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
-    if ((long long)H * W > (1ll << 30) || B > 65535) return fail(PDEPTH_E_ARG, "%s: H*W too large or B above 65535", who);
+    if (int rc = check_dims(who, B, logp ? D : 1, H, W)) return rc;   // (D belongs to the volume form)
+    if (int rc = check_launch_limits(who, B, H, W)) return rc;
     if (!metrics || !count) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
     if (pred && depth) return fail(PDEPTH_E_ARG, "%s: the depth output belongs to the volume form", who);
-    const size_t need = pdepth::depth_metrics_workspace_bytes(B, H, W);
-    if (!workspace || workspace_bytes < need)
-        return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu)", who, need, workspace_bytes);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-        return fail(PDEPTH_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
-    const hipError_t e = pdepth::launch_depth_metrics(logp, pred, d_candi, truth, mask, clamp_max, B, D, H, W, metrics, count, depth,
-                                                      workspace, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(PDEPTH_E_LAUNCH, "%s: %s", who, hipGetErrorString(e));
-    return PDEPTH_OK;
+    if (int rc = check_workspace(who, workspace, workspace_bytes, pdepth::depth_metrics_workspace_bytes(B, H, W))) return rc;
+    return launched(pdepth::launch_depth_metrics(logp, pred, d_candi, truth, mask, clamp_max, B, D, H, W, metrics, count, depth,
+                                                 workspace, (hipStream_t)stream), who);
 }
 
 }  // extern "C"
