@@ -7,6 +7,7 @@ All tensors are fp32 device tensors; nothing here runs on the CPU.
 from __future__ import annotations
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native
 
@@ -246,7 +247,7 @@ def dpv_fuse(logp, dmaps, masks, d_candi, var=0.3, eps=None, want_fused=True, wa
 # csrc/dpv_fuse_bwd.hip.
 # Differentiable: the feature maps (ref, NCHW src), logits, addend, the DPV of dpv_expect, the log-DPV of dpv_fuse.  Not differentiable: the geometry
 # (K, R, t, rays, cxcy, d_candi -- the reference's training takes them from the data loader), which is refused when it
-# requires grad.
+# requires grad.  Every backward is once_differentiable: a second-order gradient through a HIP backward raises, it is not a constant.
 
 def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in tensors)
@@ -287,6 +288,7 @@ class _SweepFn(torch.autograd.Function):
         return cost, (logp if want_logp else None), depth
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_cost, g_logp, g_depth):
         ref, src, K, R, t, rays, cxcy, dc, logp = ctx.saved_tensors
         sigma, metric, blas_mode = ctx.cfg
@@ -323,6 +325,7 @@ class _DpvReduceFn(torch.autograd.Function):
         return (logp if want_logp else None, out.get("prob"), out.get("depth"), out.get("var"), out.get("quarter"))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_logp, g_prob, g_depth, g_var, g_quarter):
         logp, dc = ctx.saved_tensors
         g = None
@@ -343,6 +346,7 @@ class _DpvFuseFn(torch.autograd.Function):
         return _native.dpv_fuse(logp, dmaps, masks, dc, var, eps, want_fused, want_log)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_fused, g_logfused):
         if g_fused is None and g_logfused is None:
             return (None,) * 8
@@ -361,6 +365,7 @@ class _DpvExpectFn(torch.autograd.Function):
         return _native.dpv_expect(dpv, dc, bv_log)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_depth):
         dpv, dc = ctx.saved_tensors
         return _native.dpv_expect_backward(dpv, dc, ctx.bv_log, g_depth), None, None
@@ -378,6 +383,7 @@ class _DpvSoftCeFn(torch.autograd.Function):
         return loss, depth
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g_loss, g_depth):
         logp, dc, count, label, depth_gt, mask = ctx.saved_tensors
         g = None
@@ -396,6 +402,7 @@ class _CorrelationFn(torch.autograd.Function):
         return _native.correlation_forward(x1, x2, *ctx.cfg)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_out):
         x1, x2 = ctx.saved_tensors
         g1, g2 = _native.correlation_backward(x1, x2, grad_out, *ctx.cfg, want1=ctx.needs_input_grad[0],
