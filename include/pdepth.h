@@ -58,7 +58,7 @@ extern "C" {
                                 *    backward-compatible additions within 6: pdepth_sweep_backward_f32, pdepth_dpv_reduce_backward_f32,
                                 *    pdepth_dpv_expect_backward_f32; pdepth_dpv_soft_ce_workspace_bytes, pdepth_dpv_soft_ce_f32,
                                 *    pdepth_dpv_soft_ce_backward_f32; pdepth_depth_metrics_workspace_bytes, pdepth_depth_metrics_f32;
-                                *    pdepth_dpv_fuse_backward_f32 */
+                                *    pdepth_dpv_fuse_backward_f32; pdepth_lidar_depth_workspace_bytes, pdepth_lidar_depth_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -496,6 +496,41 @@ size_t pdepth_depth_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int pdepth_depth_metrics_f32(const float *logp, const float *pred, const float *d_candi, const float *truth, const float *mask,
                              float clamp_max, int32_t B, int32_t D, int32_t H, int32_t W, float *metrics, float *count,
                              float *depth, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Ground truth from LiDAR: a batch of point clouds -> z-buffered, occlusion-filtered depth maps and masks at full and quarter
+ * resolution (generate_depth, external/utils_lib/python/utils_lib.cpp:86-160 with upsample = 0, followed by what the loader does
+ * with its result, kittiloader/kitti.py:683-729: util.minpool(large, 4, 1000) and the two masks).
+ *   points   [B,Nmax,point_dim] fp32, point_dim 4 = (x, y, z, w) (16-byte aligned) or 3 = (x, y, z) with w = 1;
+ *   counts   [B] int32 on the device: rows at or beyond counts[b] are ignored whatever they hold; 0 gives all-zero outputs;
+ *   M_velo2cam [4,4] (M_batched = 0) or [B,4,4];  intr [3,4] (intr_batched = 0) or [B,3,4], row-major fp32 (the reference's
+ *            binding casts the loader's float64 matrices to fp32 the same way).
+ * Per point, fp32, every product and sum rounded on its own, each chain left to right:
+ *     cam_r  = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3] w                    r = 0 .. 3
+ *     proj_r = ((I[r][0] cam_0 + I[r][1] cam_1) + I[r][2] cam_2) + I[r][3] cam_3      r = 0 .. 2
+ *     u_f = proj_0 / proj_2,  v_f = proj_1 / proj_2  (IEEE division);  u = (int)(u_f - 0.5),  v = (int)(v_f - 0.5)
+ *   kept iff cam_2 >= 0.1 and finite.  The 0.5 is subtracted in double as the reference does (exact) and the result truncated
+ *   toward zero: (-1, 1) is column 0, <= -1 and >= W are outside, likewise v.  A point whose position is not finite or beyond
+ *   the int range is skipped (the reference's conversion is undefined there).  The depth is cam_2, not proj_2.
+ * Z-buffer: per pixel the minimum cam_2 of the points that land in it (an unsigned atomic minimum on the bit pattern), 0 where
+ *   none lands: independent of the order of the points, bit-identical from call to call.
+ * Filter (filtering = f in 0 .. 4, filterdiff finite): dmap[v,u] is non-zero only for f <= v < H-f-1 and f <= u < W-f-1 (the
+ *   reference's bounds: the last f+1 rows and columns are zero); there it is the z-buffer's z unless another pixel of the
+ *   (2f+1)^2 window has zn != 0 and zn - z < -filterdiff (strict; the window reads the z-buffer, never the filtered map).
+ * mask = 1.0 where dmap >= 0.01 else 0.0; dmap is multiplied by it.  dmap_quarter [B,H/4,W/4] (a ragged remainder is dropped):
+ *   the minimum over 4x4 blocks of dmap with zeros lifted to pool_default (the loader: 1000; 0 = no lifting), a block whose
+ *   minimum equals pool_default is 0 -- so a depth >= pool_default beside an empty pixel disappears, as in the reference --;
+ *   mask_quarter and the product likewise.  dmap, mask [B,H,W] (16-byte aligned when W % 4 == 0), the quarter outputs may be
+ *   NULL when H < 4 or W < 4.
+ *   workspace: pdepth_lidar_depth_workspace_bytes(B, H, W) bytes (the z-buffer, 4 H W per item), 256-byte aligned; 0 for
+ *   non-positive sizes.  Three launches (clear the z-buffer, a thread per point, a workgroup per 32x32 pixels) on
+ *   `stream`: nothing is allocated, nothing waits for the host, the call can be captured in a graph.
+ */
+size_t pdepth_lidar_depth_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_lidar_depth_f32(const float *points, const int32_t *counts, const float *M_velo2cam, const float *intr, int32_t B,
+                           int32_t Nmax, int32_t point_dim, int32_t M_batched, int32_t intr_batched, int32_t H, int32_t W,
+                           int32_t filtering, float filterdiff, float pool_default, float *dmap, float *mask,
+                           float *dmap_quarter, float *mask_quarter, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -74,12 +74,15 @@ _SIGNATURES = {
     "pdepth_dpv_soft_ce_backward_f32": (c_int, [_P] * 4 + [_F, _F, _P, _P] + [_I] * 4 + [_P] * 4),
     "pdepth_depth_metrics_workspace_bytes": (_Z, [_I] * 3),
     "pdepth_depth_metrics_f32": (c_int, [_P] * 5 + [_F] + [_I] * 4 + [_P] * 4 + [_Z, _P]),
+    "pdepth_lidar_depth_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_lidar_depth_f32": (c_int, [_P] * 4 + [_I] * 8 + [_F, _F] + [_P] * 5 + [_Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, metrics and fusion-backward entries live in objects of their own: part of an entry's name -> the source file.  The
+# The loss, metrics, fusion-backward and LiDAR entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
-_SOURCE_OF_ENTRY = {"_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip"}
+_SOURCE_OF_ENTRY = {"_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
+                    "_lidar_depth_": "csrc/lidar_depth.hip"}
 _ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if any(part in n for part in _SOURCE_OF_ENTRY))
 
 
@@ -962,3 +965,45 @@ def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_ma
                                                      _stream(dev))
     _check(rc, lib)
     return metrics, count, depth
+
+
+# ---- ground truth from LiDAR (ops.lidar_depth) ----------------------------------------------------------------------------------
+def lidar_depth(points, counts, M_velo2cam, intr, height, width, filtering=2, filterdiff=1.0, pool_default=1000.0):
+    """points [B,Nmax,4|3], counts [B] int32, M_velo2cam [4,4] | [B,4,4], intr [3,4] | [B,3,4] -> (dmap [B,H,W], mask [B,H,W],
+    dmap_quarter [B,H//4,W//4], mask_quarter [B,H//4,W//4]): pdepth_lidar_depth_f32 on the current stream, no host
+    synchronisation."""
+    who = "lidar_depth"
+    lib = load()
+    _no_autograd(who, points, M_velo2cam, intr)
+    if points.dim() != 3 or points.shape[2] not in (3, 4):
+        raise RuntimeError(f"{who}: points must be [B,Nmax,4] or [B,Nmax,3], got {tuple(points.shape)}")
+    B, Nmax, dim = points.shape
+    _shape(counts, (B,), "counts", who)
+    if M_velo2cam.dim() not in (2, 3) or intr.dim() not in (2, 3):
+        raise RuntimeError(f"{who}: M_velo2cam must be [4,4] or [B,4,4] and intr [3,4] or [B,3,4]")
+    _shape(M_velo2cam, (4, 4) if M_velo2cam.dim() == 2 else (B, 4, 4), "M_velo2cam", who)
+    _shape(intr, (3, 4) if intr.dim() == 2 else (B, 3, 4), "intr", who)
+    H, W = int(height), int(width)
+    for nm, t in (("points", points), ("counts", counts), ("M_velo2cam", M_velo2cam), ("intr", intr)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{nm}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+    if counts.dtype != torch.int32:
+        raise RuntimeError(f"counts: expected int32, got {counts.dtype}")
+    for nm, t in (("points", points), ("M_velo2cam", M_velo2cam), ("intr", intr)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{nm}: expected float32, got {t.dtype}")
+    points, counts, M_velo2cam, intr = (t.contiguous() for t in (points, counts, M_velo2cam, intr))
+    dev = points.device
+    ws_bytes = _entry(lib, "pdepth_lidar_depth_workspace_bytes")(B, H, W)
+    large = torch.empty((2, B, max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
+    small = torch.empty((2, B, max(H, 0) // 4, max(W, 0) // 4), dtype=torch.float32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_lidar_depth_f32")(_ptr(points) or None, counts.data_ptr(), M_velo2cam.data_ptr(), intr.data_ptr(),
+                                                   B, Nmax, dim, int(M_velo2cam.dim() == 3), int(intr.dim() == 3), H, W,
+                                                   int(filtering), float(filterdiff), float(pool_default),
+                                                   large[0].data_ptr() or None, large[1].data_ptr() or None,
+                                                   small[0].data_ptr() or None, small[1].data_ptr() or None,
+                                                   ws.data_ptr() or None, ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return large[0], large[1], small[0], small[1]

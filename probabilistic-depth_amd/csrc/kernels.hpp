@@ -118,6 +118,14 @@ hipError_t launch_depth_metrics(const float* logp, const float* pred, const floa
                                 float clamp_max, int B, int D, int H, int W, float* metrics, float* count, float* depth,
                                 void* workspace, hipStream_t stream);
 
+// lidar_depth.hip: LiDAR scans -> z-buffered, filtered depth maps and masks at full and quarter resolution.  points [B,Nmax,dim]
+// (dim 3: w = 1), counts [B], M [4,4] | [B,4,4], intr [3,4] | [B,3,4]; the workspace is the z-buffer
+size_t lidar_depth_workspace_bytes(int B, int H, int W);
+hipError_t launch_lidar_depth(const float* points, const int* counts, const float* M, const float* intr, int B, int Nmax,
+                              int point_dim, int M_batched, int intr_batched, int H, int W, int filtering, float filterdiff,
+                              float pool_default, float* dmap, float* mask, float* dmap_q, float* mask_q, void* workspace,
+                              hipStream_t stream);
+
 // sweep_bwd.hip: gradient of the cost volume with respect to the NCHW features (either output may be nullptr, not both;
 // grad_src [B,V,C,H,W] contiguous, zeroed by the launcher; grad_ref [B,C,H,W] contiguous)
 hipError_t launch_sweep_backward(const SweepArgs& a, const float* grad_cost, float* grad_ref, float* grad_src, hipStream_t stream);

@@ -135,6 +135,25 @@ def validate(model, frames, cfg=None, sync_debug="error"):
             "results": results, "results_refined": results_refined, "steps": steps}
 
 
+def _lidar_params(params):
+    """(filtering, filterdiff) of the reference's parameter dict / attribute dict; upsample != 0 is refused."""
+    get = params.get if hasattr(params, "get") else (lambda k, d=None: getattr(params, k, d))
+    if float(get("upsample", 0) or 0) != 0:
+        raise NotImplementedError("lidar: params['upsample'] != 0 selects the beam resampling upsample_velodyne "
+                                  "(external/utils_lib/python/utils_lib.cpp:20-84), which is not implemented")
+    filterdiff = get("filterdiff", None)
+    return int(get("filtering")), 1.0 if filterdiff is None else float(filterdiff)
+
+
+def targets_from_lidar(points, counts, M_velo2cam, intr, width, height, params=None):
+    """The ground-truth part of gt_input for a batch of LiDAR scans on the device (kittiloader/kitti.py:683-729): the dict of
+    ops.lidar_depth -- dmaps, dmap_imgsizes, masks, masks_imgsizes -- as validate_step and BaseLoss(labels_from_depth=True) read
+    them.  params: the loader's {"filtering", "upsample"[, "filterdiff"]}; None = {"filtering": 2, "upsample": 0}, what the loader
+    uses when cfg.lidar.enabled is false."""
+    filtering, filterdiff = _lidar_params({"filtering": 2, "upsample": 0} if params is None else params)
+    return ops.lidar_depth(points, counts, M_velo2cam, intr, width, height, filtering=filtering, filterdiff=filterdiff)
+
+
 def model_from_config(path, device, id=0):
     """get_model() for an experiment file in the reference's JSON schema (train.py:34-37 + models/get_model.py:4-13):
     returns (model on `device` in eval mode, cfg, the float64 depth candidates of default_trainer.py:38-39)."""

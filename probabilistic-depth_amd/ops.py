@@ -204,6 +204,29 @@ def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_ma
     return _native.depth_metrics(truth, pred=pred, logp=logp, d_candi=dc, mask=mask, clamp_max=clamp_max, want_depth=want_depth)
 
 
+def lidar_depth(points, counts, M_velo2cam, intr, width, height, filtering=2, filterdiff=1.0, pool=4, pool_default=1000.0):
+    """The ground truth of a batch from its LiDAR scans, on the device: generate_depth (external/utils_lib/python/utils_lib.cpp:
+    86-160, upsample = 0) for every item, then the loader's quarter-resolution map and masks (kittiloader/kitti.py:683-729), in
+    one call on the current stream without a host synchronisation.
+
+    points [B,Nmax,4] = (x, y, z, w) or [B,Nmax,3] (w = 1); counts [B] int32: rows at or beyond counts[b] are ignored, 0 gives
+    all-zero maps; M_velo2cam [4,4] | [B,4,4]; intr [3,4] | [3,3] | [B,3,4] | [B,3,3] (a 3x3 gets the zero column the loader
+    appends), all fp32 -- cast float64 calibration with .float(), as the reference's binding does.  A point is transformed and
+    projected in fp32, kept iff cam.z >= 0.1, lands in pixel ((int)(u_f - 0.5), (int)(v_f - 0.5)) (truncation toward zero), and
+    the pixel takes the minimum cam.z; the filter clears a pixel when another pixel of its (2 filtering + 1)^2 window is nearer by
+    more than filterdiff, and the last filtering + 1 rows and columns (include/pdepth.h has every detail).
+    Returns {"dmap_imgsizes" [B,H,W], "masks_imgsizes" [B,1,H,W], "dmaps" [B,H//4,W//4], "masks" [B,1,H//4,W//4]}: the keys
+    BaseLoss(labels_from_depth=True), harness.validate_step and nmode default_upsample read.  Not differentiable."""
+    if pool != 4:
+        raise NotImplementedError(f"lidar_depth: pool = {pool}: the kernel pools 4x4 blocks (the loader's resize_dmap = 0.25)")
+    _refuse_grad("lidar_depth", points=points, M_velo2cam=M_velo2cam, intr=intr)
+    if intr.shape[-1] == 3:
+        intr = torch.cat([intr, intr.new_zeros(intr.shape[:-1] + (1,))], dim=-1)
+    dmap, mask, dmap_q, mask_q = _native.lidar_depth(points, counts, M_velo2cam, intr, height, width, filtering, filterdiff,
+                                                     pool_default)
+    return {"dmap_imgsizes": dmap, "masks_imgsizes": mask.unsqueeze(1), "dmaps": dmap_q, "masks": mask_q.unsqueeze(1)}
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
