@@ -717,8 +717,16 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                         const int voffA = opaque_v(ntex + kq * PB);
                         // a block's texel operands in consumption order: (high c, low c) for c < NCHK, tail; NS register sets: NS
                         // blocks of the wave are in flight, every chunk refilled with the operands of the block after the next
-                        // right behind its last multiplication.  (One set -- round 5 -- left every block of a wave waiting a whole
-                        // memory latency for its operands: three to four latencies per pass on a forward motion.)
+                        // right behind its last multiplication: the NAC loads of a refill have a whole block's time to return, a
+                        // wave exposes about one memory latency per block.  (One set without refills under way -- round 5 -- left
+                        // every block of a wave waiting a whole memory latency for its operands.)
+                        // The compiler places the waits, and it counts right only where every path issues the same loads: with the
+                        // refills behind a uniform `if (more)` in ONE loop body it took, at every join, the count of the path that
+                        // issues nothing -- vmcnt(4), (3), (2), (1), (0) for the five chunks of <2,1>: the last two waited for
+                        // refills issued moments before, a second full latency per block, and never more than three loads of
+                        // the next block were in flight.  So the blocks that have a successor NS blocks on run in a steady loop
+                        // in which `more` is a compile-time true (vmcnt(4), (3), (4), (4), (4)), the last ones of the wave, fewer than 2 NS,
+                        // straight-line behind it (y_block; tests/test_isa_y_loop.py reads the waits off the listing).
                         h8 S[NS][NAC];
                         // Block j of the pass (lane j): the byte offset of its first texel in plane 0.  Its row = the lane rho with
                         // fb <= j < fb + nblk: the row lanes scatter their index through LDS (every wave writes the same values and
@@ -732,10 +740,18 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             // (xs + RING is a multiple of 4: the block starts at a texel group)
                             boff = lane < nb ? ((yb + rho + dist::RING) * (Wp / dist::GROUP) + (xs + dist::RING) / dist::GROUP) * GB : OOB;
                         }
-                        // (the tail chunk: planes high | low | high again | specials = the tail's planes 0, 1, 0, 2 for K slices 0 .. 3)
+                        // (the tail chunk: planes high | low | high again | specials = the tail's planes 0, 1, 0, 2 for K slices 0 .. 3:
+                        //  the lane's offset less 0, 0, 2 PB, PB for kq = 0 .. 3.  Formed per block from voffA, whose bits 6..7 are
+                        //  kq -- four vector instructions into the chunk's own registers, behind a pin: kept across the loop the
+                        //  difference was the register that the steady loop's second copy of the block did not have, 2 spilled at <2,1>)
                         // (the lane's constants captured by value: by reference the kernel took a scalar register more)
-                        auto fetch = [&S, rsrc, voffA, kq](int set, int i, int soff) {   // chunk i: planes 4 i .. 4 i + 3 (the lane's: + kq, in voffA)
-                            const int voff = i == NAC - 1 ? voffA - (kq == 2 ? 2 * PB : (kq == 3 ? PB : 0)) : voffA;
+                        auto fetch = [&S, rsrc, voffA](int set, int i, int soff) {   // chunk i: planes 4 i .. 4 i + 3 (the lane's: + kq, in voffA)
+                            int voff = voffA;
+                            if (i == NAC - 1) {
+                                static_assert(PB == 64 && GB % 256 == 0, "kq = bits 6..7 of voffA");
+                                asm volatile("" : "+v"(voff));
+                                voff -= (int)((0x40800000u >> ((voff >> 3) & 0x18)) & 0xffu);
+                            }
                             S[set][i] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff + i * 4 * PB, 0));
                         };
                         auto fetch_block = [&](int set, int soff) {
@@ -751,7 +767,9 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             for (int u = 0; u < NS; ++u)
                                 if (b0 + u < b1) fetch_block(u, __builtin_amdgcn_readlane(boff, b0 + u));
                             // (the first blocks' operand loads go in front of the Q records', which are needed behind the pass's second barrier only:
-                            // -0.8 % headline, -2.5 % config 5)
+                            // -0.8 % headline, -2.5 % config 5.  The DMA is issued from inline asm: the compiler does not count it, the
+                            // hardware does -- the compiler's counted waits of the Y blocks are at worst stricter than needed, and
+                            // only on the wave's first block, while the DMA is among the NAC youngest loads)
                             // the Q records of the pass's cells, from memory straight to LDS: blocks 4 g .. 4 g + 3 per instruction
                             // (lane = (block, texel)); wave w moves groups w and w + 4
 #pragma unroll
@@ -775,27 +793,41 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             sl1[j] = cxx + o1;
                         }
                         if (go) {
+                            // one block: multiply set u, refill it chunk by chunk with block bj + NS (`more`: there is one -- a
+                            // constant at every call but one, so that no path through a block issues some of its refills only)
+                            auto y_block = [&](int u, int bj, bool more) {
+                                const int soff = more ? __builtin_amdgcn_readlane(boff, bj + NS) : 0;
+                                v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                                for (int c = 0; c < NCHK; ++c) {
+                                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][c], Bv[c], acc, 0, 0, 0);
+                                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][c], Bv[NCHK + c], acc, 0, 0, 0);
+                                    if (more) fetch(u, c, soff);
+                                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][NCHK + c], Bv[c], acc, 0, 0, 0);
+                                    if (more) fetch(u, NCHK + c, soff);
+                                }
+                                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][NAC - 1], Bv[NAC - 1], acc, 0, 0, 0);
+                                if (more) fetch(u, NAC - 1, soff);
+                                // Y[texel 4 kq ..][pixel n] of the block
+                                int bjo = bj;
+                                asm volatile("" : "+s"(bjo));   // (the address from the scalar, per block: not a vector induction variable across the loop)
+                                *reinterpret_cast<v4f*>(&L.Ys[n * XSTRIDE + 16 * bjo + 4 * kq]) = acc;
+                            };
+                            // steady: blocks bi .. bi + NS - 1 all have their successor (bi + 2 NS - 1 < b1)
+                            int bi = b0;
 #pragma unroll 1
-                            for (int bi = b0; bi < b1; bi += NS) {   // (rolled: unrolled, the compiler hoists the later blocks' work and spills)
+                            for (; bi + 2 * NS <= b1; bi += NS) {   // (rolled: unrolled, the compiler hoists the later blocks' work and spills)
 #pragma unroll
-                                for (int u = 0; u < NS; ++u) {
-                                    const int bj = bi + u;
-                                    if (bj >= b1) break;   // uniform
-                                    const bool more = bj + NS < b1;   // uniform
-                                    const int soff = more ? __builtin_amdgcn_readlane(boff, bj + NS) : 0;
-                                    v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                                    for (int c = 0; c < NCHK; ++c) {
-                                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][c], Bv[c], acc, 0, 0, 0);
-                                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][c], Bv[NCHK + c], acc, 0, 0, 0);
-                                        if (more) fetch(u, c, soff);
-                                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][NCHK + c], Bv[c], acc, 0, 0, 0);
-                                        if (more) fetch(u, NCHK + c, soff);
-                                    }
-                                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(S[u][NAC - 1], Bv[NAC - 1], acc, 0, 0, 0);
-                                    if (more) fetch(u, NAC - 1, soff);
-                                    // Y[texel 4 kq ..][pixel n] of the block
-                                    *reinterpret_cast<v4f*>(&L.Ys[n * XSTRIDE + 16 * bj + 4 * kq]) = acc;
+                                for (int u = 0; u < NS; ++u) y_block(u, bi + u, true);
+                            }
+                            // the last 1 .. 2 NS - 1 blocks: set 0 holds block bi, set 1 block bi + 1; only a third one is still to load
+                            if (bi < b1) {
+                                if (NS == 1) {
+                                    y_block(0, bi, false);
+                                } else {
+                                    y_block(0, bi, bi + 2 < b1);
+                                    if (bi + 1 < b1) y_block(1, bi + 1, false);
+                                    if (bi + 2 < b1) y_block(0, bi + 2, false);
                                 }
                             }
                             DSTAMP(6)   // slots, loads + multiplications
