@@ -292,7 +292,7 @@ int pdepth_sample_coords_f32(const pdepth_sweep_desc *desc, const pdepth_camera 
  * :178-181 by the evaluation loop, trainer/default_trainer.py:243-244), batched over B.
  *   dpv [B,D,H,W] (log-DPV if bv_log, else probabilities), intr [B,3,3] full-resolution intrinsics, mask [B,H,W] or
  *   NULL (validity of the ground-truth volume).  unc_ang = rows the volume is shifted by (cfgx["unc_ang"]; 0 = no
- *   shift), [z_start, z_end] = height band (cfgx: unc_shift, unc_shift + unc_span), min_depth / quash as in the
+ *   shift; a shift needs H, W >= 2, its sampling grid divides by size - 1), [z_start, z_end] = height band (cfgx: unc_shift, unc_shift + unc_span), min_depth / quash as in the
  *   reference's branches (:269-290: cfgx and ILIM 3 / 1, KITTI 0 / 0), oob_depth = the depth the reference assigns to
  *   rows shifted in from outside (sum_k d_k for a log-DPV -- exp of the zero padding -- else 0).
  *   plane [B,D,W] = per column the mean depth distribution of the pixels in the band (NaN for columns without one, as

@@ -281,7 +281,9 @@ int pdepth_ufield_f32(const float* dpv, const float* d_candi, const float* intr,
                       size_t workspace_bytes, void* stream) {
     const char* who = "pdepth_ufield_f32";
     if (!dpv || !d_candi || !intr || !plane || !depth_zero) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    if (B <= 0 || D <= 0 || H <= 1 || W <= 1) return fail(PDEPTH_E_ARG, "%s: bad dimension", who);
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: bad dimension", who);
+    // the sampling grid of a shift divides by size - 1 (convert_flowfield): a single row or column can only be collapsed unshifted
+    if (unc_ang != 0.0f && (H <= 1 || W <= 1)) return fail(PDEPTH_E_ARG, "%s: a shift needs H, W >= 2", who);
     const size_t need = pdepth::ufield_workspace_bytes(B, H, W);
     if (!workspace || workspace_bytes < need)
         return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu)", who, need, workspace_bytes);

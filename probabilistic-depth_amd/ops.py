@@ -141,6 +141,9 @@ def ufield(dpv, d_candi, intr, mask=None, BV_log=True, unc_ang=5, z_start=0.6, z
     (utils/img_utils.py:268-358).  mask [B,H,W] | [B,1,H,W] | None."""
     if mask is not None and mask.dim() == 4:
         mask = mask[:, 0]
+    if unc_ang != 0 and dpv.dim() == 4 and (dpv.shape[2] == 1 or dpv.shape[3] == 1):
+        # the reference's convert_flowfield divides by size - 1 (utils/img_utils.py:170-176) and fails the same way
+        raise ZeroDivisionError("ufield: a shift (unc_ang != 0) needs H, W >= 2: the sampling grid divides by size - 1")
     # depth of rows shifted in from outside the image = dpv_to_depthmap of the zero padding = the fp32 sum of the candidates:
     # formed on the host when the candidates come from the host (no device synchronisation inside the call)
     d_sum = None
