@@ -311,7 +311,9 @@ int pdepth_ufield_f32(const float *dpv, const float *d_candi, const float *intr,
  * lines of BaseModel.forward_int (models/models.py:666-672).
  *   logp [B,D,H,W] log-DPV of the network, dmaps [B,H,W] sparse depth, masks [B,H,W] validity (channel 0
  *   of the reference's [B,1,H,W]), var = 0.3 in the reference, eps = torch.finfo(float).eps.
- *   fused [B,D,H,W] (clamped probabilities) and logfused [B,D,H,W]; either may be NULL, not both.
+ *   fused [B,D,H,W] (clamped probabilities) and logfused [B,D,H,W]; either may be NULL, not both.  H*W <= 2^30, B <= 65535.
+ *   A column of logp with a NaN, with -inf on every plane or whose exp overflows comes out as eps (log eps) on every plane,
+ *   where the reference returns NaN; the backward returns non-finite values on such a column.
  */
 int pdepth_dpv_fuse_f32(const float *logp, const float *dmaps, const float *masks, const float *d_candi,
                         int32_t B, int32_t D, int32_t H, int32_t W, float var, float eps, float *fused,

@@ -297,6 +297,7 @@ int pdepth_dpv_fuse_f32(const float* logp, const float* dmaps, const float* mask
     if (!logp || !dmaps || !masks || !d_candi) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: null input");
     if (!fused && !logfused) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: no output requested");
     if (int rc = check_dims("pdepth_dpv_fuse_f32", B, D, H, W)) return rc;
+    if (int rc = check_launch_limits("pdepth_dpv_fuse_f32", B, H, W)) return rc;   // (B is grid.y, like in the backward)
     if (!(var > 0.0f)) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: var must be positive");
     return launched(pdepth::launch_dpv_fuse(logp, dmaps, masks, d_candi, B, D, H, W, var, eps, fused, logfused,
                                             (hipStream_t)stream), "pdepth_dpv_fuse_f32");

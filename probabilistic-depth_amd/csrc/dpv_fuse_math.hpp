@@ -1,5 +1,7 @@
 // exp / log / divide of the DPV fusion kernels (extras.hip: forward; dpv_fuse_bwd.hip: backward).  Both include this header, so
 // the backward recomputes the forward's values bit for bit and decides the clamp on the number the forward clamped.
+// That claim is tested on every pair of forward and backward kernels (tests/test_fuse_gpu.py: test_forward_and_backward_agree_on_q,
+// test_forward_and_backward_agree_on_the_clamp).
 //
 // Hardware exp2 / log2 with an exact-argument reduction (exp_nonpos, geometry.hpp: ~1.5 ulp), log2 x ln 2 (~2 ulp, absolute 1e-7
 // near 1) and a refined reciprocal -- the libm forms cost ~20 instructions each, five per element, and made the forward VALU

@@ -103,7 +103,9 @@ __global__ __launch_bounds__(256) void dpv_fuse_kernel(const float* __restrict__
         float t = expf(-(a * a) / two_var) / sumg;
         if (t != t) t = -1.0f;                       // zero_invalid (img_utils.py:45)
         const float m = t * mask + uni * inv_mask;   // img_utils.py:371
-        return fminf(fmaxf(m, eps), 1.0f);            // clamp(eps, 1) keeps NaN out like torch.clamp
+        // fmaxf / fminf return the other operand for a NaN: a NaN m (or q below) becomes eps, where torch.clamp keeps the NaN.
+        // A NaN, an all -inf or an overflowing column of logp comes out as eps on every plane.
+        return fminf(fmaxf(m, eps), 1.0f);
     };
     float sumf = 0.0f;
     for (int k = 0; k < D; ++k) sumf = sumf + expf(lp[(size_t)k * HW] + logf(tofuse(k)));

@@ -50,6 +50,14 @@ def test_launch_limits():
     assert rc == 1 and "H*W must be at most 2^30" in msg
     rc, msg = _call(B=65536)
     assert rc == 1 and "B at most 65535" in msg
+    # the forward entry puts B into grid.y as well and refuses alike, before any launch
+    lib = _native.load()
+    for kw, what in ((dict(B=65536), "B at most 65535"), (dict(H=1 << 16, W=(1 << 14) + 1), "H*W must be at most 2^30")):
+        a = dict(B=1, H=2, W=2)
+        a.update(kw)
+        rc = lib.pdepth_dpv_fuse_f32(FAKE, FAKE * 2, FAKE * 3, FAKE * 4, a["B"], 4, a["H"], a["W"], 0.3, 1e-7, FAKE * 5, FAKE * 6, None)
+        msg = lib.pdepth_last_error().decode()
+        assert rc == 1 and msg.startswith("pdepth_dpv_fuse_f32: ") and what in msg
 
 
 @pytest.mark.parametrize("var", [0.0, -0.3, float("nan")])
