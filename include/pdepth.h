@@ -58,7 +58,8 @@ extern "C" {
                                 *    backward-compatible additions within 6: pdepth_sweep_backward_f32, pdepth_dpv_reduce_backward_f32,
                                 *    pdepth_dpv_expect_backward_f32; pdepth_dpv_soft_ce_workspace_bytes, pdepth_dpv_soft_ce_f32,
                                 *    pdepth_dpv_soft_ce_backward_f32; pdepth_depth_metrics_workspace_bytes, pdepth_depth_metrics_f32;
-                                *    pdepth_dpv_fuse_backward_f32; pdepth_lidar_depth_workspace_bytes, pdepth_lidar_depth_f32 */
+                                *    pdepth_dpv_fuse_backward_f32; pdepth_lidar_depth_workspace_bytes, pdepth_lidar_depth_f32;
+                                *    pdepth_loss_terms_workspace_bytes, pdepth_loss_{dsc,rsc,dc,smooth}_f32 and their _backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -533,6 +534,65 @@ int pdepth_lidar_depth_f32(const float *points, const int32_t *counts, const flo
                            int32_t Nmax, int32_t point_dim, int32_t M_batched, int32_t intr_batched, int32_t H, int32_t W,
                            int32_t filtering, float filterdiff, float pool_default, float *dmap, float *mask,
                            float *dmap_quarter, float *mask_quarter, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The consistency and smoothness terms of the training loss, one value per batch item, and their gradients (csrc/loss_terms.hip).
+ * Each forward is one pass over the maps plus a one-workgroup-per-item sum of the workgroups' partial sums in a fixed order (the
+ * same bits from call to call); each backward recomputes the per-pixel quantities from the forward's inputs and scales them by
+ * g_value[b] / denominator[b].  Where a mask selects pixels the products with it are kept (x * 0): an item whose mask is empty
+ * is 0 / 0 = NaN, and a NaN or an infinite depth makes its own item NaN, as the torch composition does.  Gradient rules are
+ * torch's: sign(0) = 0 behind abs, a clamp passes the gradient on min <= x <= max, masks, validity and taps are constants.
+ *   All maps fp32, contiguous.  B <= 65535, H, W >= 2 (the down-sample term: >= 4), H * W <= 2^24 (pixel counts are exact in fp32).
+ *   workspace: pdepth_loss_terms_workspace_bytes(B, H, W) bytes (8 bytes per 256 pixels and item) for a term whose threads walk
+ *   a [B,H,W] map -- the down-sample term walks the small map and needs (B, H/4, W/4) --, 256-byte aligned; 0 for sizes out of range.
+ *   value [B]; count [B] = the number of pixels the mask selects (the denominator; the RGB term divides by 3 count).  The backward
+ *   entries take the forward's count.  Nothing is allocated, nothing waits for the host.
+ *
+ * pdepth_loss_dsc_f32: depth_stereo_consistency_loss (losses/loss_blocks.py:147-171 with mean_on_mask :68-71, transform_dmap
+ *   utils/inverse_warp.py:212-253, inverse_warp 'nearest' :174-210).  src_depth, tgt_depth, src_mask [B,H,W]; Kinv [B,3,3] and
+ *   proj [B,3,4] as pdepth_inverse_warp_f32 takes them (target to source); pose_row = the third row of the 4x4 source-to-target
+ *   pose, [B,4] (pose_batched = 1) or [4]; intr [B,3,3].  Per target pixel the sample position, validity and nearest tap are
+ *   those of pdepth_inverse_warp_f32 bit for bit; at the tap z = max(src_depth, 1e-3), z' = ((P0 xs z + P1 ys z) + P2 z) + P3 with
+ *   xs = (x - cx) / fx, ys = (y - cy) / fy, warped = z' src_mask; m = valid & row >= H / 3 & warped > 0;
+ *   value = sum(clamp(|a - b| / |a + b|, 0, 1) m) / sum(m), a = max(tgt_depth m, 1e-3), b = max(warped m, 1e-3).
+ *   Backward: g_tgt_depth [B,H,W] through the quotient (written per pixel, reproducible; the nearest warp passes nothing through
+ *   the position), g_src_depth [B,H,W] through the tap (cleared, then scattered with float atomics: the last bits depend on the
+ *   order of arrival); either may be NULL, not both.
+ * pdepth_loss_rsc_f32: rgb_stereo_consistency_loss (losses/loss_blocks.py:114-145).  src_rgb, tgt_rgb [B,3,H,W], tgt_depth
+ *   [B,H,W]; bilinear taps with zeros padding, the weights and the fma order of pdepth_inverse_warp_f32; m = valid & row >= H / 3;
+ *   value = sum_c sum(|tgt_c m - warped_c m| m) / (3 sum(m)).  Backward: g_tgt_depth [B,H,W] through the sample position -- what
+ *   pdepth_inverse_warp_backward_f32 and the products behind it give, in one thread per pixel, no atomics.
+ * pdepth_loss_dc_f32: depth_consistency_loss (losses/loss_blocks.py:173-184, minpool utils/img_utils.py:87-95).  large [B,H,W],
+ *   small [B,H/4,W/4] (a remainder of H or W is dropped); p = max(min of the 4x4 block, 1e-3) -- a tie goes to the first element
+ *   in row-major order --, s = max(small, 1e-3), keep = row >= (H/4) / 3 of the small map;
+ *   value = sum(clamp(|p - s| / |p + s|, 0, 1) keep) / sum(keep).  Backward: g_large [B,H,W] (every element written: zero but at the
+ *   minimum of each block) and g_small; either may be NULL, not both; no atomics.
+ * pdepth_loss_smooth_f32: edge_aware_smoothness_loss at one scale with the image at the map's size (losses/loss_blocks.py:73-112).
+ *   depth [B,H,W], rgb [B,3,H,W]; value = mean(|d_y - d_y+1| exp(-mean_c |rgb_y - rgb_y+1|)) + the same along x.  Backward:
+ *   g_depth [B,H,W], each pixel gathering its up-to-four differences; no atomics.
+ */
+size_t pdepth_loss_terms_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_loss_dsc_f32(const float *src_depth, const float *tgt_depth, const float *src_mask, const float *Kinv, const float *proj,
+                        const float *pose_row, int32_t pose_batched, const float *intr, int32_t B, int32_t H, int32_t W,
+                        float *value, float *count, void *workspace, size_t workspace_bytes, void *stream);
+int pdepth_loss_dsc_backward_f32(const float *src_depth, const float *tgt_depth, const float *src_mask, const float *Kinv,
+                                 const float *proj, const float *pose_row, int32_t pose_batched, const float *intr,
+                                 const float *count, const float *g_value, int32_t B, int32_t H, int32_t W, float *g_src_depth,
+                                 float *g_tgt_depth, void *stream);
+int pdepth_loss_rsc_f32(const float *src_rgb, const float *tgt_rgb, const float *tgt_depth, const float *Kinv, const float *proj,
+                        int32_t B, int32_t H, int32_t W, float *value, float *count, void *workspace, size_t workspace_bytes,
+                        void *stream);
+int pdepth_loss_rsc_backward_f32(const float *src_rgb, const float *tgt_rgb, const float *tgt_depth, const float *Kinv,
+                                 const float *proj, const float *count, const float *g_value, int32_t B, int32_t H, int32_t W,
+                                 float *g_tgt_depth, void *stream);
+int pdepth_loss_dc_f32(const float *large, const float *small, int32_t B, int32_t H, int32_t W, float *value, float *count,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int pdepth_loss_dc_backward_f32(const float *large, const float *small, const float *count, const float *g_value, int32_t B,
+                                int32_t H, int32_t W, float *g_large, float *g_small, void *stream);
+int pdepth_loss_smooth_f32(const float *depth, const float *rgb, int32_t B, int32_t H, int32_t W, float *value, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int pdepth_loss_smooth_backward_f32(const float *depth, const float *rgb, const float *g_value, int32_t B, int32_t H, int32_t W,
+                                    float *g_depth, void *stream);
 
 #ifdef __cplusplus
 }

@@ -76,13 +76,22 @@ _SIGNATURES = {
     "pdepth_depth_metrics_f32": (c_int, [_P] * 5 + [_F] + [_I] * 4 + [_P] * 4 + [_Z, _P]),
     "pdepth_lidar_depth_workspace_bytes": (_Z, [_I] * 3),
     "pdepth_lidar_depth_f32": (c_int, [_P] * 4 + [_I] * 8 + [_F, _F] + [_P] * 5 + [_Z, _P]),
+    "pdepth_loss_terms_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_loss_dsc_f32": (c_int, [_P] * 6 + [_I, _P] + [_I] * 3 + [_P] * 3 + [_Z, _P]),
+    "pdepth_loss_dsc_backward_f32": (c_int, [_P] * 6 + [_I] + [_P] * 3 + [_I] * 3 + [_P] * 3),
+    "pdepth_loss_rsc_f32": (c_int, [_P] * 5 + [_I] * 3 + [_P] * 3 + [_Z, _P]),
+    "pdepth_loss_rsc_backward_f32": (c_int, [_P] * 7 + [_I] * 3 + [_P] * 2),
+    "pdepth_loss_dc_f32": (c_int, [_P] * 2 + [_I] * 3 + [_P] * 3 + [_Z, _P]),
+    "pdepth_loss_dc_backward_f32": (c_int, [_P] * 4 + [_I] * 3 + [_P] * 3),
+    "pdepth_loss_smooth_f32": (c_int, [_P] * 2 + [_I] * 3 + [_P] * 2 + [_Z, _P]),
+    "pdepth_loss_smooth_backward_f32": (c_int, [_P] * 3 + [_I] * 3 + [_P] * 2),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, metrics, fusion-backward and LiDAR entries live in objects of their own: part of an entry's name -> the source file.  The
+# The loss, loss-term, metrics, fusion-backward and LiDAR entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
 _SOURCE_OF_ENTRY = {"_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
-                    "_lidar_depth_": "csrc/lidar_depth.hip"}
+                    "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip"}
 _ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if any(part in n for part in _SOURCE_OF_ENTRY))
 
 
@@ -916,6 +925,197 @@ def dpv_soft_ce_backward(logp, d_candi, count, label=None, depth_gt=None, varian
                                                             out.data_ptr(), _stream(logp.device))
     _check(rc, lib)
     return out
+
+
+# ---- consistency and smoothness terms of the training loss (ops.depth_stereo_consistency ...) ----------------------------------
+def _maps(who, **named):
+    """Contiguous fp32 device tensors of a loss-term entry, in the order given (shapes are checked by the caller first)."""
+    out = []
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        out.append(t.float().contiguous())
+    return out
+
+
+def _map_dims(who, t, name, least=2):
+    if t.dim() != 3:
+        raise RuntimeError(f"{who}: {name} must be [B,H,W], got {list(t.shape)}")
+    B, H, W = t.shape
+    if B < 1 or H < least or W < least:
+        raise RuntimeError(f"{who}: {name} must be [B,H,W] with B >= 1 and H, W >= {least}, got {list(t.shape)}")
+    return B, H, W
+
+
+def _terms_out(lib, B, H, W, dev, rows=2):
+    ws_bytes = _entry(lib, "pdepth_loss_terms_workspace_bytes")(B, H, W)
+    return torch.empty((rows, B), dtype=torch.float32, device=dev), torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev), ws_bytes
+
+
+def _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
+    B, H, W = _map_dims(who, tgt_depth, "tgt_depth")
+    _shape(src_depth, (B, H, W), "src_depth", who)
+    _shape(src_mask, (B, H, W), "src_mask", who)
+    _shape(Kinv, (B, 3, 3), "Kinv", who)
+    _shape(proj, (B, 3, 4), "proj", who)
+    _shape(intr, (B, 3, 3), "intr", who)
+    if tuple(pose_row.shape) not in ((B, 4), (1, 4)):
+        raise RuntimeError(f"{who}: pose_row must be [{B}, 4] or [1, 4], got {list(pose_row.shape)}")
+    batched = 1 if (pose_row.shape[0] == B and B > 1) else 0
+    return (B, H, W), batched, _maps(who, src_depth=src_depth, tgt_depth=tgt_depth, src_mask=src_mask, Kinv=Kinv, proj=proj,
+                                     pose_row=pose_row, intr=intr)
+
+
+def loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
+    """-> (value [B], count [B]): pdepth_loss_dsc_f32 on the current stream, no host synchronisation."""
+    who = "loss_dsc"
+    _no_autograd(who, src_depth, tgt_depth)
+    (B, H, W), batched, t = _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
+    lib = load()
+    dev = t[0].device
+    out, ws, ws_bytes = _terms_out(lib, B, H, W, dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_dsc_f32")(*(x.data_ptr() for x in t[:6]), batched, t[6].data_ptr(), B, H, W, out[0].data_ptr(),
+                                                out[1].data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return out[0], out[1]
+
+
+def loss_dsc_backward(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, count, g_value, want_src=True, want_tgt=True):
+    """-> (g_src_depth | None, g_tgt_depth | None), each [B,H,W]: pdepth_loss_dsc_backward_f32."""
+    who = "loss_dsc_backward"
+    (B, H, W), batched, t = _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
+    _shape(count, (B,), "count", who)
+    _shape(g_value, (B,), "g_value", who)
+    count, g_value = _maps(who, count=count, g_value=g_value)
+    lib = load()
+    dev = t[0].device
+    g_src = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_src else None
+    g_tgt = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_tgt else None
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_dsc_backward_f32")(*(x.data_ptr() for x in t[:6]), batched, t[6].data_ptr(), count.data_ptr(),
+                                                         g_value.data_ptr(), B, H, W, _ptr(g_src), _ptr(g_tgt), _stream(dev))
+    _check(rc, lib)
+    return g_src, g_tgt
+
+
+def _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
+    B, H, W = _map_dims(who, tgt_depth, "tgt_depth")
+    _shape(src_rgb, (B, 3, H, W), "src_rgb", who)
+    _shape(tgt_rgb, (B, 3, H, W), "tgt_rgb", who)
+    _shape(Kinv, (B, 3, 3), "Kinv", who)
+    _shape(proj, (B, 3, 4), "proj", who)
+    return (B, H, W), _maps(who, src_rgb=src_rgb, tgt_rgb=tgt_rgb, tgt_depth=tgt_depth, Kinv=Kinv, proj=proj)
+
+
+def loss_rsc(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
+    """-> (value [B], count [B]): pdepth_loss_rsc_f32 (count = pixels of the mask; the value divides by 3 count)."""
+    who = "loss_rsc"
+    _no_autograd(who, tgt_depth)
+    (B, H, W), t = _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+    lib = load()
+    dev = t[0].device
+    out, ws, ws_bytes = _terms_out(lib, B, H, W, dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_rsc_f32")(*(x.data_ptr() for x in t), B, H, W, out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(),
+                                                ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return out[0], out[1]
+
+
+def loss_rsc_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count, g_value):
+    """-> g_tgt_depth [B,H,W]: pdepth_loss_rsc_backward_f32."""
+    who = "loss_rsc_backward"
+    (B, H, W), t = _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+    _shape(count, (B,), "count", who)
+    _shape(g_value, (B,), "g_value", who)
+    count, g_value = _maps(who, count=count, g_value=g_value)
+    lib = load()
+    dev = t[0].device
+    g = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_rsc_backward_f32")(*(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W,
+                                                         g.data_ptr(), _stream(dev))
+    _check(rc, lib)
+    return g
+
+
+def _dc_args(who, large, small):
+    B, H, W = _map_dims(who, large, "large", least=4)
+    _shape(small, (B, H // 4, W // 4), "small", who)
+    return (B, H, W), _maps(who, large=large, small=small)
+
+
+def loss_dc(large, small):
+    """-> (value [B], count [B]): pdepth_loss_dc_f32."""
+    who = "loss_dc"
+    _no_autograd(who, large, small)
+    (B, H, W), (large, small) = _dc_args(who, large, small)
+    lib = load()
+    dev = large.device
+    out, ws, ws_bytes = _terms_out(lib, B, H // 4, W // 4, dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_dc_f32")(large.data_ptr(), small.data_ptr(), B, H, W, out[0].data_ptr(), out[1].data_ptr(),
+                                               ws.data_ptr(), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return out[0], out[1]
+
+
+def loss_dc_backward(large, small, count, g_value, want_large=True, want_small=True):
+    """-> (g_large [B,H,W] | None, g_small [B,H/4,W/4] | None): pdepth_loss_dc_backward_f32."""
+    who = "loss_dc_backward"
+    (B, H, W), (large, small) = _dc_args(who, large, small)
+    _shape(count, (B,), "count", who)
+    _shape(g_value, (B,), "g_value", who)
+    count, g_value = _maps(who, count=count, g_value=g_value)
+    lib = load()
+    g_large = torch.empty_like(large) if want_large else None
+    g_small = torch.empty_like(small) if want_small else None
+    with _on_device(large.device):
+        rc = _entry(lib, "pdepth_loss_dc_backward_f32")(large.data_ptr(), small.data_ptr(), count.data_ptr(), g_value.data_ptr(), B, H, W,
+                                                        _ptr(g_large), _ptr(g_small), _stream(large.device))
+    _check(rc, lib)
+    return g_large, g_small
+
+
+def _smooth_args(who, depth, rgb):
+    B, H, W = _map_dims(who, depth, "depth")
+    if tuple(rgb.shape) != (B, 3, H, W):
+        raise RuntimeError(f"{who}: rgb must be {[B, 3, H, W]}, the size of the depth map, got {list(rgb.shape)}; the multi-scale form "
+                           "is loss_blocks.edge_aware_smoothness_loss")
+    return (B, H, W), _maps(who, depth=depth, rgb=rgb)
+
+
+def loss_smooth(depth, rgb):
+    """-> value [B]: pdepth_loss_smooth_f32."""
+    who = "loss_smooth"
+    _no_autograd(who, depth)
+    (B, H, W), (depth, rgb) = _smooth_args(who, depth, rgb)
+    lib = load()
+    dev = depth.device
+    out, ws, ws_bytes = _terms_out(lib, B, H, W, dev, rows=1)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_smooth_f32")(depth.data_ptr(), rgb.data_ptr(), B, H, W, out.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                   _stream(dev))
+    _check(rc, lib)
+    return out[0]
+
+
+def loss_smooth_backward(depth, rgb, g_value):
+    """-> g_depth [B,H,W]: pdepth_loss_smooth_backward_f32."""
+    who = "loss_smooth_backward"
+    (B, H, W), (depth, rgb) = _smooth_args(who, depth, rgb)
+    _shape(g_value, (B,), "g_value", who)
+    (g_value,) = _maps(who, g_value=g_value)
+    lib = load()
+    g = torch.empty_like(depth)
+    with _on_device(depth.device):
+        rc = _entry(lib, "pdepth_loss_smooth_backward_f32")(depth.data_ptr(), rgb.data_ptr(), g_value.data_ptr(), B, H, W, g.data_ptr(),
+                                                            _stream(depth.device))
+    _check(rc, lib)
+    return g
 
 
 # ---- evaluation metrics (ops.depth_metrics) -----------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 
 #include "dpv_fuse_math.hpp"
 #include "geometry.hpp"
+#include "inverse_warp_math.hpp"
 #include "kernels.hpp"
 
 namespace pdepth {
@@ -487,55 +488,7 @@ hipError_t launch_correlation_backward(const float* x1, const float* x2, const f
 // (like ATen's grid_sampler backward) and the gradient with respect to the projected point (X, Y, Z) written per
 // pixel; the 3x3 / 3x4 algebra behind it (depth, pose, intrinsics) is a handful of small matmuls on the host side.
 // ---------------------------------------------------------------------------------------------------
-namespace {
-
-struct WarpSample {
-    float X, Y, pz, Z;       // projected point, pz before the clamp
-    float ix, iy;            // un-normalised sample position
-    int x0, y0;              // top-left tap (clamped to [-2, size + 1])
-    float nw, ne, sw, se;    // bilinear weights
-    float w, e, n, s;
-    bool finite, xi0, xi1, yi0, yi1;
-    float xn, yn;
-};
-
-__device__ __forceinline__ WarpSample warp_sample(const float* __restrict__ ki, const float* __restrict__ pr, int x, int y,
-                                                   float d, int H, int W) {
-    WarpSample q;
-    const float fx = (float)x, fy = (float)y;
-    float cam[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        cam[i] = __builtin_fmaf(ki[i * 3 + 2], 1.0f, __builtin_fmaf(ki[i * 3 + 1], fy, ki[i * 3 + 0] * fx)) * d;
-    float pc[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        pc[i] = __builtin_fmaf(pr[i * 4 + 2], cam[2], __builtin_fmaf(pr[i * 4 + 1], cam[1], pr[i * 4 + 0] * cam[0])) + pr[i * 4 + 3];
-    q.X = pc[0]; q.Y = pc[1]; q.pz = pc[2];
-    q.Z = fmaxf(pc[2], 1e-3f);
-    q.xn = 2.0f * (pc[0] / q.Z) / (float)(W - 1) - 1.0f;
-    q.yn = 2.0f * (pc[1] / q.Z) / (float)(H - 1) - 1.0f;
-    q.ix = __builtin_fmaf(q.xn + 1.0f, (float)W / 2.0f, -0.5f);
-    q.iy = __builtin_fmaf(q.yn + 1.0f, (float)H / 2.0f, -0.5f);
-    const float xf = floorf(q.ix), yf = floorf(q.iy);
-    q.w = q.ix - xf; q.e = 1.0f - q.w; q.n = q.iy - yf; q.s = 1.0f - q.n;
-    q.nw = q.s * q.e; q.ne = q.s * q.w; q.sw = q.n * q.e; q.se = q.n * q.w;
-    q.finite = (q.ix == q.ix) && (q.iy == q.iy);
-    q.x0 = (int)fminf(fmaxf(xf, -2.0f), (float)(W + 1)); q.y0 = (int)fminf(fmaxf(yf, -2.0f), (float)(H + 1));
-    q.xi0 = q.x0 >= 0 && q.x0 < W; q.xi1 = q.x0 + 1 >= 0 && q.x0 + 1 < W;
-    q.yi0 = q.y0 >= 0 && q.y0 < H; q.yi1 = q.y0 + 1 >= 0 && q.y0 + 1 < H;
-    return q;
-}
-
-// nearest tap of grid_sample(mode='nearest'): round half to even of the un-normalised position; -1 = outside / NaN
-__device__ __forceinline__ int nearest_tap(const WarpSample& q, int H, int W) {
-    if (!q.finite) return -1;
-    const float rx = rintf(q.ix), ry = rintf(q.iy);
-    if (!(rx >= 0.0f && rx < (float)W && ry >= 0.0f && ry < (float)H)) return -1;
-    return (int)ry * W + (int)rx;
-}
-
-}  // namespace
+// The per-pixel chain (WarpSample, warp_sample, warp_valid, nearest_tap) is inverse_warp_math.hpp, shared with loss_terms.hip.
 
 template <int MODE>   // 0 bilinear, 1 nearest
 __global__ __launch_bounds__(256) void inverse_warp_kernel(const float* __restrict__ img,
@@ -549,7 +502,7 @@ __global__ __launch_bounds__(256) void inverse_warp_kernel(const float* __restri
     const int b = blockIdx.y;
     const int y = pix / W, x = pix - y * W;
     const WarpSample q = warp_sample(Kinv + b * 9, proj + b * 12, x, y, depth[(size_t)b * HW + pix], H, W);
-    if (valid) valid[(size_t)b * HW + pix] = (fmaxf(fabsf(q.xn), fabsf(q.yn)) <= 1.0f) ? 1 : 0;
+    if (valid) valid[(size_t)b * HW + pix] = warp_valid(q) ? 1 : 0;
     float* ob = out + (size_t)b * C * HW + pix;
     if (MODE == 1) {
         const int tap = nearest_tap(q, H, W);

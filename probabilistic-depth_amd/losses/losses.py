@@ -11,13 +11,18 @@ regresses them again, :80-88), an item without a valid pixel contributes 0 on th
 host: no .item(), no truth test on a tensor, no host copy.  With labels_from_depth=True and dmaps / dmap_imgsizes in the
 target, the soft labels are formed inside the kernel from the depth maps (variance cfg.var.softce, prepared as the loader
 does: clamp(d_candi[0], d_candi[-1]) * mask, kittiloader/batch_scheduler.py:105-106) and soft_labels* may be absent.
+
+With fused_terms=True the consistency and smoothness terms (dc, dsc, rsc, smooth) are the fused HIP passes of csrc/loss_terms.hip
+(ops.depth_consistency, depth_stereo_consistency, rgb_stereo_consistency, edge_aware_smoothness) instead of the torch compositions
+of loss_blocks.py.  The camera matrices they take are formed with the helpers the compositions use (_inv3, intr @ pose[:3]), once
+per (intrinsics, pose) pair of the call, so the masks keep their bits.  The default is the composition.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .loss_blocks import (depth_consistency_loss, depth_stereo_consistency_loss, edge_aware_smoothness_loss,
+from .loss_blocks import (_inv3, depth_consistency_loss, depth_stereo_consistency_loss, edge_aware_smoothness_loss,
                           rgb_stereo_consistency_loss)
 
 
@@ -26,11 +31,12 @@ def _stacked(labels):
 
 
 class BaseLoss(nn.Module):
-    def __init__(self, cfg, id, labels_from_depth=False):
+    def __init__(self, cfg, id, labels_from_depth=False, fused_terms=False):
         super().__init__()
         self.cfg = cfg
         self.id = id
         self.labels_from_depth = labels_from_depth
+        self.fused_terms = fused_terms
 
     def _cross_entropy(self, volumes, tgt, label_key, depth_key, mask_key, d_candi):
         """(sum over the volumes and the items of the per-item cross-entropy, depth map [B,h,w] of the last volume)."""
@@ -72,8 +78,22 @@ class BaseLoss(nn.Module):
         pose_l2r = T.unsqueeze(0).to(device, non_blocking=True)     # target = left, source = right
         pose_r2l = T_inv.unsqueeze(0).to(device, non_blocking=True)
 
+        fused = self.fused_terms
+        cams = {}
+
+        def camera(intr, pose):
+            """(Kinv [B,3,3], proj [B,3,4]) of an (intrinsics, pose) pair as loss_blocks._warp forms them, once per call."""
+            key = (id(intr), id(pose))
+            if key not in cams:
+                k = intr.float()
+                cams[key] = (_inv3(k).expand(B, 3, 3), torch.matmul(k, pose[:, 0:3, :].float()).expand(B, 3, 4))
+            return cams[key]
+
         dc_loss = 0
-        if mul.dc_mul != 0:
+        if mul.dc_mul != 0 and fused:
+            dc_loss = (ops.depth_consistency(large["l"], small["l"])[0].sum() +
+                       ops.depth_consistency(large["r"], small["r"])[0].sum())
+        elif mul.dc_mul != 0:
             dc_loss = (depth_consistency_loss(large["l"], small["l"], per_item=True).sum() +
                        depth_consistency_loss(large["r"], small["r"], per_item=True).sum())
 
@@ -83,6 +103,14 @@ class BaseLoss(nn.Module):
                 dm = large if hi else small
                 mk = "masks_imgsizes" if hi else "masks"
                 ik = "intrinsics_up" if hi else "intrinsics"
+                if fused:   # right into left, then left into right
+                    Kinv, proj = camera(tgt_l[ik], pose_l2r)
+                    dsc_loss = dsc_loss + ops.depth_stereo_consistency(dm["r"], dm["l"], tgt_r[mk], Kinv, proj, pose_r2l[:, 2],
+                                                                       tgt_l[ik].float())[0].sum()
+                    Kinv, proj = camera(tgt_r[ik], pose_r2l)
+                    dsc_loss = dsc_loss + ops.depth_stereo_consistency(dm["l"], dm["r"], tgt_l[mk], Kinv, proj, pose_l2r[:, 2],
+                                                                       tgt_r[ik].float())[0].sum()
+                    continue
                 dl, dr = dm["l"].unsqueeze(1), dm["r"].unsqueeze(1)
                 # right into left, then left into right
                 dsc_loss = dsc_loss + depth_stereo_consistency_loss(dr, dl, tgt_r[mk], tgt_l[mk], pose_l2r, tgt_l[ik],
@@ -92,7 +120,10 @@ class BaseLoss(nn.Module):
 
         rgb_l, rgb_r = tgt_l["rgb"][:, -1], tgt_r["rgb"][:, -1]
         rsc_loss = 0
-        if mul.rsc_mul != 0:
+        if mul.rsc_mul != 0 and fused:
+            rsc_loss = (ops.rgb_stereo_consistency(rgb_r, rgb_l, large["l"], *camera(tgt_l["intrinsics_up"], pose_l2r))[0].sum() +
+                        ops.rgb_stereo_consistency(rgb_l, rgb_r, large["r"], *camera(tgt_r["intrinsics_up"], pose_r2l))[0].sum())
+        elif mul.rsc_mul != 0:
             rsc_loss = (rgb_stereo_consistency_loss(rgb_r, rgb_l, large["l"], pose_l2r, tgt_l["intrinsics_up"], per_item=True).sum() +
                         rgb_stereo_consistency_loss(rgb_l, rgb_r, large["r"], pose_r2l, tgt_r["intrinsics_up"], per_item=True).sum())
 
@@ -104,7 +135,9 @@ class BaseLoss(nn.Module):
                             rgb_stereo_consistency_loss(low_l, low_r, small["r"], pose_r2l, tgt_r["intrinsics"], per_item=True).sum())
 
         smooth_loss = 0
-        if mul.smooth_mul != 0:   # (a mean over the batch times B = the sum of the per-item means)
+        if mul.smooth_mul != 0 and fused:
+            smooth_loss = ops.edge_aware_smoothness(large["l"], rgb_l).sum() + ops.edge_aware_smoothness(large["r"], rgb_r).sum()
+        elif mul.smooth_mul != 0:   # (a mean over the batch times B = the sum of the per-item means)
             smooth_loss = B * (edge_aware_smoothness_loss([large["l"].unsqueeze(1)], rgb_l, 1) +
                                edge_aware_smoothness_loss([large["r"].unsqueeze(1)], rgb_r, 1))
 

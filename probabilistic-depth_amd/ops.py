@@ -230,6 +230,58 @@ def lidar_depth(points, counts, M_velo2cam, intr, width, height, filtering=2, fi
     return {"dmap_imgsizes": dmap, "masks_imgsizes": mask.unsqueeze(1), "dmaps": dmap_q, "masks": mask_q.unsqueeze(1)}
 
 
+def depth_stereo_consistency(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
+    """depth_stereo_consistency_loss per item (losses/loss_blocks.py:147-171), one HIP pass: (value [B], count [B]).
+
+    src_depth, tgt_depth [B,H,W] | [B,1,H,W]; src_mask likewise; Kinv [B,3,3] = intr^-1 and proj [B,3,4] = intr @ pose_target2src[:3]
+    as utils.inverse_warp.warp_with_matrices takes them; pose_row [B,4] | [1,4] = the third row of the source-to-target pose; intr
+    [B,3,3].  The mask (valid & lower two thirds & warped > 0) is formed from the sample positions of the HIP inverse_warp, bit for
+    bit; count is its size per item, not differentiable; an item with an empty mask is NaN.  Differentiable with respect to both
+    depth maps (the source through an atomic scatter); everything else is data."""
+    who = "depth_stereo_consistency"
+    src_depth, tgt_depth, src_mask = (_squeeze_map(t) for t in (src_depth, tgt_depth, src_mask))
+    if _wants_grad(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
+        _refuse_data_grad(who, src_mask=src_mask, Kinv=Kinv, proj=proj, pose_row=pose_row, intr=intr)
+        return _DscFn.apply(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
+    return _native.loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
+
+
+def rgb_stereo_consistency(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
+    """rgb_stereo_consistency_loss per item (losses/loss_blocks.py:114-145), one HIP pass: (value [B], count [B]).
+
+    src_rgb, tgt_rgb [B,3,H,W]; tgt_depth [B,H,W] | [B,1,H,W]; Kinv, proj as above.  count = the pixels of the mask (valid & lower
+    two thirds); the value divides by 3 count.  Differentiable with respect to tgt_depth only, through the sample position."""
+    who = "rgb_stereo_consistency"
+    tgt_depth = _squeeze_map(tgt_depth)
+    if _wants_grad(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
+        _refuse_data_grad(who, src_rgb=src_rgb, tgt_rgb=tgt_rgb, Kinv=Kinv, proj=proj)
+        return _RscFn.apply(src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+    return _native.loss_rsc(src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+
+
+def depth_consistency(large, small):
+    """depth_consistency_loss per item (losses/loss_blocks.py:173-184), one HIP pass: (value [B], count [B]).  large [B,H,W], small
+    [B,H//4,W//4]; differentiable with respect to both."""
+    if _wants_grad(large, small):
+        return _DcFn.apply(large, small)
+    return _native.loss_dc(large, small)
+
+
+def edge_aware_smoothness(depth, rgb):
+    """edge_aware_smoothness_loss at one scale, per item (losses/loss_blocks.py:73-112), one HIP pass: value [B].  depth [B,H,W] |
+    [B,1,H,W], rgb [B,3,H,W] of the same size (another size -- the multi-scale form -- is
+    loss_blocks.edge_aware_smoothness_loss); differentiable with respect to depth only."""
+    who = "edge_aware_smoothness"
+    depth = _squeeze_map(depth)
+    if depth.dim() != 3 or rgb.dim() != 4 or tuple(rgb.shape) != (depth.shape[0], 3) + tuple(depth.shape[1:]):
+        raise RuntimeError(f"{who}: depth {list(depth.shape)} and rgb {list(rgb.shape)} must be [B,H,W] and [B,3,H,W] of one size; "
+                           "for an image of another size use loss_blocks.edge_aware_smoothness_loss")
+    if _wants_grad(depth, rgb):
+        _refuse_data_grad(who, rgb=rgb)
+        return _SmoothFn.apply(depth, rgb)
+    return _native.loss_smooth(depth, rgb)
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
@@ -284,6 +336,18 @@ def _refuse_grad(who, **named):
         if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
             raise RuntimeError(f"{who}: {name} requires grad, but the HIP backward differentiates the feature maps / volumes only "
                                f"(geometry and depth candidates are data); detach {name}")
+
+
+def _squeeze_map(t):
+    """[B,1,H,W] -> [B,H,W] (the reference's layout of depth maps and masks)."""
+    return t[:, 0] if isinstance(t, torch.Tensor) and t.dim() == 4 and t.shape[1] == 1 else t
+
+
+def _refuse_data_grad(who, **named):
+    for name, x in named.items():
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{who}: {name} requires grad, but the HIP backward differentiates the depth maps only "
+                               f"(images, masks, poses and intrinsics are data); detach {name}")
 
 
 def _sweep_wants_grad(who, ref, src, K, R, t, rays, cxcy, d_candi):
@@ -416,6 +480,84 @@ class _DpvSoftCeFn(torch.autograd.Function):
         if g_loss is not None or g_depth is not None:
             g = _native.dpv_soft_ce_backward(logp, dc, count, label, depth_gt, ctx.cfg[0], mask, g_loss, g_depth, ctx.cfg[1])
         return (g,) + (None,) * 7
+
+
+class _DscFn(torch.autograd.Function):
+    """depth_stereo_consistency under autograd: (value, count); the backward recomputes every pixel from the inputs."""
+
+    @staticmethod
+    def forward(ctx, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
+        ctx.set_materialize_grads(False)
+        value, count = _native.loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
+        ctx.save_for_backward(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, count)
+        ctx.mark_non_differentiable(count)
+        return value, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, _g_count):
+        want_src, want_tgt = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_value is None or not (want_src or want_tgt):
+            return (None,) * 7
+        *inputs, count = ctx.saved_tensors
+        g_src, g_tgt = _native.loss_dsc_backward(*inputs, count, g_value, want_src=want_src, want_tgt=want_tgt)
+        return (g_src, g_tgt) + (None,) * 5
+
+
+class _RscFn(torch.autograd.Function):
+    """rgb_stereo_consistency under autograd: (value, count)."""
+
+    @staticmethod
+    def forward(ctx, src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
+        ctx.set_materialize_grads(False)
+        value, count = _native.loss_rsc(src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+        ctx.save_for_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count)
+        ctx.mark_non_differentiable(count)
+        return value, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, _g_count):
+        if g_value is None or not ctx.needs_input_grad[2]:
+            return (None,) * 5
+        return None, None, _native.loss_rsc_backward(*ctx.saved_tensors, g_value), None, None
+
+
+class _DcFn(torch.autograd.Function):
+    """depth_consistency under autograd: (value, count)."""
+
+    @staticmethod
+    def forward(ctx, large, small):
+        ctx.set_materialize_grads(False)
+        value, count = _native.loss_dc(large, small)
+        ctx.save_for_backward(large, small, count)
+        ctx.mark_non_differentiable(count)
+        return value, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, _g_count):
+        want_large, want_small = ctx.needs_input_grad
+        if g_value is None or not (want_large or want_small):
+            return None, None
+        return _native.loss_dc_backward(*ctx.saved_tensors, g_value, want_large=want_large, want_small=want_small)
+
+
+class _SmoothFn(torch.autograd.Function):
+    """edge_aware_smoothness under autograd."""
+
+    @staticmethod
+    def forward(ctx, depth, rgb):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(depth, rgb)
+        return _native.loss_smooth(depth, rgb)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value):
+        if g_value is None or not ctx.needs_input_grad[0]:
+            return None, None
+        return _native.loss_smooth_backward(*ctx.saved_tensors, g_value), None
 
 
 class _CorrelationFn(torch.autograd.Function):
