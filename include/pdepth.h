@@ -59,7 +59,8 @@ extern "C" {
                                 *    pdepth_dpv_expect_backward_f32; pdepth_dpv_soft_ce_workspace_bytes, pdepth_dpv_soft_ce_f32,
                                 *    pdepth_dpv_soft_ce_backward_f32; pdepth_depth_metrics_workspace_bytes, pdepth_depth_metrics_f32;
                                 *    pdepth_dpv_fuse_backward_f32; pdepth_lidar_depth_workspace_bytes, pdepth_lidar_depth_f32;
-                                *    pdepth_loss_terms_workspace_bytes, pdepth_loss_{dsc,rsc,dc,smooth}_f32 and their _backward_f32 */
+                                *    pdepth_loss_terms_workspace_bytes, pdepth_loss_{dsc,rsc,dc,smooth}_f32 and their _backward_f32;
+                                *    PDEPTH_DTYPE_F16 / PDEPTH_DTYPE_BF16, pdepth_dpv_reduce_ex_lp, pdepth_dpv_reduce_backward_lp */
 
 enum {
     PDEPTH_OK = 0,
@@ -255,6 +256,24 @@ int pdepth_dpv_reduce_ex_f32(const float *logits, const float *addend, const flo
                              int32_t H, int32_t W, float *logp, float *prob, float *depth, float *variance,
                              float *logp_quarter, void *stream);
 
+/* the 2-byte element types of the _lp entries (0 and every other value: PDEPTH_E_ARG) */
+enum { PDEPTH_DTYPE_F16 = 1, PDEPTH_DTYPE_BF16 = 2 };
+
+/*
+ * pdepth_dpv_reduce_ex_f32 on half-precision logits, as a model under torch.autocast hands them over: logits and the
+ * optional addend [B,D,H,W] are IEEE binary16 (PDEPTH_DTYPE_F16) or bfloat16 (PDEPTH_DTYPE_BF16), both of the one dtype.
+ * Every element is widened to fp32 where it is loaded, which is exact, and nothing else changes: every sum is the fp32 one
+ * of pdepth_dpv_reduce_ex_f32, in its order, so logp, depth, variance and logp_quarter (fp32, shapes and the H, W >= 4 rule
+ * as there) have the bits pdepth_dpv_reduce_ex_f32 gives on the widened input.  prob is fp32 (prob_is_lp = 0) or of the
+ * logits' dtype (prob_is_lp != 0): the fp32 value rounded to nearest-even where it is stored.  The cast costs no pass of its
+ * own: 6 bytes per element for logp against 14 for a cast followed by the fp32 entry.
+ * logp is fp32 and so cannot alias the half-precision logits; no output may alias an input.  A volume whose base address
+ * is not 8-byte aligned (a 2-byte view may start 2 bytes into its storage), W % 4 != 0 or D > 128 runs one pixel per thread.
+ */
+int pdepth_dpv_reduce_ex_lp(int32_t dtype, const void *logits, const void *addend, const float *d_candi, int32_t B, int32_t D,
+                            int32_t H, int32_t W, float *logp, void *prob, int32_t prob_is_lp, float *depth, float *variance,
+                            float *logp_quarter, void *stream);
+
 /*
  * Expectation only: depth[b,y,x] = sum_k d_k * (bv_log ? exp(dpv[b,k,y,x]) : dpv[b,k,y,x]).
  * Replaces dpv_to_depthmap (utils/img_utils.py:52-61), batched over B.
@@ -423,6 +442,16 @@ int pdepth_sweep_backward_f32(const pdepth_sweep_desc *desc, const pdepth_camera
 int pdepth_dpv_reduce_backward_f32(const float *logp, const float *d_candi, int32_t B, int32_t D, int32_t H, int32_t W,
                                    const float *g_logp, const float *g_prob, const float *g_depth, float *g_logits,
                                    void *stream);
+
+/*
+ * Backward of pdepth_dpv_reduce_ex_lp: pdepth_dpv_reduce_backward_f32 with g_logits [B,D,H,W] stored in `dtype`, the fp32
+ * value rounded to nearest-even, and g_prob read in fp32 (g_prob_is_lp = 0) or in `dtype` (g_prob_is_lp != 0: the type prob
+ * was emitted in), widened where it is loaded.  logp, g_logp and g_depth are fp32, and so is every sum: one thread per pixel,
+ * planes ascending, the bits of pdepth_dpv_reduce_backward_f32 rounded once.  g_logits may alias no input.
+ */
+int pdepth_dpv_reduce_backward_lp(int32_t dtype, const float *logp, const float *d_candi, int32_t B, int32_t D, int32_t H,
+                                  int32_t W, const float *g_logp, const void *g_prob, int32_t g_prob_is_lp,
+                                  const float *g_depth, void *g_logits, void *stream);
 
 /*
  * Backward of pdepth_dpv_expect_f32 (dpv_to_depthmap, utils/img_utils.py:52-61):

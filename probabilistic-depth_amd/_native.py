@@ -55,6 +55,8 @@ _SIGNATURES = {
     "pdepth_dpv_reduce_f32": (c_int, [_P, _P] + [_I] * 4 + [_P] * 3),
     "pdepth_dpv_reduce_ex_f32": (c_int, [_P] * 3 + [_I] * 4 + [_P] * 6),
     "pdepth_dpv_reduce_backward_f32": (c_int, [_P, _P] + [_I] * 4 + [_P] * 5),
+    "pdepth_dpv_reduce_ex_lp": (c_int, [_I] + [_P] * 3 + [_I] * 4 + [_P] * 2 + [_I] + [_P] * 4),
+    "pdepth_dpv_reduce_backward_lp": (c_int, [_I, _P, _P] + [_I] * 4 + [_P] * 2 + [_I] + [_P] * 3),
     "pdepth_dpv_expect_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 2),
     "pdepth_dpv_expect_backward_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 3),
     "pdepth_dpv_moments_f32": (c_int, [_P, _P] + [_I] * 5 + [_P] * 3),
@@ -91,7 +93,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
 _SOURCE_OF_ENTRY = {"_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
-                    "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip"}
+                    "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
+                    "_reduce_backward_lp": "csrc/dpv_half.hip"}
 _ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if any(part in n for part in _SOURCE_OF_ENTRY))
 
 
@@ -196,14 +199,19 @@ def _volume_dims(who, volume, d_candi, name):
     return tuple(volume.shape)
 
 
-def _dev(t: torch.Tensor, name: str) -> int:
+def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> int:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a torch.Tensor")
     if not t.is_cuda:
         raise RuntimeError(f"{name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: expected float32, got {t.dtype}")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {t.dtype}")
     return t.data_ptr()
+
+
+# the element types of the half-precision reductions (pdepth_dpv_reduce_ex_lp): torch dtype -> PDEPTH_DTYPE_*
+DTYPE_F16, DTYPE_BF16 = 1, 2
+_LP_DTYPES = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -452,6 +460,9 @@ def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
     """logits [B,D,H,W] -> (logp [B,D,H,W] | None, depth [B,H,W] | None)."""
     lib = load()
     _no_autograd("dpv_reduce", logits)   # (in place it would also overwrite a tensor that carries a grad_fn)
+    if isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in _LP_DTYPES:
+        out = dpv_reduce_ex(logits, d_candi, None, want_logp, False, want_depth)   # (fp32 outputs: nothing to write in place)
+        return out.get("logp"), out.get("depth")
     _dev(logits, "logits")
     B, D, H, W = _volume_dims("dpv_reduce", logits, d_candi, "logits")
     logits, d_candi = logits.contiguous(), d_candi.contiguous()
@@ -466,13 +477,60 @@ def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
     return logp, depth
 
 
+def _dpv_reduce_ex_lp(lib, logits, d_candi, addend, want_logp, want_prob, want_depth, want_var, want_quarter, prob_dtype):
+    """dpv_reduce_ex on fp16 / bf16 logits (pdepth_dpv_reduce_ex_lp): every output fp32, prob in prob_dtype."""
+    who, dtype = "dpv_reduce_ex", logits.dtype
+    if addend is not None and logits.dim() == 4:
+        if isinstance(addend, torch.Tensor) and addend.dtype != dtype:
+            raise RuntimeError(f"{who}: addend is {addend.dtype}, logits are {dtype}: both must be of one dtype "
+                               "(cast the fp32 one down, or the half one up with .float())")
+        _dev(addend, "addend", dtype)
+        if addend.shape != logits.shape:
+            raise RuntimeError(f"{who}: addend shape {tuple(addend.shape)} != logits {tuple(logits.shape)}")
+        addend = addend.contiguous()
+    if prob_dtype not in (None, torch.float32, dtype):
+        raise RuntimeError(f"{who}: prob_dtype must be torch.float32 or the logits' {dtype}, got {prob_dtype}")
+    prob_lp = prob_dtype == dtype
+    B, D, H, W = _volume_dims(who, logits, d_candi, "logits")
+    logits, d_candi = logits.contiguous(), d_candi.contiguous()
+    dev = logits.device
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {}
+    if want_logp:
+        out["logp"] = f32(B, D, H, W)
+    if want_prob:
+        out["prob"] = torch.empty_like(logits) if prob_lp else f32(B, D, H, W)
+    if want_depth:
+        out["depth"] = f32(B, H, W)
+    if want_var:
+        out["var"] = f32(B, H, W)
+    if want_quarter:
+        out["quarter"] = f32(B, D, H // 4, W // 4)
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    with torch.cuda.device(dev):
+        rc = _entry(lib, "pdepth_dpv_reduce_ex_lp")(_LP_DTYPES[dtype], logits.data_ptr(), addend.data_ptr() if addend is not None else None,
+                                                    _dev(d_candi, "d_candi"), B, D, H, W, ptr("logp"), ptr("prob"), int(prob_lp),
+                                                    ptr("depth"), ptr("var"), ptr("quarter"), _stream(dev))
+    _check(rc, lib)
+    return out
+
+
 def dpv_reduce_ex(logits, d_candi, addend=None, want_logp=True, want_prob=False, want_depth=False, want_var=False,
-                  want_quarter=False, inplace=False):
+                  want_quarter=False, inplace=False, prob_dtype=None):
     """(logits [+ addend]) [B,D,H,W] -> dict of the requested outputs: logp, prob = exp(logp) [B,D,H,W], depth, var
-    [B,H,W], quarter = nearest quarter-resolution logp [B,D,H//4,W//4] -- one pass (pdepth_dpv_reduce_ex_f32)."""
+    [B,H,W], quarter = nearest quarter-resolution logp [B,D,H//4,W//4] -- one pass (pdepth_dpv_reduce_ex_f32).
+    fp16 / bf16 logits (and addend, of the same dtype) are widened in the load (pdepth_dpv_reduce_ex_lp): the outputs are
+    fp32, prob is fp32 or, with prob_dtype=logits.dtype, of that dtype; inplace is ignored there, the output being another type."""
     lib = load()
     _no_autograd("dpv_reduce_ex", logits, addend)
+    if isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in _LP_DTYPES:
+        return _dpv_reduce_ex_lp(lib, logits, d_candi, addend, want_logp, want_prob, want_depth, want_var, want_quarter, prob_dtype)
     _dev(logits, "logits")
+    if prob_dtype not in (None, torch.float32):
+        raise RuntimeError(f"dpv_reduce_ex: prob_dtype must be torch.float32 or the logits' {logits.dtype}, got {prob_dtype}")
+    if isinstance(addend, torch.Tensor) and addend.dtype != logits.dtype and addend.dtype in _LP_DTYPES:
+        raise RuntimeError(f"dpv_reduce_ex: addend is {addend.dtype}, logits are {logits.dtype}: both must be of one dtype "
+                           "(cast the fp32 one down, or the half one up with .float())")
     if addend is not None and logits.dim() == 4:   # (the addend's shape before the candidates: the order these checks have had)
         _dev(addend, "addend")
         if addend.shape != logits.shape:
@@ -799,6 +857,39 @@ def dpv_reduce_backward(logp, d_candi, g_logp=None, g_prob=None, g_depth=None):
         rc = lib.pdepth_dpv_reduce_backward_f32(logp.data_ptr(), d_candi.data_ptr(), B, D, H, W,
                                                 *[None if g is None else g.data_ptr() for g in gs], out.data_ptr(),
                                                 _stream(logp.device))
+    _check(rc, lib)
+    return out
+
+
+def dpv_reduce_backward_lp(logp, d_candi, dtype, g_logp=None, g_prob=None, g_depth=None):
+    """dpv_reduce_backward with g_logits in `dtype` (torch.float16 | torch.bfloat16), the fp32 value rounded once; g_prob is read
+    in fp32 or in `dtype`, as it comes: no copy of either (pdepth_dpv_reduce_backward_lp)."""
+    who = "dpv_reduce_backward_lp"
+    if dtype not in _LP_DTYPES:
+        raise RuntimeError(f"{who}: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+    if g_logp is None and g_prob is None and g_depth is None:
+        raise RuntimeError(f"{who}: no incoming gradient")
+    B, D, H, W = _volume_dims(who, logp, d_candi, "logp")
+    for nm, g, shp in (("g_logp", g_logp, (B, D, H, W)), ("g_prob", g_prob, (B, D, H, W)), ("g_depth", g_depth, (B, H, W))):
+        if g is not None:
+            _shape(g, shp, nm, who)
+    lib = load()
+    _dev(logp, "logp"), _dev(d_candi, "d_candi")
+    logp, d_candi = logp.contiguous(), d_candi.contiguous()
+    g_logp, g_depth = [None if g is None else g.contiguous().float() for g in (g_logp, g_depth)]
+    prob_lp = g_prob is not None and g_prob.dtype == dtype
+    if g_prob is not None:
+        g_prob = g_prob.contiguous() if prob_lp else g_prob.contiguous().float()
+    for nm, g in (("g_logp", g_logp), ("g_depth", g_depth)):
+        if g is not None:
+            _dev(g, nm)
+    if g_prob is not None:
+        _dev(g_prob, "g_prob", dtype if prob_lp else torch.float32)
+    out = torch.empty(logp.shape, dtype=dtype, device=logp.device)
+    ptr = lambda g: None if g is None else g.data_ptr()
+    with _on_device(logp.device):
+        rc = _entry(lib, "pdepth_dpv_reduce_backward_lp")(_LP_DTYPES[dtype], logp.data_ptr(), d_candi.data_ptr(), B, D, H, W, ptr(g_logp),
+                                                          ptr(g_prob), int(prob_lp), ptr(g_depth), out.data_ptr(), _stream(logp.device))
     _check(rc, lib)
     return out
 

@@ -11,94 +11,12 @@
 #include <hip/hip_runtime.h>
 
 #include "dpv_lanes.hpp"
+#include "dpv_reduce_body.hpp"
 #include "kernels.hpp"
 
 namespace pdepth {
 
-// Extras of the extended reduction (pdepth_dpv_reduce_ex_f32): the same single pass with optional outputs, all from the
-// registers that already hold the column --
-//   addend   : x = logits + addend before the softmax   (feedback update log_softmax(BV_cur + BV_resi), models.py:694)
-//   prob     : exp(logp), the decoder's input            (models.py:697 torch.exp(BV_cur_upd), :651)
-//   variance : sum_k (d_k - E[d])^2 p_k                   (trainer/default_trainer.py:333-336)
-//   quarter  : logp at every 4th row and column, [B,D,H/4,W/4] = F.interpolate(logp, scale_factor=0.25,
-//              mode='nearest'), the next frame's prev_output (trainer/default_trainer.py:221)
-struct DpvExtras {
-    const float* addend;
-    float* prob;
-    float* variance;
-    float* quarter;
-    int W;
-};
-
-// The log-softmax sweep of a lane's RPL planes + the expectation; EX: with the extras (compiled out of the plain kernel).
-template <int RPL, bool EX>
-__device__ __forceinline__ void dpv_reduce_lanes(const float* __restrict__ x, const float* __restrict__ dc, int D, int HW,
-                                                 float* logp, float* __restrict__ depth, const DpvExtras& ex) {
-    const QuadLane L = quad_lane(D, HW);
-    const int g = L.g, b = L.b;
-    const bool live = L.live;
-    float4 v[RPL];
-    load_planes(v, x, L, 0, D, HW, -INFINITY, true, EX ? ex.addend : nullptr);
-    float4 m = v[0];
-#pragma unroll
-    for (int i = 1; i < RPL; ++i) {
-        m.x = fmaxf(m.x, v[i].x); m.y = fmaxf(m.y, v[i].y); m.z = fmaxf(m.z, v[i].z); m.w = fmaxf(m.w, v[i].w);
-    }
-    m = group_max(m);
-    float4 sum = splat4(0.f);
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        if (g + 4 * i < D) {
-            v[i].x -= m.x; v[i].y -= m.y; v[i].z -= m.z; v[i].w -= m.w;
-            sum.x += expf(v[i].x); sum.y += expf(v[i].y); sum.z += expf(v[i].z); sum.w += expf(v[i].w);
-        }
-    }
-    sum = group_sum(sum);
-    const float4 ls = make_float4(logf(sum.x), logf(sum.y), logf(sum.z), logf(sum.w));
-    float4 e = splat4(0.f);
-    // quarter-resolution copy: this lane's first pixel, when its row is a multiple of 4 (W % 4 == 0: a quad never
-    // straddles rows and starts at a column that is a multiple of 4)
-    int py = 0, pxq = 0, Wq = 0, Hq = 0;
-    bool qrow = false;
-    if (EX) {
-        const int pix = L.q * 4;
-        py = pix / ex.W, pxq = (pix - py * ex.W) >> 2;
-        Wq = ex.W >> 2, Hq = (HW / ex.W) >> 2;
-        qrow = ex.quarter && live && (py & 3) == 0 && (py >> 2) < Hq && pxq < Wq;
-    }
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-        const int k = g + 4 * i;
-        if (k < D) {
-            const float4 lp = make_float4(v[i].x - ls.x, v[i].y - ls.y, v[i].z - ls.z, v[i].w - ls.w);
-            const float4 p = make_float4(expf(lp.x), expf(lp.y), expf(lp.z), expf(lp.w));
-            if (EX) v[i] = p;   // (kept for the variance sweep)
-            if (live) {
-                if (logp) store_nt(logp + L.off + (size_t)k * HW, lp);
-                if (EX && ex.prob) store_nt(ex.prob + L.off + (size_t)k * HW, p);
-                if (EX && qrow) ex.quarter[((size_t)b * D + k) * Hq * Wq + (size_t)(py >> 2) * Wq + pxq] = lp.x;
-            }
-            expect_add<false>(e, dc[k], p);
-        }
-    }
-    e = group_sum(e);
-    if (depth && live && g == 0) *reinterpret_cast<float4*>(depth + L.poff) = e;
-    if (EX && ex.variance) {   // second sweep over the registers: sum_k (d_k - mean)^2 p_k with the mean just formed
-        float4 var = splat4(0.f);
-#pragma unroll
-        for (int i = 0; i < RPL; ++i) {
-            const int k = g + 4 * i;
-            if (k < D) {
-                const float dk = dc[k];
-                const float4 dd = make_float4(dk - e.x, dk - e.y, dk - e.z, dk - e.w);
-                var.x += (dd.x * dd.x) * v[i].x; var.y += (dd.y * dd.y) * v[i].y;
-                var.z += (dd.z * dd.z) * v[i].z; var.w += (dd.w * dd.w) * v[i].w;
-            }
-        }
-        var = group_sum(var);
-        if (live && g == 0) *reinterpret_cast<float4*>(ex.variance + L.poff) = var;
-    }
-}
+// (DpvExtras and the bodies dpv_reduce_lanes / dpv_reduce_ex_pixel: dpv_reduce_body.hpp, shared with dpv_half.hip)
 
 template <int RPL>
 __global__ __launch_bounds__(256) void dpv_reduce_vec4_kernel(const float* __restrict__ x,
@@ -143,34 +61,7 @@ __global__ __launch_bounds__(256) void dpv_reduce_ex_vec4_kernel(const float* __
 __global__ __launch_bounds__(256) void dpv_reduce_ex_scalar_kernel(const float* x, const float* __restrict__ dc, int D,
                                                                    int HW, float* logp, float* __restrict__ depth,
                                                                    DpvExtras ex) {
-    const int pix = blockIdx.x * 256 + threadIdx.x;
-    if (pix >= HW) return;
-    const int b = blockIdx.y;
-    const size_t off = (size_t)b * D * HW + pix;
-    auto at = [&](int k) { return x[off + (size_t)k * HW] + (ex.addend ? ex.addend[off + (size_t)k * HW] : 0.0f); };
-    float m = -INFINITY;
-    for (int k = 0; k < D; ++k) m = fmaxf(m, at(k));
-    float s = 0.f;
-    for (int k = 0; k < D; ++k) s += expf(at(k) - m);
-    const float ls = logf(s);
-    const int py = pix / ex.W, px = pix - py * ex.W, Wq = ex.W >> 2, Hq = (HW / ex.W) >> 2;
-    const bool qpix = ex.quarter && (py & 3) == 0 && (px & 3) == 0 && (py >> 2) < Hq && (px >> 2) < Wq;
-    float e = 0.f;
-    for (int k = 0; k < D; ++k) {   // (logp may alias logits: nothing is read again after this sweep unless variance)
-        const float lp = (at(k) - m) - ls;
-        e += dc[k] * expf(lp);
-    }
-    float var = 0.f;
-    for (int k = 0; k < D; ++k) {
-        const float lp = (at(k) - m) - ls, p = expf(lp), dd = dc[k] - e;
-        var += (dd * dd) * p;
-        if (ex.prob) ex.prob[off + (size_t)k * HW] = p;
-        if (qpix) ex.quarter[((size_t)b * D + k) * Hq * Wq + (size_t)(py >> 2) * Wq + (px >> 2)] = lp;
-    }
-    if (logp)
-        for (int k = 0; k < D; ++k) logp[off + (size_t)k * HW] = (at(k) - m) - ls;   // last: logp may alias logits
-    if (depth) depth[(size_t)b * HW + pix] = e;
-    if (ex.variance) ex.variance[(size_t)b * HW + pix] = var;
+    dpv_reduce_ex_pixel<false>(x, dc, D, HW, logp, depth, ex);
 }
 
 // Expectation in the wave layout: all loads of a lane issued up front (RPL 16-byte non-temporal loads in flight per lane).

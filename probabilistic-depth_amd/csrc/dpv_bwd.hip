@@ -9,6 +9,7 @@
 // results are reproducible bit for bit.
 #include <hip/hip_runtime.h>
 
+#include "dpv_reduce_body.hpp"
 #include "kernels.hpp"
 
 namespace pdepth {
@@ -18,26 +19,7 @@ namespace {
 __global__ __launch_bounds__(256) void dpv_reduce_bwd_kernel(const float* __restrict__ logp, const float* __restrict__ dc, int D, int HW,
                                                              const float* __restrict__ g_logp, const float* __restrict__ g_prob,
                                                              const float* __restrict__ g_depth, float* __restrict__ g_x) {
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= HW) return;
-    const size_t b = blockIdx.y;
-    const size_t base = b * D * HW + pix;
-    const float gd = g_depth ? g_depth[b * HW + pix] : 0.0f;
-    float sum = 0.0f;
-    for (int k = 0; k < D; ++k) {
-        const size_t i = base + (size_t)k * HW;
-        const float p = expf(logp[i]);
-        float G = g_logp ? g_logp[i] : 0.0f;
-        G = G + p * ((g_prob ? g_prob[i] : 0.0f) + gd * dc[k]);
-        sum = sum + G;
-    }
-    for (int k = 0; k < D; ++k) {
-        const size_t i = base + (size_t)k * HW;
-        const float p = expf(logp[i]);
-        float G = g_logp ? g_logp[i] : 0.0f;
-        G = G + p * ((g_prob ? g_prob[i] : 0.0f) + gd * dc[k]);
-        g_x[i] = G - p * sum;
-    }
+    dpv_reduce_bwd_pixel(logp, dc, D, HW, g_logp, g_prob, g_depth, g_x);   // (dpv_reduce_body.hpp, shared with dpv_half.hip)
 }
 
 __global__ __launch_bounds__(256) void dpv_expect_bwd_kernel(const float* __restrict__ dpv, const float* __restrict__ dc, int D, int HW,

@@ -1,5 +1,6 @@
 // The wave layout of the kernels that read a [B,D,H,W] volume once and reduce it over D: dpv.hip (log-softmax + expectation),
-// loss.hip (soft-label cross-entropy) and metrics.hip (volume form).  This is the one description of it.
+// dpv_half.hip (the same on fp16 / bf16 logits: a quad is then one 8-byte access), loss.hip (soft-label cross-entropy) and
+// metrics.hip (volume form).  This is the one description of it.
 //
 // A workgroup is 4 waves and covers 256 consecutive pixels of one item (blockIdx.y); a wave covers 64 of them.
 //   lane = (plane group g = lane >> 4, pixel quad q = lane & 15).  A quad is 4 consecutive pixels, one 16-byte access; the 16
@@ -36,6 +37,39 @@ __device__ __forceinline__ float4 load_nt(const float* p) {
 }
 __device__ __forceinline__ void store_nt(float* p, float4 v) {
     __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f*>(p));
+}
+// The 2-byte element types a reduction may read its logits in or write prob / a gradient in (dpv_half.hip); everything between
+// the load and the store is fp32.  Widening is exact; narrowing rounds to nearest-even (overflow to inf, NaN stays NaN): the
+// compiler's conversions, v_cvt_f16_f32 and on gfx950 v_cvt_pk_bf16_f32 (the integer form of the bf16 rounding cost the 8-plane
+// kernel two registers, and with them a wave per SIMD).
+struct f16_t { uint16_t bits; };    // IEEE binary16
+struct bf16_t { uint16_t bits; };   // bfloat16: the upper half of a binary32
+__device__ __forceinline__ float widen(float v) { return v; }
+__device__ __forceinline__ float widen(f16_t h) { return (float)__builtin_bit_cast(_Float16, h.bits); }
+__device__ __forceinline__ float widen(bf16_t h) { return __uint_as_float((uint32_t)h.bits << 16); }
+template <typename T>
+__device__ __forceinline__ T narrow(float v);
+template <>
+__device__ __forceinline__ float narrow<float>(float v) { return v; }
+template <>
+__device__ __forceinline__ f16_t narrow<f16_t>(float v) { return f16_t{__builtin_bit_cast(uint16_t, (_Float16)v)}; }
+template <>
+__device__ __forceinline__ bf16_t narrow<bf16_t>(float v) {
+    return bf16_t{__builtin_bit_cast(uint16_t, (__bf16)v)};
+}
+// a quad of 2-byte elements: one 8-byte non-temporal access (the pointer 8-byte aligned)
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+template <typename T, typename = std::enable_if_t<sizeof(T) == 2>>
+__device__ __forceinline__ float4 load_nt(const T* p) {
+    const v2u t = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p));
+    return make_float4(widen(T{(uint16_t)(t.x & 0xffffu)}), widen(T{(uint16_t)(t.x >> 16)}), widen(T{(uint16_t)(t.y & 0xffffu)}),
+                       widen(T{(uint16_t)(t.y >> 16)}));
+}
+template <typename T, typename = std::enable_if_t<sizeof(T) == 2>>
+__device__ __forceinline__ void store_nt(T* p, float4 v) {
+    const v2u t = {(uint32_t)narrow<T>(v.x).bits | ((uint32_t)narrow<T>(v.y).bits << 16),
+                   (uint32_t)narrow<T>(v.z).bits | ((uint32_t)narrow<T>(v.w).bits << 16)};
+    __builtin_nontemporal_store(t, reinterpret_cast<v2u*>(p));
 }
 __device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
     return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
@@ -90,9 +124,10 @@ __device__ __forceinline__ float4 load_quad(const float* map, const QuadLane& L,
 }
 
 // planes g + 4 (c0 + u), u < N, of the lane's quad [+ the same planes of `add`]; `fill` where there is no such plane to read
-template <int N>
-__device__ __forceinline__ void load_planes(float4 (&v)[N], const float* x, const QuadLane& L, int c0, int D, int HW, float fill,
-                                            bool wanted = true, const float* add = nullptr) {
+// (T: float, or a 2-byte element type widened at the load)
+template <int N, typename T>
+__device__ __forceinline__ void load_planes(float4 (&v)[N], const T* x, const QuadLane& L, int c0, int D, int HW, float fill,
+                                            bool wanted = true, const T* add = nullptr) {
 #pragma unroll
     for (int u = 0; u < N; ++u) {
         const int k = L.g + 4 * (c0 + u);
@@ -135,6 +170,7 @@ __device__ __forceinline__ T wg_sum_get(const T (&s)[4]) {
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // workgroups of 256 pixels per item
 inline int n_blocks(int H, int W) { return (int)(((long long)H * W + 255) / 256); }

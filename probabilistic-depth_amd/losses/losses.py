@@ -55,6 +55,12 @@ class BaseLoss(nn.Module):
         return total, depth
 
     def forward(self, output, target):
+        # fp32 throughout, also when called inside a torch.autocast region: the log-DPVs arrive in fp32, and autocast would hand
+        # the camera products below to the fp32-only kernels in half precision
+        with torch.autocast(output[0]["output"][-1].device.type, enabled=False):
+            return self._forward(output, target)
+
+    def _forward(self, output, target):
         out_l, out_r = output
         tgt_l, tgt_r = target
         mul = self.cfg.loss

@@ -306,7 +306,9 @@ class BaseModel(nn.Module):
                 feats = None       # (any other failure of the native call -- launch error, out of memory -- propagates)
         if feats is None:
             rate = int(flat.shape[3] / feat.shape[3])
-            feats = per_view(torch.cat((feat, F.avg_pool2d(flat, rate)), dim=1))  # [B, V1, C+3, h, w]  (models.py:518-520)
+            # (.float(): under torch.autocast the encoder's maps are fp16 / bf16, the sweep and its backward fp32 only -- a
+            # quarter-resolution tensor; fp32 stays itself)
+            feats = per_view(torch.cat((feat.float(), F.avg_pool2d(flat, rate)), dim=1))  # [B, V1, C+3, h, w]  (models.py:518-520)
         return per_view(half), per_view(raw), feats
 
     def _camera(self, model_input):
@@ -330,7 +332,9 @@ class BaseModel(nn.Module):
         """log-DPV of the cost volume (models.py:555-560); with want_prob also exp(logp) and E[d] from the same pass."""
         x = self.conv0_2(self.conv0_1(self.conv0(cost_volumes)))
         if want_prob:
-            r = ops.dpv_reduce_ex(x, d_candi, want_logp=True, want_prob=True, want_depth=True, inplace=True)
+            # (half logits under torch.autocast: prob in their type, what the decoder's first conv would cast it to anyway)
+            lp = {"prob_dtype": x.dtype} if x.dtype in (torch.float16, torch.bfloat16) else {}
+            r = ops.dpv_reduce_ex(x, d_candi, want_logp=True, want_prob=True, want_depth=True, inplace=True, **lp)
             return r["logp"], r["prob"], r["depth"]
         logp, _ = ops.dpv_reduce(x, d_candi, want_logp=True, want_depth=False, inplace=True)  # models.py:560
         return logp
@@ -348,7 +352,7 @@ class BaseModel(nn.Module):
         cost_volumes = self._sweep(feats, model_input)
         K, poses, rays, cxcy = self._camera(model_input)
         # all views incl. the reference (identity pose), channel i warped with plane i (models.py:613-629)
-        warped = ops.warp_feature(raw, K, poses[:, :, :3, :3], poses[:, :, :3, 3], rays, cxcy, model_input["d_candi"],
+        warped = ops.warp_feature(raw.float(), K, poses[:, :, :3, :3], poses[:, :, :3, 3], rays, cxcy, model_input["d_candi"],
                                   blas=self.sweep_blas)
         BV = self._low_res_dpv(cost_volumes, model_input["d_candi"])
         last = [feats[:, -1, :-3], half[:, -1]]
@@ -386,7 +390,8 @@ class BaseModel(nn.Module):
                 prev = model_input["prev_output"].unsqueeze(1)
             resi = self.based_3d(torch.cat([BV_cur.unsqueeze(1), prev, warped], dim=1), prob=False)
             # log_softmax(BV_cur + BV_resi), its exp for the decoder and E[d] in one pass (models.py:694,:697)
-            r = ops.dpv_reduce_ex(BV_cur, d_candi, addend=resi.contiguous(), want_logp=True, want_prob=True, want_depth=True)
+            # (.float(): BV_cur is an fp32 log-DPV, and under torch.autocast the 3-D convs' residual is not)
+            r = ops.dpv_reduce_ex(BV_cur, d_candi, addend=resi.float().contiguous(), want_logp=True, want_prob=True, want_depth=True)
             BV_upd = r["logp"]
             BV_refined = self.base_decoder(r["prob"], img_features=last, d_candi=d_candi)
             self.last_aux = dict(self.base_decoder.aux or {}, depth_lowres=r["depth"])

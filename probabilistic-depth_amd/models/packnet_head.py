@@ -33,7 +33,8 @@ class PacknetHead(nn.Module):
         flat = rgb.reshape(B * V1, rgb.shape[2], rgb.shape[3], rgb.shape[4])
         feat = self.encoder(flat)
         rate = int(flat.shape[3] / feat.shape[3])
-        both = torch.cat((feat, F.avg_pool2d(flat, rate)), dim=1)
+        # (.float(): under torch.autocast the encoder hands over fp16 / bf16 maps; the sweep is fp32 only)
+        both = torch.cat((feat.float(), F.avg_pool2d(flat.float(), rate)), dim=1)
         return both.view(B, V1, both.shape[1], both.shape[2], both.shape[3])
 
     @torch.no_grad()
@@ -57,6 +58,7 @@ class PacknetHead(nn.Module):
         if src is None:
             if feat_imgs_all is None:
                 feat_imgs_all = self.features(model_input["rgb"])
+            feat_imgs_all = feat_imgs_all.float()   # (precomputed features of an autocast encoder; fp32 stays itself)
             ref, src = feat_imgs_all[:, -1], feat_imgs_all[:, :-1]
             if self.sweep_algo == "auto":   # precomputed features: re-laid once, then the packed entry
                 try:

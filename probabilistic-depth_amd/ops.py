@@ -102,6 +102,8 @@ def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
     """(logp, depth) from logits [B,D,H,W]: log_softmax(dim=1) + dpv_to_depthmap(BV_log=True).
 
     d_candi may be None when only the log-softmax is wanted (want_depth=False).
+    fp16 / bf16 logits (torch.autocast) are widened in the kernel's load: logp and depth are fp32, the gradient comes back in the
+    logits' dtype, and inplace is ignored, the output being another type.
     """
     if d_candi is None:
         if want_depth:
@@ -111,15 +113,20 @@ def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
         dc = d_candi_tensor(d_candi, logits.device)
     if _wants_grad(logits):
         _refuse_grad("dpv_reduce", d_candi=d_candi)
-        out = _DpvReduceFn.apply(logits, None, dc, want_logp, False, want_depth, False, False, False)
+        out = _DpvReduceFn.apply(logits, None, dc, want_logp, False, want_depth, False, False, False, None)
         return out[0], out[2]
     return _native.dpv_reduce(logits, dc, want_logp, want_depth, inplace)
 
 
 def dpv_reduce_ex(logits, d_candi=None, addend=None, want_logp=True, want_prob=False, want_depth=False, want_var=False,
-                  want_quarter=False, inplace=False):
+                  want_quarter=False, inplace=False, prob_dtype=None):
     """One pass over (logits [+ addend]): log_softmax over D and any of exp(logp), E[d], Var[d], the nearest
     quarter-resolution log-DPV (the next frame's prev_output).  Returns a dict with the requested outputs.
+
+    Mixed precision: fp16 / bf16 logits (and an addend of the same dtype; another dtype raises) are widened to fp32 in the
+    kernel's load and every sum is the fp32 one.  The outputs are fp32; prob is fp32 (prob_dtype=None) or, with
+    prob_dtype=logits.dtype, the fp32 value rounded once to that dtype (what a conv under autocast would make of it).  inplace
+    is ignored for half logits: the output is another type.  Gradients come back in the dtype of logits and addend.
 
     models/models.py:694 + :697 (feedback update and decoder input), trainer/default_trainer.py:333-336 (variance),
     :221 (prev_output)."""
@@ -131,9 +138,9 @@ def dpv_reduce_ex(logits, d_candi=None, addend=None, want_logp=True, want_prob=F
         dc = d_candi_tensor(d_candi, logits.device)
     if _wants_grad(logits, addend):
         _refuse_grad("dpv_reduce_ex", d_candi=d_candi)
-        out = _DpvReduceFn.apply(logits, addend, dc, want_logp, want_prob, want_depth, want_var, want_quarter, True)
+        out = _DpvReduceFn.apply(logits, addend, dc, want_logp, want_prob, want_depth, want_var, want_quarter, True, prob_dtype)
         return {k: v for k, v in zip(("logp", "prob", "depth", "var", "quarter"), out) if v is not None}
-    return _native.dpv_reduce_ex(logits, dc, addend, want_logp, want_prob, want_depth, want_var, want_quarter, inplace)
+    return _native.dpv_reduce_ex(logits, dc, addend, want_logp, want_prob, want_depth, want_var, want_quarter, inplace, prob_dtype)
 
 
 def ufield(dpv, d_candi, intr, mask=None, BV_log=True, unc_ang=5, z_start=0.6, z_end=0.9, min_depth=0.0, quash=False):
@@ -397,13 +404,16 @@ class _SweepFn(torch.autograd.Function):
 
 class _DpvReduceFn(torch.autograd.Function):
     """dpv_reduce / dpv_reduce_ex under autograd: (logp, prob, depth, var, quarter), each None unless requested; var and
-    quarter (the next frame's prev_output) are not differentiable.  inplace is not honoured: the outputs are new tensors."""
+    quarter (the next frame's prev_output) are not differentiable.  inplace is not honoured: the outputs are new tensors.
+    Half-precision logits: the saved logp is fp32, the gradient of logits and addend is stored in their dtype by the backward
+    kernel, and a g_prob of prob's half dtype is read as it is."""
 
     @staticmethod
-    def forward(ctx, logits, addend, dc, want_logp, want_prob, want_depth, want_var, want_quarter, ex):
+    def forward(ctx, logits, addend, dc, want_logp, want_prob, want_depth, want_var, want_quarter, ex, prob_dtype):
         ctx.set_materialize_grads(False)
+        ctx.in_dtype = logits.dtype
         if ex:   # (the forward of the public function that was called: dpv_reduce_ex or dpv_reduce)
-            out = _native.dpv_reduce_ex(logits, dc, addend, True, want_prob, want_depth, want_var, want_quarter, False)
+            out = _native.dpv_reduce_ex(logits, dc, addend, True, want_prob, want_depth, want_var, want_quarter, False, prob_dtype)
         else:
             lp, dep = _native.dpv_reduce(logits, dc, True, want_depth, False)
             out = {"logp": lp} if dep is None else {"logp": lp, "depth": dep}
@@ -420,8 +430,11 @@ class _DpvReduceFn(torch.autograd.Function):
         logp, dc = ctx.saved_tensors
         g = None
         if g_logp is not None or g_prob is not None or g_depth is not None:
-            g = _native.dpv_reduce_backward(logp, dc, g_logp=g_logp, g_prob=g_prob, g_depth=g_depth)
-        return (g if ctx.needs_input_grad[0] else None, g if ctx.needs_input_grad[1] else None) + (None,) * 7
+            if ctx.in_dtype == torch.float32:
+                g = _native.dpv_reduce_backward(logp, dc, g_logp=g_logp, g_prob=g_prob, g_depth=g_depth)
+            else:
+                g = _native.dpv_reduce_backward_lp(logp, dc, ctx.in_dtype, g_logp=g_logp, g_prob=g_prob, g_depth=g_depth)
+        return (g if ctx.needs_input_grad[0] else None, g if ctx.needs_input_grad[1] else None) + (None,) * 8
 
 
 class _DpvFuseFn(torch.autograd.Function):
