@@ -24,6 +24,7 @@ import pdepth_amd  # noqa: F401
 from pdepth_amd import _native, ops, synth
 from util import to_dev
 import util_dpv_backward as U
+import util_dpv_forward as UF
 
 pytestmark = pytest.mark.gpu
 
@@ -97,11 +98,15 @@ def test_non_finite_inputs_stay_in_their_pixel(dev):
 
 
 # ---- the wiring, bit for bit -----------------------------------------------------------------------------------------------
-def _check_forward(logp, x0, a0=None):
-    """The forward's logp against the float64 log-softmax, at the tolerance of tests/test_ops_fuzz.py."""
-    z = x0.double().cpu() if a0 is None else x0.double().cpu() + a0.double().cpu()
-    assert float((logp.detach().double().cpu() - U.logp64(x0.cpu(), None if a0 is None else a0.cpu())).abs().max()) \
-        < 3e-5 * max(1.0, float(z.abs().max()) / 10)
+def _check_forward(logp, idx, op, a0=None):
+    """The forward's logp against the float64 log-softmax of the float32 input (logits + addend formed in float32): every element
+    inside the per-element bound of tests/util_dpv_forward.py, in the summation order the dispatch gives `op` on this shape."""
+    r = UF.reference(idx, "randn3", a0 is not None)
+    if a0 is not None:
+        assert torch.equal(a0.cpu(), UF.addend(idx))
+    E = UF.bound(idx, "randn3", a0 is not None, UF.order_of(op, U.CASES[idx]))
+    w = UF.worst(logp, r["f"]["logp"], E["logp"])
+    assert w <= 1.0, (U.CASE_IDS[idx], op, w)
 
 
 @pytest.mark.parametrize("idx", IDX, ids=U.CASE_IDS)
@@ -119,7 +124,7 @@ def test_reduce_wiring_is_the_native_call(dev, idx):
         sum((r[k] * g[k]).sum() for k in names).backward()
         assert torch.equal(x.grad, bwd(r["logp"], **{"g_" + k: g[k] for k in names})), used
         assert torch.equal(x.detach(), x0)   # inplace under autograd leaves the input untouched
-        _check_forward(r["logp"], x0)
+        _check_forward(r["logp"], idx, "reduce_ex")
     for used in ((True, False), (False, True), (True, True)):
         names = [k for k, on in zip(("logp", "depth"), used) if on]
         x = x0.clone().requires_grad_(True)
@@ -127,7 +132,7 @@ def test_reduce_wiring_is_the_native_call(dev, idx):
         sum(({"logp": logp, "depth": depth}[k] * g[k]).sum() for k in names).backward()
         assert torch.equal(x.grad, bwd(logp, **{"g_" + k: g[k] for k in names})), used
         assert torch.equal(x.detach(), x0)
-        _check_forward(logp, x0)
+        _check_forward(logp, idx, "reduce")
     # want_logp=False with the depth used: the Function keeps the logp it does not return
     x = x0.clone().requires_grad_(True)
     none, depth = ops.dpv_reduce(x, dc, want_logp=False, want_depth=True)
@@ -171,7 +176,7 @@ def test_addend_wiring(dev, idx):
         assert (x.grad is not None) == gx and (a.grad is not None) == ga
         for got in (x.grad, a.grad):
             assert got is None or torch.equal(got, want), (gx, ga)
-        _check_forward(r["logp"], x0, a0)
+        _check_forward(r["logp"], idx, "reduce_ex", a0)
         with torch.no_grad():
             assert torch.equal(r["logp"].detach(), ops.dpv_reduce_ex(x0, dc, addend=a0)["logp"])
 
