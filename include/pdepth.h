@@ -60,7 +60,8 @@ extern "C" {
                                 *    pdepth_dpv_soft_ce_backward_f32; pdepth_depth_metrics_workspace_bytes, pdepth_depth_metrics_f32;
                                 *    pdepth_dpv_fuse_backward_f32; pdepth_lidar_depth_workspace_bytes, pdepth_lidar_depth_f32;
                                 *    pdepth_loss_terms_workspace_bytes, pdepth_loss_{dsc,rsc,dc,smooth}_f32 and their _backward_f32;
-                                *    PDEPTH_DTYPE_F16 / PDEPTH_DTYPE_BF16, pdepth_dpv_reduce_ex_lp, pdepth_dpv_reduce_backward_lp */
+                                *    PDEPTH_DTYPE_F16 / PDEPTH_DTYPE_BF16, pdepth_dpv_reduce_ex_lp, pdepth_dpv_reduce_backward_lp;
+                                *    pdepth_det_scale_exponent and the three _backward_det_f32 entries with their _det_workspace_bytes */
 
 enum {
     PDEPTH_OK = 0,
@@ -426,7 +427,7 @@ int pdepth_inverse_warp_backward_f32(const float *img, const float *depth, const
  *   grad_cost [B,D,H,W] contiguous;
  *   grad_ref  [B,C,H,W] contiguous or NULL: a per-pixel gather, no atomics, bitwise reproducible;
  *   grad_src  [B,V,C,H,W] contiguous or NULL: zeroed on the stream, then scattered with float atomics (summed per workgroup
- *             in LDS first); the last bits depend on the order in which the adds arrive.
+ *             in LDS first); the last bits depend on the order in which the adds arrive (pdepth_sweep_backward_det_f32: they do not).
  * At least one output must be non-NULL.  Taps outside the image receive nothing (ATen's grid_sampler_2d backward).
  */
 int pdepth_sweep_backward_f32(const pdepth_sweep_desc *desc, const pdepth_camera *cam, const float *ref, const float *src,
@@ -622,6 +623,65 @@ int pdepth_loss_smooth_f32(const float *depth, const float *rgb, int32_t B, int3
                            size_t workspace_bytes, void *stream);
 int pdepth_loss_smooth_backward_f32(const float *depth, const float *rgb, const float *g_value, int32_t B, int32_t H, int32_t W,
                                     float *g_depth, void *stream);
+
+/*
+ * Deterministic backward: the three scattered gradients as order-independent sums.
+ *
+ * grad_src of pdepth_sweep_backward_f32, g_src_depth of pdepth_loss_dsc_backward_f32 and grad_img of
+ * pdepth_inverse_warp_backward_f32 are sums of contributions that arrive in an order the hardware chooses; with float atomics
+ * their last bits differ from call to call.  The _det entries below form the same contributions q_i (the same fp32 expressions
+ * in the same order as the entries they stand beside) and sum them exactly, as integers:
+ *     g[t] = fl32(2^-S_b sum_i rn(2^S_b q_i)),     rn: to the nearest integer, ties to even; the product is exact (formed in double)
+ * added with 64-bit integer atomics into an accumulator in the workspace and converted by a last pass.  The result depends only
+ * on the multiset of contributions: two calls give the same bits, and so do two builds that stage or group the adds differently.
+ *
+ * The scale: S_b is chosen per batch item b, on the device (no read-back, no host synchronisation), so an item's result does not
+ * depend on the other items of the batch.  With M_b a bound of |q_i| over the item and N the largest number of contributions one
+ * destination can receive, S_b = pdepth_det_scale_exponent(M_b, N): the integer with N 2 M_b 2^S_b <= 2^62 (no overflow of the
+ * int64, roundings included) and N M_b 2^S_b > 2^58 (at most 3 of the 62 bits unused); every contribution is thus rounded at
+ * 2^-59 N M_b or finer.
+ *   sweep:  N = D H W (per view a (plane, pixel) sample puts at most one tap, of weight <= 1, on a texel);
+ *           M_b = |gscale| max|grad_cost[b]| E_b, gscale = 2 / sigma (L2), 1 / sigma (L1), E_b = max|src[b]| + max|ref[b]| (L2), 1 (L1),
+ *           the maxima from a pre-pass over the item's inputs;
+ *   dsc, inverse_warp:  N = 4 H W (pixels x taps); M_b = the exact maximum of |q_i|, from a first run of the per-pixel chain.
+ * M_b == 0: the item's gradient is exactly 0.
+ * Non-finite: if M_b is NaN or infinite -- a NaN or an infinity among the inputs that enter it --, or overflows (the sweep: M_b or
+ * one of its factors |gscale| max|grad_cost[b]|, E_b at or above 2^127, where the fp32 chain may leave the finite range), EVERY
+ * element of that item's scattered gradient is NaN, and every other item is untouched.  This departs on purpose from the atomic
+ * entries, which confine a NaN to the texels it reaches: an integer accumulator cannot hold a NaN, and a non-finite gradient
+ * anywhere in an item is what an overflow check of a loss scaler looks for.
+ * Conversion: int64 -> double (exact below 2^53, else one rounding to nearest), times 2^-S_b (exact), double -> fp32 (one rounding
+ * to nearest): at most two roundings, always the same instruction sequence.
+ * The gradients written per owner (grad_ref, g_tgt_depth, grad_point) come from the kernels of the atomic entries and have the
+ * same bits as theirs.
+ *
+ * Workspace (256-byte aligned; needed when the scattered gradient is requested; cleared by the call):
+ *   sweep         roundup256(16 B) + roundup256(8 B V C H W) bytes: B = 4, V = 1, C = 67: 17.6 MB at 64 x 128, 281 MB at 256 x 512;
+ *   dsc           roundup256(4 B)  + roundup256(8 B H W);
+ *   inverse_warp  roundup256(4 B)  + roundup256(8 B C H W).
+ * The queries return 0 for sizes out of range.  A workspace that is missing, too small or misaligned is PDEPTH_E_WORKSPACE.
+ *
+ * pdepth_det_scale_exponent(bound, n): the exponent rule itself, a host function (the kernels call the same inline code): S for
+ * a finite bound > 0 (denormals included) and n >= 1; PDEPTH_DET_EXP_ZERO for bound == 0; PDEPTH_DET_EXP_NONFINITE for a NaN or
+ * infinite bound (or n < 1).
+ * Every other argument, check and message: as the entry without _det.
+ */
+#define PDEPTH_DET_EXP_ZERO (-2147483647 - 1)
+#define PDEPTH_DET_EXP_NONFINITE 2147483647
+int32_t pdepth_det_scale_exponent(float bound, int64_t n);
+size_t pdepth_sweep_backward_det_workspace_bytes(const pdepth_sweep_desc *desc);
+int pdepth_sweep_backward_det_f32(const pdepth_sweep_desc *desc, const pdepth_camera *cam, const float *ref, const float *src,
+                                  const float *d_candi, const float *grad_cost, float *grad_ref, float *grad_src, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+size_t pdepth_loss_dsc_backward_det_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_loss_dsc_backward_det_f32(const float *src_depth, const float *tgt_depth, const float *src_mask, const float *Kinv,
+                                     const float *proj, const float *pose_row, int32_t pose_batched, const float *intr,
+                                     const float *count, const float *g_value, int32_t B, int32_t H, int32_t W, float *g_src_depth,
+                                     float *g_tgt_depth, void *workspace, size_t workspace_bytes, void *stream);
+size_t pdepth_inverse_warp_backward_det_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int pdepth_inverse_warp_backward_det_f32(const float *img, const float *depth, const float *Kinv, const float *proj,
+                                         const float *grad_out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t mode,
+                                         float *grad_img, float *grad_point, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ LAYOUT_NONE, LAYOUT_C4, LAYOUT_DIST16 = 0, 1, 3   # (2: a retired layout; pdepth
 # workspace ints behind the tile flags that the diagnostics below read (csrc/sweep_workspace.hpp; tests/test_capi_symbols.py compares them)
 NONCENTRED_SLOT, LAYOUT_SLOT, DIST_DIRECT_LAST_SLOT, DIST_NONCE_SLOT = 51, 56, 59, 60
 BLAS_FMA, BLAS_SEPARATE = 0, 1
+DET_EXP_ZERO, DET_EXP_NONFINITE = -2 ** 31, 2 ** 31 - 1   # what pdepth_det_scale_exponent answers for a zero / non-finite bound
 
 class SweepDesc(Structure):
     _fields_ = [
@@ -87,12 +88,21 @@ _SIGNATURES = {
     "pdepth_loss_dc_backward_f32": (c_int, [_P] * 4 + [_I] * 3 + [_P] * 3),
     "pdepth_loss_smooth_f32": (c_int, [_P] * 2 + [_I] * 3 + [_P] * 2 + [_Z, _P]),
     "pdepth_loss_smooth_backward_f32": (c_int, [_P] * 3 + [_I] * 3 + [_P] * 2),
+    "pdepth_det_scale_exponent": (c_int32, [_F, c_int64]),
+    "pdepth_sweep_backward_det_workspace_bytes": (_Z, [_DESC]),
+    "pdepth_sweep_backward_det_f32": (c_int, [_DESC, _CAM] + [_P] * 7 + [_Z, _P]),
+    "pdepth_loss_dsc_backward_det_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_loss_dsc_backward_det_f32": (c_int, [_P] * 6 + [_I] + [_P] * 3 + [_I] * 3 + [_P] * 3 + [_Z, _P]),
+    "pdepth_inverse_warp_backward_det_workspace_bytes": (_Z, [_I] * 4),
+    "pdepth_inverse_warp_backward_det_f32": (c_int, [_P] * 5 + [_I] * 5 + [_P] * 3 + [_Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, loss-term, metrics, fusion-backward and LiDAR entries live in objects of their own: part of an entry's name -> the source file.  The
+# The loss, loss-term, metrics, fusion-backward, LiDAR and deterministic-backward entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
-_SOURCE_OF_ENTRY = {"_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
+_SOURCE_OF_ENTRY = {"_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
+                    "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
+                    "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
 _ABSENT_FROM_EXPERIMENT_LIBS = tuple(n for n in _SIGNATURES if any(part in n for part in _SOURCE_OF_ENTRY))
@@ -777,8 +787,14 @@ def inverse_warp(img, depth, Kinv, proj, mode="bilinear"):
     return out, valid.bool()
 
 
-def inverse_warp_backward(img, depth, Kinv, proj, grad_out, mode="bilinear", want_img=True, want_point=True):
-    """-> (grad_img [B,C,H,W] | None, grad_point [B,3,H,W] | None): pdepth_inverse_warp_backward_f32."""
+def _det_workspace(nbytes, dev):
+    """The workspace of a deterministic backward (the int64 accumulator + the per-item header), or (None, 0)."""
+    return (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes) if nbytes else (None, 0)
+
+
+def inverse_warp_backward(img, depth, Kinv, proj, grad_out, mode="bilinear", want_img=True, want_point=True, deterministic=False):
+    """-> (grad_img [B,C,H,W] | None, grad_point [B,3,H,W] | None): pdepth_inverse_warp_backward_f32; deterministic:
+    pdepth_inverse_warp_backward_det_f32 (grad_img as an order-independent sum; grad_point has the same bits either way)."""
     lib = load()
     img, depth, Kinv, proj, grad_out = (t.contiguous() for t in (img, depth, Kinv, proj, grad_out))
     B, C, H, W = img.shape
@@ -786,11 +802,15 @@ def inverse_warp_backward(img, depth, Kinv, proj, grad_out, mode="bilinear", wan
         raise RuntimeError("inverse_warp_backward: grad_out must have the shape of img")
     g_img = torch.empty_like(img) if want_img else None
     g_pt = torch.empty((B, 3, H, W), dtype=torch.float32, device=img.device) if want_point else None
+    args = (_dev(img, "img"), _dev(depth, "depth"), _dev(Kinv, "Kinv"), _dev(proj, "proj"), _dev(grad_out, "grad_out"), B, C, H, W,
+            SAMPLE_MODES[mode], g_img.data_ptr() if want_img else None, g_pt.data_ptr() if want_point else None)
     with torch.cuda.device(img.device):
-        rc = lib.pdepth_inverse_warp_backward_f32(_dev(img, "img"), _dev(depth, "depth"), _dev(Kinv, "Kinv"), _dev(proj, "proj"),
-                                                  _dev(grad_out, "grad_out"), B, C, H, W, SAMPLE_MODES[mode],
-                                                  g_img.data_ptr() if want_img else None,
-                                                  g_pt.data_ptr() if want_point else None, _stream(img.device))
+        if deterministic:
+            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_inverse_warp_backward_det_workspace_bytes")(B, C, H, W) if want_img else 0,
+                                          img.device)
+            rc = _entry(lib, "pdepth_inverse_warp_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(img.device))
+        else:
+            rc = lib.pdepth_inverse_warp_backward_f32(*args, _stream(img.device))
     _check(rc, lib)
     return g_img, g_pt
 
@@ -802,10 +822,12 @@ def _shape(t, shape, name, who):
 
 
 def sweep_backward(ref, src, K, R, t, rays, cxcy, d_candi, grad_cost, sigma, metric=METRIC_L2, want_ref=True, want_src=True,
-                   blas_mode=None):
+                   blas_mode=None, deterministic=False):
     """grad_cost [B,D,H,W] -> (grad_ref [B,C,H,W] | None, grad_src [B,V,C,H,W] | None): pdepth_sweep_backward_f32.
     ref / src / camera as sweep() (NCHW source only).  grad_ref is reproducible bit for bit; grad_src is summed with float
-    atomics (last bits depend on the order of arrival)."""
+    atomics (last bits depend on the order of arrival) unless deterministic: pdepth_sweep_backward_det_f32 sums it as 64-bit
+    integers in a workspace of 8 bytes per element, allocated here -- the same bits from call to call (a non-finite input makes
+    that item's grad_src NaN throughout: include/pdepth.h)."""
     who = "sweep_backward"
     if not (want_ref or want_src):
         raise RuntimeError(f"{who}: no output requested")
@@ -826,10 +848,14 @@ def sweep_backward(ref, src, K, R, t, rays, cxcy, d_candi, grad_cost, sigma, met
     g_ref = torch.empty_like(ref) if want_ref else None
     g_src = torch.empty_like(src) if want_src else None
     dev = ref.device
+    args = (ctypes.byref(desc), ctypes.byref(cam), ref.data_ptr(), src.data_ptr(), d_candi.data_ptr(), grad_cost.data_ptr(),
+            g_ref.data_ptr() if want_ref else None, g_src.data_ptr() if want_src else None)
     with _on_device(dev):
-        rc = lib.pdepth_sweep_backward_f32(ctypes.byref(desc), ctypes.byref(cam), ref.data_ptr(), src.data_ptr(), d_candi.data_ptr(),
-                                           grad_cost.data_ptr(), g_ref.data_ptr() if want_ref else None,
-                                           g_src.data_ptr() if want_src else None, _stream(dev))
+        if deterministic:
+            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_sweep_backward_det_workspace_bytes")(ctypes.byref(desc)) if want_src else 0, dev)
+            rc = _entry(lib, "pdepth_sweep_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
+        else:
+            rc = lib.pdepth_sweep_backward_f32(*args, _stream(dev))
     _check(rc, lib)
     del keep
     return g_ref, g_src
@@ -1074,8 +1100,10 @@ def loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
     return out[0], out[1]
 
 
-def loss_dsc_backward(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, count, g_value, want_src=True, want_tgt=True):
-    """-> (g_src_depth | None, g_tgt_depth | None), each [B,H,W]: pdepth_loss_dsc_backward_f32."""
+def loss_dsc_backward(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, count, g_value, want_src=True, want_tgt=True,
+                      deterministic=False):
+    """-> (g_src_depth | None, g_tgt_depth | None), each [B,H,W]: pdepth_loss_dsc_backward_f32; deterministic:
+    pdepth_loss_dsc_backward_det_f32 (g_src_depth as an order-independent sum; g_tgt_depth has the same bits either way)."""
     who = "loss_dsc_backward"
     (B, H, W), batched, t = _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
     _shape(count, (B,), "count", who)
@@ -1085,9 +1113,13 @@ def loss_dsc_backward(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr
     dev = t[0].device
     g_src = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_src else None
     g_tgt = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_tgt else None
+    args = (*(x.data_ptr() for x in t[:6]), batched, t[6].data_ptr(), count.data_ptr(), g_value.data_ptr(), B, H, W, _ptr(g_src), _ptr(g_tgt))
     with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_dsc_backward_f32")(*(x.data_ptr() for x in t[:6]), batched, t[6].data_ptr(), count.data_ptr(),
-                                                         g_value.data_ptr(), B, H, W, _ptr(g_src), _ptr(g_tgt), _stream(dev))
+        if deterministic:
+            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_loss_dsc_backward_det_workspace_bytes")(B, H, W) if want_src else 0, dev)
+            rc = _entry(lib, "pdepth_loss_dsc_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
+        else:
+            rc = _entry(lib, "pdepth_loss_dsc_backward_f32")(*args, _stream(dev))
     _check(rc, lib)
     return g_src, g_tgt
 

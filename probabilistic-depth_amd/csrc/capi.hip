@@ -14,46 +14,11 @@ using namespace pdepth::capi;
 
 thread_local char g_err[512] = "";
 
-// every dimension positive of a descriptor
-bool dims_positive(const pdepth_sweep_desc* d) { return d->B > 0 && d->V > 0 && d->C > 0 && d->D > 0 && d->H > 0 && d->W > 0; }
-int check_desc_dims(const char* who, const pdepth_sweep_desc* d) {
-    if (dims_positive(d)) return PDEPTH_OK;
-    return fail(PDEPTH_E_ARG, "%s: non-positive dimension B=%d V=%d C=%d D=%d H=%d W=%d", who, d->B, d->V, d->C, d->D, d->H, d->W);
-}
 size_t workspace_bytes_of(const pdepth_sweep_desc* d) { return pdepth::sweep_workspace_bytes(d->B, d->V, d->C, d->H, d->W); }
 // a sweep workspace: present, large enough, 256-byte aligned
 int check_sweep_workspace(const char* who, const pdepth_sweep_desc* d, const void* workspace, size_t bytes) {
     return check_workspace(who, workspace, bytes, workspace_bytes_of(d),
                            "; query pdepth_sweep_workspace_bytes()");
-}
-
-int check_desc(const pdepth_sweep_desc* d, const pdepth_camera* cam, const char* who) {
-    if (!d || !cam) return fail(PDEPTH_E_ARG, "%s: null descriptor", who);
-    if (int rc = check_desc_dims(who, d)) return rc;
-    if ((long long)d->H * d->W > (1ll << 30))
-        return fail(PDEPTH_E_ARG, "%s: H*W too large", who);
-    if (!cam->K || !cam->R || !cam->t || !cam->rays || !cam->cxcy)
-        return fail(PDEPTH_E_ARG, "%s: null camera pointer", who);
-    if (d->blas_mode != PDEPTH_BLAS_FMA && d->blas_mode != PDEPTH_BLAS_SEPARATE)
-        return fail(PDEPTH_E_ARG, "%s: unknown blas_mode %d", who, d->blas_mode);
-    const long long chw = (long long)d->C * d->H * d->W;
-    if (d->src_vstride < chw || d->src_bstride < 0 || d->ref_bstride < 0)
-        return fail(PDEPTH_E_ARG, "%s: bad strides", who);
-    return PDEPTH_OK;
-}
-
-// the one place a SweepArgs is filled from a descriptor (cam == nullptr: the entries that launch no sampling kernel)
-pdepth::SweepArgs make_args(const pdepth_sweep_desc* d, const pdepth_camera* cam = nullptr, const float* ref = nullptr,
-                            const float* src = nullptr, const float* d_candi = nullptr) {
-    pdepth::SweepArgs a{};
-    a.ref = ref; a.src = src; a.packed_src = nullptr;
-    if (cam) { a.K = cam->K; a.R = cam->R; a.t = cam->t; a.rays = cam->rays; a.cxcy = cam->cxcy; }
-    a.d_candi = d_candi;
-    a.B = d->B; a.V = d->V; a.C = d->C; a.D = d->D; a.H = d->H; a.W = d->W;
-    a.metric = d->metric; a.sigma = d->sigma; a.blas_mode = d->blas_mode;
-    a.fast_div = d->algo != PDEPTH_ALGO_DIRECT;
-    a.ref_bstride = d->ref_bstride; a.src_bstride = d->src_bstride; a.src_vstride = d->src_vstride;
-    return a;
 }
 
 }  // namespace
@@ -425,18 +390,7 @@ int pdepth_inverse_warp_backward_f32(const float* img, const float* depth, const
 int pdepth_sweep_backward_f32(const pdepth_sweep_desc* desc, const pdepth_camera* cam, const float* ref, const float* src,
                               const float* d_candi, const float* grad_cost, float* grad_ref, float* grad_src, void* stream) {
     const char* who = "pdepth_sweep_backward_f32";
-    if (int rc = check_desc(desc, cam, who)) return rc;
-    if (!ref || !src || !d_candi || !grad_cost) return fail(PDEPTH_E_ARG, "%s: null input pointer", who);
-    if (!grad_ref && !grad_src) return fail(PDEPTH_E_ARG, "%s: no output requested", who);
-    if (desc->metric != PDEPTH_METRIC_L2 && desc->metric != PDEPTH_METRIC_L1)
-        return fail(PDEPTH_E_ARG, "%s: undefined metric for feature distance (%d)", who, desc->metric);
-    if (!(desc->sigma > 0.0f) && !(desc->sigma < 0.0f)) return fail(PDEPTH_E_ARG, "%s: sigma must be non-zero", who);
-    if (desc->D > 512) return fail(PDEPTH_E_ARG, "%s: D=%d exceeds the 512 planes one launch supports", who, desc->D);
-    if ((long long)desc->C * desc->H * desc->W >= (1ll << 31) || desc->B > 65535)
-        return fail(PDEPTH_E_ARG, "%s: C*H*W must be below 2^31 and B at most 65535", who);
-    if ((const void*)grad_ref == (const void*)grad_src || (const float*)grad_ref == ref || (const float*)grad_src == src ||
-        (const float*)grad_ref == grad_cost || (const float*)grad_src == grad_cost)
-        return fail(PDEPTH_E_ARG, "%s: the outputs may not alias each other or an input", who);
+    if (int rc = check_sweep_backward(who, desc, cam, ref, src, d_candi, grad_cost, grad_ref, grad_src)) return rc;
     pdepth::SweepArgs a = make_args(desc, cam, ref, src, d_candi);
     a.fast_div = 0;
     return launched(pdepth::launch_sweep_backward(a, grad_cost, grad_ref, grad_src, (hipStream_t)stream), who);

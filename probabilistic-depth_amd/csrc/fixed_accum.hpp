@@ -1,0 +1,70 @@
+// Order-independent sums of fp32 contributions: exact integer accumulation (sweep_bwd_det.hip, scatter_det.hip).
+//
+// Float addition is not associative, integer addition is.  A contribution q (fp32) is scaled by 2^S (exact: the product is
+// formed in double, whose exponent range holds every fp32 times every 2^S chosen below), rounded to the nearest integer, ties to
+// even, and added to a 64-bit integer with an integer atomic; a last pass converts the sum back:
+//     g = fl32(2^-S * sum_i rn(2^S q_i))
+// The result depends on the multiset of the q_i alone -- not on the order of arrival, the scheduling of workgroups or the way
+// a kernel stages its adds.
+//
+// The exponent S is chosen per batch item from a bound M >= |q_i| and the largest number n of contributions one destination
+// can receive (det_scale_exponent): n 2 M 2^S <= 2^62, so the sum stays below 2^62 + n / 2 even when every rounding goes
+// up and M is a few ulp short, and n M 2^S > 2^58: at most 3 bits of the 62 are wasted.  A destination's absolute error
+// is at most n_actual / 2 units of 2^-S, i.e. below 2^-59 n M per contribution actually added.
+//
+// Conversion (det_to_float): int64 -> double (exact below 2^53, otherwise one rounding to nearest), times 2^-S (exact),
+// double -> fp32 (one rounding to nearest): at most two roundings, one fixed instruction sequence.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace pdepth {
+namespace fixed {
+
+// the two answers of det_scale_exponent that are no exponent (every exponent lies in [-200, 300])
+constexpr int32_t EXP_ZERO = INT32_MIN;        // bound == 0: every contribution is 0
+constexpr int32_t EXP_NONFINITE = INT32_MAX;   // bound is NaN or infinite
+
+__host__ __device__ inline uint32_t float_bits(float x) {
+    union { float f; uint32_t u; } v;
+    v.f = x;
+    return v.u;
+}
+
+// S with n 2 bound 2^S <= 2^62 < 16 n bound 2^S, for a finite bound > 0 (denormals included) and n >= 1; integer arithmetic on
+// the bit pattern of the bound only: the host and the device give the same answer.
+//   bound < 2^em, bound >= 2^(em - 1);  n <= 2^en, n > 2^(en - 1)  =>  S = 61 - em - en: n 2 bound 2^S <= 2^62, n bound 2^S > 2^59
+__host__ __device__ inline int32_t det_scale_exponent(float bound, int64_t n) {
+    const uint32_t bits = float_bits(bound) & 0x7fffffffu;
+    if (bits == 0u) return EXP_ZERO;
+    if (bits >= 0x7f800000u) return EXP_NONFINITE;
+    const int field = (int)(bits >> 23);
+    const int em = field != 0 ? field - 126 : (32 - __builtin_clz(bits)) - 149;   // (field 0: bits is the mantissa, bound = bits 2^-149)
+    const int en = n > 1 ? 64 - __builtin_clzll((unsigned long long)(n - 1)) : 0;
+    return 61 - em - en;
+}
+
+// |x| as an unsigned integer: ordered like |x| for finite values, every infinity above them and every NaN above the infinities --
+// a maximum over these (atomicMax) is order-independent and a NaN or infinity anywhere wins it
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+__device__ __forceinline__ bool bits_finite(uint32_t abs_bits_of_x) { return abs_bits_of_x < 0x7f800000u; }
+
+// maximum of v over the 64 lanes of a wave (every lane calls; dead lanes pass 0)
+__device__ __forceinline__ uint32_t wave_max_bits(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
+}
+
+// rn(2^S q): the product is exact in double, the rounding is to nearest, ties to even
+__device__ __forceinline__ long long det_quantise(float q, int S) { return (long long)__builtin_rint(__builtin_ldexp((double)q, S)); }
+
+// quantise and add: one ds_add_u64 on LDS, one global_atomic_add_x2 on global memory (two's complement: unsigned adds)
+__device__ __forceinline__ void det_add(unsigned long long* dst, float q, int S) { atomicAdd(dst, (unsigned long long)det_quantise(q, S)); }
+
+// the sum back in fp32 (two roundings at most, see above)
+__device__ __forceinline__ float det_to_float(long long acc, int S) { return (float)__builtin_ldexp((double)acc, -S); }
+
+}  // namespace fixed
+}  // namespace pdepth

@@ -36,17 +36,11 @@
 #include "dpv_lanes.hpp"
 #include "inverse_warp_math.hpp"
 #include "kernels.hpp"
+#include "loss_terms_math.hpp"
 
 namespace pdepth {
 
 namespace {
-
-constexpr float FLOOR = 1e-3f;   // the clamp of every depth that enters a quotient
-
-// torch.clamp(min=lo) / torch.clamp(0, 1): a NaN stays a NaN
-__device__ __forceinline__ float clamp_min(float x, float lo) { return x < lo ? lo : x; }
-__device__ __forceinline__ float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
-__device__ __forceinline__ float sign0(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }   // (NaN: 0)
 
 // two sums of a workgroup -> its slots of the workspace ([2][B][nblk])
 __device__ __forceinline__ void block_partial(float s0, float s1, float* __restrict__ part, int nitems) {
@@ -62,76 +56,7 @@ __device__ __forceinline__ void block_partial(float s0, float s1, float* __restr
     }
 }
 
-// the relative difference clamp(|a - b| / |a + b|, 0, 1) and its two partial derivatives
-struct RelDiff {
-    float n, dd, q, diff;
-};
-__device__ __forceinline__ RelDiff rel_diff(float a, float b) {
-    RelDiff r;
-    r.n = fabsf(a - b);
-    r.dd = fabsf(a + b);
-    r.q = r.n / r.dd;
-    r.diff = clamp01(r.q);
-    return r;
-}
-// gd = dL / d diff -> (dL / da, dL / db)
-__device__ __forceinline__ void rel_diff_grad(const RelDiff& r, float a, float b, float gd, float& ga, float& gb) {
-    const float gq = (r.q >= 0.0f && r.q <= 1.0f) ? gd : 0.0f;
-    const float gn = gq / r.dd;
-    const float gdd = -gq * r.n / (r.dd * r.dd);
-    const float s1 = sign0(a - b), s2 = sign0(a + b);
-    ga = gn * s1 + gdd * s2;
-    gb = gdd * s2 - gn * s1;
-}
-
-// ---- depth stereo consistency ---------------------------------------------------------------------------------------------------
-struct DscArgs {
-    const float* src;      // [B,H,W] source depth
-    const float* tgt;      // [B,H,W] target depth
-    const float* smask;    // [B,H,W] source mask
-    const float* Kinv;     // [B,3,3]
-    const float* proj;     // [B,3,4]
-    const float* row;      // [B,4] | [1,4]: third row of the source-to-target pose
-    const float* intr;     // [B,3,3]
-    int row_stride;        // 4 | 0
-    int H, W;
-};
-
-struct DscPixel {
-    float m, tgt_m, got_m, a, b;
-    int tap;
-    float dmoved;          // d warped / d src[tap] (the source mask and the clamp's pass included); 0 without a tap
-};
-
-__device__ __forceinline__ DscPixel dsc_pixel(const DscArgs& g, int b, int pix) {
-    const int H = g.H, W = g.W, HW = H * W;
-    const int y = pix / W, x = pix - y * W;
-    const float t = g.tgt[(size_t)b * HW + pix];
-    const WarpSample q = warp_sample(g.Kinv + b * 9, g.proj + b * 12, x, y, t, H, W);
-    DscPixel p;
-    p.tap = nearest_tap(q, H, W);
-    float warped = 0.0f;
-    p.dmoved = 0.0f;
-    if (p.tap >= 0) {
-        // transform_dmap (utils/inverse_warp.py:212-253) of the source depth at the tap, times the source mask
-        const float* K = g.intr + b * 9;
-        const float* P = g.row + (size_t)b * g.row_stride;
-        const int ty = p.tap / W, tx = p.tap - ty * W;
-        const float xs = ((float)tx - K[2]) / K[0], ys = ((float)ty - K[5]) / K[4];
-        const float zr = g.src[(size_t)b * HW + p.tap], sm = g.smask[(size_t)b * HW + p.tap];
-        const float z = clamp_min(zr, FLOOR);
-        const float moved = ((P[0] * (xs * z) + P[1] * (ys * z)) + P[2] * z) + P[3];
-        warped = moved * sm;
-        p.dmoved = zr >= FLOOR ? ((P[0] * xs + P[1] * ys) + P[2]) * sm : 0.0f;
-    }
-    p.m = (warp_valid(q) && y >= H / 3 && warped > 0.0f) ? 1.0f : 0.0f;
-    p.tgt_m = t * p.m;
-    p.got_m = warped * p.m;
-    p.a = clamp_min(p.tgt_m, FLOOR);
-    p.b = clamp_min(p.got_m, FLOOR);
-    return p;
-}
-
+// ---- depth stereo consistency (the per-pixel chain: loss_terms_math.hpp) ----------------------------------------------------------
 __global__ __launch_bounds__(256) void loss_dsc_kernel(DscArgs g, int B, float* __restrict__ part) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     float num = 0.0f, den = 0.0f;
@@ -150,17 +75,9 @@ __global__ __launch_bounds__(256) void loss_dsc_bwd_kernel(DscArgs g, const floa
     const int HW = g.H * g.W;
     if (pix >= HW) return;
     const int b = blockIdx.y;
-    const DscPixel p = dsc_pixel(g, b, pix);
-    const RelDiff r = rel_diff(p.a, p.b);
-    const float gd = (g_value[b] / count[b]) * p.m;
-    float ga, gb;
-    rel_diff_grad(r, p.a, p.b, gd, ga, gb);
-    if (g_tgt) g_tgt[(size_t)b * HW + pix] = p.tgt_m >= FLOOR ? ga * p.m : 0.0f;
-    if (g_src && p.tap >= 0) {
-        const float gw = p.got_m >= FLOOR ? gb * p.m : 0.0f;
-        const float v = gw * p.dmoved;
-        if (v != 0.0f) atomicAdd(g_src + (size_t)b * HW + p.tap, v);
-    }
+    const DscGrad d = dsc_pixel_grad(g, count, g_value, b, pix);
+    if (g_tgt) g_tgt[(size_t)b * HW + pix] = d.g_tgt;
+    if (g_src && d.tap >= 0 && d.v != 0.0f) atomicAdd(g_src + (size_t)b * HW + d.tap, d.v);
 }
 
 // ---- RGB stereo consistency ----------------------------------------------------------------------------------------------------
@@ -443,15 +360,6 @@ namespace {
 
 using namespace pdepth;
 using namespace pdepth::capi;
-
-// B, H, W of a map walked one thread per pixel: positive, at least `least` rows and columns, H W <= 2^24 (a pixel count is exact
-// in fp32), B within the grid's y
-int check_map(const char* who, int32_t B, int32_t H, int32_t W, int least) {
-    if (B <= 0 || H <= 0 || W <= 0) return fail(PDEPTH_E_ARG, "%s: non-positive dimension", who);
-    if (H < least || W < least) return fail(PDEPTH_E_ARG, "%s: H and W must be at least %d", who, least);
-    if ((long long)H * W > (1ll << 24) || B > 65535) return fail(PDEPTH_E_ARG, "%s: H*W must be at most 2^24 and B at most 65535", who);
-    return PDEPTH_OK;
-}
 
 }  // namespace
 

@@ -1,0 +1,224 @@
+// The two scattered gradients of the training loss as order-independent sums (fixed_accum.hpp): g_src_depth of the depth stereo
+// consistency term (loss_terms.hip: loss_dsc_bwd_kernel) and grad_img of inverse_warp (extras.hip: inverse_warp_bwd_kernel, both
+// sampling modes).  The same bits from call to call, and an item's result does not depend on its neighbours in the batch.
+//
+// Both are one-thread-per-pixel kernels, so the per-pixel chain (loss_terms_math.hpp, inverse_warp_math.hpp: the expressions of
+// the atomic kernels, in their order) simply runs twice:
+//   pass 0  the exact maximum of |q| over the contributions of an item (atomicMax over the bit patterns of |q|: order-independent,
+//           a NaN or an infinity wins it) -> S_b = det_scale_exponent(max, N), N = 4 H W (pixels x taps);
+//   pass 1  the same contributions, quantised with S_b and added to the int64 accumulator (global_atomic_add_x2);
+//   convert accumulator -> fp32.  An item whose maximum is 0 is 0; an item with a non-finite contribution is NaN in every element
+//           (an integer cannot hold a NaN; the atomic path confines it to the texels it reaches), every other item is untouched.
+// The gradients that are written per owner -- g_tgt_depth, grad_point -- are those of the existing kernels, called with a null
+// scatter pointer: the same bits as the atomic path's.
+//
+// Workspace: a 256-byte-rounded header of 4 bytes per item, then one int64 per element of the scattered gradient.
+#include <hip/hip_runtime.h>
+
+#include "capi_util.hpp"
+#include "fixed_accum.hpp"
+#include "inverse_warp_math.hpp"
+#include "kernels.hpp"
+#include "loss_terms_math.hpp"
+
+namespace pdepth {
+
+namespace {
+
+using namespace fixed;
+
+size_t header_bytes(int B) { return ((size_t)B * sizeof(uint32_t) + 255) / 256 * 256; }
+size_t workspace_bytes(int B, size_t per_item) { return header_bytes(B) + (B * per_item * sizeof(long long) + 255) / 256 * 256; }
+unsigned long long* accumulator(void* workspace, int B) {
+    return reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + header_bytes(B));
+}
+
+// the maximum of a wave's |q| bits into the item's header word (every lane of the wave calls)
+__device__ __forceinline__ void put_max(uint32_t m, uint32_t* __restrict__ slot) {
+    m = wave_max_bits(m);
+    if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(slot, m);
+}
+
+// PASS 0: maximum of |v|; PASS 1: scatter.  grid (blocks of 256 pixels, B)
+template <int PASS>
+__global__ __launch_bounds__(256) void dsc_det_kernel(DscArgs g, const float* __restrict__ count, const float* __restrict__ g_value,
+                                                      uint32_t* __restrict__ hdr, unsigned long long* __restrict__ acc) {
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    const int HW = g.H * g.W;
+    const int b = blockIdx.y;
+    float v = 0.0f;
+    int tap = -1;
+    if (pix < HW) {
+        const DscGrad d = dsc_pixel_grad(g, count, g_value, b, pix);
+        tap = d.tap;
+        v = tap >= 0 ? d.v : 0.0f;
+    }
+    if (PASS == 0) {
+        put_max(abs_bits(v), hdr + b);
+    } else {
+        const int S = det_scale_exponent(__uint_as_float(hdr[b]), 4ll * HW);
+        if (S == EXP_ZERO || S == EXP_NONFINITE) return;
+        if (tap >= 0 && v != 0.0f) det_add(acc + (size_t)b * HW + tap, v, S);
+    }
+}
+
+// grad_img of inverse_warp_bwd_kernel<MODE>: q = g (nearest) / g w_t (bilinear) at the in-bounds taps
+template <int MODE, int PASS>
+__global__ __launch_bounds__(256) void inverse_warp_det_kernel(const float* __restrict__ depth, const float* __restrict__ Kinv,
+                                                               const float* __restrict__ proj, const float* __restrict__ go, int C, int H,
+                                                               int W, uint32_t* __restrict__ hdr, unsigned long long* __restrict__ acc) {
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    const int HW = H * W;
+    const int b = blockIdx.y;
+    const bool live = pix < HW;
+    const int pc = live ? pix : HW - 1;   // dead lanes shadow the last pixel and add nothing
+    const int y = pc / W, x = pc - y * W;
+    const WarpSample q = warp_sample(Kinv + b * 9, proj + b * 12, x, y, depth[(size_t)b * HW + pc], H, W);
+    const float* gb = go + (size_t)b * C * HW + pc;
+    int S = 0;
+    if (PASS == 1) {
+        S = det_scale_exponent(__uint_as_float(hdr[b]), 4ll * HW);
+        if (S == EXP_ZERO || S == EXP_NONFINITE) return;
+    }
+    uint32_t m = 0u;
+    if (MODE == 1) {
+        const int tap = live ? nearest_tap(q, H, W) : -1;
+        if (tap >= 0) {
+            for (int c = 0; c < C; ++c) {
+                const float g = gb[(size_t)c * HW];
+                if (PASS == 0) m = max(m, abs_bits(g));
+                else det_add(acc + ((size_t)b * C + c) * HW + tap, g, S);
+            }
+        }
+    } else {
+        const size_t base = (size_t)b * C * HW + (q.y0 * W + q.x0);
+        const bool ok = live && q.finite;
+        const bool t00 = ok && q.xi0 && q.yi0, t01 = ok && q.xi1 && q.yi0;
+        const bool t10 = ok && q.xi0 && q.yi1, t11 = ok && q.xi1 && q.yi1;
+        if (t00 || t01 || t10 || t11) {
+            for (int c = 0; c < C; ++c) {
+                const float g = gb[(size_t)c * HW];
+                const float q00 = g * q.nw, q01 = g * q.ne, q10 = g * q.sw, q11 = g * q.se;
+                if (PASS == 0) {
+                    if (t00) m = max(m, abs_bits(q00));
+                    if (t01) m = max(m, abs_bits(q01));
+                    if (t10) m = max(m, abs_bits(q10));
+                    if (t11) m = max(m, abs_bits(q11));
+                } else {
+                    unsigned long long* gi = acc + base + (size_t)c * HW;
+                    if (t00) det_add(gi, q00, S);
+                    if (t01) det_add(gi + 1, q01, S);
+                    if (t10) det_add(gi + W, q10, S);
+                    if (t11) det_add(gi + W + 1, q11, S);
+                }
+            }
+        }
+    }
+    if (PASS == 0) put_max(m, hdr + b);
+}
+
+// grid (blocks of 256 elements of an item, B); n: the N of the scatter's exponent
+__global__ __launch_bounds__(256) void det_convert_kernel(const uint32_t* __restrict__ hdr, const long long* __restrict__ acc,
+                                                          float* __restrict__ out, size_t per_item, long long n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= per_item) return;
+    const int b = blockIdx.y;
+    const int S = det_scale_exponent(__uint_as_float(hdr[b]), n);
+    const size_t at = (size_t)b * per_item + i;
+    out[at] = S == EXP_ZERO ? 0.0f : S == EXP_NONFINITE ? __uint_as_float(0x7fc00000u) : det_to_float(acc[at], S);
+}
+
+hipError_t convert(void* workspace, int B, size_t per_item, long long n, float* out, hipStream_t stream) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(det_convert_kernel, dim3((unsigned)((per_item + 255) / 256), B), dim3(256), 0, stream,
+                       static_cast<const uint32_t*>(workspace), reinterpret_cast<const long long*>(accumulator(workspace, B)), out, per_item, n);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+}  // namespace pdepth
+
+// ---- C ABI (include/pdepth.h), beside the kernels like the entries of loss_terms.hip ------------------------------------------------
+using namespace pdepth;
+using namespace pdepth::capi;
+
+extern "C" {
+
+size_t pdepth_loss_dsc_backward_det_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    return (B > 0 && H > 0 && W > 0 && (long long)H * W <= (1ll << 24)) ? workspace_bytes(B, (size_t)H * W) : 0;
+}
+
+size_t pdepth_inverse_warp_backward_det_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+    return (B > 0 && C > 0 && H > 0 && W > 0 && (long long)H * W <= (1ll << 30)) ? workspace_bytes(B, (size_t)C * H * W) : 0;
+}
+
+int pdepth_loss_dsc_backward_det_f32(const float* src_depth, const float* tgt_depth, const float* src_mask, const float* Kinv,
+                                     const float* proj, const float* pose_row, int32_t pose_batched, const float* intr, const float* count,
+                                     const float* g_value, int32_t B, int32_t H, int32_t W, float* g_src_depth, float* g_tgt_depth,
+                                     void* workspace, size_t workspace_bytes_given, void* stream) {
+    const char* who = "pdepth_loss_dsc_backward_det_f32";
+    if (!src_depth || !tgt_depth || !src_mask || !Kinv || !proj || !pose_row || !intr || !count || !g_value)
+        return fail(PDEPTH_E_ARG, "%s: null pointer", who);
+    if (!g_src_depth && !g_tgt_depth) return fail(PDEPTH_E_ARG, "%s: no gradient requested", who);
+    if (int rc = check_map(who, B, H, W, 2)) return rc;
+    const size_t per_item = (size_t)H * W;
+    if (g_src_depth) {
+        if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, per_item),
+                                     "; query pdepth_loss_dsc_backward_det_workspace_bytes()"))
+            return rc;
+    }
+    if (g_tgt_depth) {   // written per owner: the existing kernel, nothing scattered
+        if (int rc = pdepth_loss_dsc_backward_f32(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, pose_batched, intr, count, g_value, B,
+                                                  H, W, nullptr, g_tgt_depth, stream))
+            return rc;
+    }
+    if (!g_src_depth) return PDEPTH_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes(B, per_item), s);
+    if (e != hipSuccess) return launched(e, who);
+    const DscArgs a{src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, pose_batched ? 4 : 0, H, W};
+    uint32_t* hdr = static_cast<uint32_t*>(workspace);
+    unsigned long long* acc = accumulator(workspace, B);
+    const dim3 grid((unsigned)((per_item + 255) / 256), B);
+    hipLaunchKernelGGL(dsc_det_kernel<0>, grid, dim3(256), 0, s, a, count, g_value, hdr, acc);
+    hipLaunchKernelGGL(dsc_det_kernel<1>, grid, dim3(256), 0, s, a, count, g_value, hdr, acc);
+    return launched(convert(workspace, B, per_item, 4ll * (long long)per_item, g_src_depth, s), who);
+}
+
+int pdepth_inverse_warp_backward_det_f32(const float* img, const float* depth, const float* Kinv, const float* proj, const float* grad_out,
+                                         int32_t B, int32_t C, int32_t H, int32_t W, int32_t mode, float* grad_img, float* grad_point,
+                                         void* workspace, size_t workspace_bytes_given, void* stream) {
+    const char* who = "pdepth_inverse_warp_backward_det_f32";
+    if (!img || !depth || !Kinv || !proj || !grad_out || (!grad_img && !grad_point)) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
+    if (B <= 0 || C <= 0 || H <= 1 || W <= 1) return fail(PDEPTH_E_ARG, "%s: bad dimension", who);
+    if (mode != PDEPTH_SAMPLE_BILINEAR && mode != PDEPTH_SAMPLE_NEAREST) return fail(PDEPTH_E_ARG, "%s: unknown mode %d", who, mode);
+    if (int rc = check_launch_limits(who, B, H, W)) return rc;
+    const size_t per_item = (size_t)C * H * W;
+    if (grad_img) {
+        if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, per_item),
+                                     "; query pdepth_inverse_warp_backward_det_workspace_bytes()"))
+            return rc;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (grad_point) {   // written per owner: the existing kernel, nothing scattered
+        if (int rc = launched(launch_inverse_warp_backward(img, depth, Kinv, proj, grad_out, B, C, H, W, mode, nullptr, grad_point, s), who))
+            return rc;
+    }
+    if (!grad_img) return PDEPTH_OK;
+    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes(B, per_item), s);
+    if (e != hipSuccess) return launched(e, who);
+    uint32_t* hdr = static_cast<uint32_t*>(workspace);
+    unsigned long long* acc = accumulator(workspace, B);
+    const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), B);
+    auto go = [&](auto k0, auto k1) {
+        hipLaunchKernelGGL(k0, grid, dim3(256), 0, s, depth, Kinv, proj, grad_out, C, H, W, hdr, acc);
+        hipLaunchKernelGGL(k1, grid, dim3(256), 0, s, depth, Kinv, proj, grad_out, C, H, W, hdr, acc);
+    };
+    if (mode == PDEPTH_SAMPLE_BILINEAR) go(inverse_warp_det_kernel<0, 0>, inverse_warp_det_kernel<0, 1>);
+    else go(inverse_warp_det_kernel<1, 0>, inverse_warp_det_kernel<1, 1>);
+    return launched(convert(workspace, B, per_item, 4ll * H * W, grad_img, s), who);
+}
+
+}  // extern "C"

@@ -36,6 +36,7 @@ constexpr int BT = 16;            // tile edge (pixels)
 constexpr int BTHREADS = BT * BT;
 constexpr int BCC = 8;            // channels per pass
 constexpr int BOX_CAP = 2048;     // texels of the LDS box image: BCC * BOX_CAP * 4 B = 64 KB
+static_assert(BT == SWEEP_BWD_TILE && BOX_CAP == SWEEP_BWD_BOX_CAP, "sweep_bwd_det.hip forms the same plane groups");
 
 __device__ __forceinline__ int wave_min(int x) {
 #pragma unroll

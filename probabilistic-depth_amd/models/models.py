@@ -270,6 +270,9 @@ class BaseModel(nn.Module):
         self.sweep_algo = "auto"  # "direct" selects the gather kernel (debugging / comparison)
         self.packed_epilogue = True   # encoder epilogue kernel + packed sweep entry (False: cat + avg_pool2d + plain entry)
         self.sweep_blas = None    # None = rounding of this host's CPU BLAS; "fma" / "separate" to force
+        # how the sweep's backward sums the gradient of the source features: None follows torch.use_deterministic_algorithms(),
+        # True / False force the integer sum (reproducible bit for bit) / the float atomics (ops.sweep_cost)
+        self.sweep_deterministic = None
 
     def set_viz(self, viz):
         self.viz = viz
@@ -325,8 +328,9 @@ class BaseModel(nn.Module):
         if isinstance(feats, _SweepFeatures):   # sources already in the staging layout: the packed entry, no pre-pass
             return ops.sweep_cost(feats.ref, feats.packed, K, R, t, rays, cxcy, model_input["d_candi"],
                                   self.sigma_soft_max, feat_dist="L2", algo="auto", blas=self.sweep_blas)
+        det = {} if self.sweep_deterministic is None else {"deterministic": self.sweep_deterministic}   # (None: the op's default)
         return ops.sweep_cost(feats[:, -1], feats[:, :-1], K, R, t, rays, cxcy, model_input["d_candi"],
-                              self.sigma_soft_max, feat_dist="L2", algo=self.sweep_algo, blas=self.sweep_blas)
+                              self.sigma_soft_max, feat_dist="L2", algo=self.sweep_algo, blas=self.sweep_blas, **det)
 
     def _low_res_dpv(self, cost_volumes, d_candi, want_prob=False):
         """log-DPV of the cost volume (models.py:555-560); with want_prob also exp(logp) and E[d] from the same pass."""

@@ -49,16 +49,24 @@ def d_candi_tensor(d_candi, device):
     return t
 
 
-def sweep_cost(ref, src, K, R, t, rays, cxcy, d_candi, sigma, feat_dist="L2", algo="auto", blas=None):
+def _deterministic(flag):
+    """The `deterministic` keyword of the ops with a scattered gradient: None follows torch.use_deterministic_algorithms()."""
+    return torch.are_deterministic_algorithms_enabled() if flag is None else bool(flag)
+
+
+def sweep_cost(ref, src, K, R, t, rays, cxcy, d_candi, sigma, feat_dist="L2", algo="auto", blas=None, deterministic=None):
     """cost [B,D,H,W].  Batched est_swp_volume_v4 (warping/homography.py:98-135).
 
     blas: None = reproduce the rounding of THIS host's CPU BLAS (see _native.host_blas_mode),
     "fma" / "separate" to force one (golden fixtures record the mode of the host that made them).
+    deterministic (backward only; the forward and its values are the same either way): True sums the gradient of src as
+    64-bit integers (csrc/sweep_bwd_det.hip: the same bits from run to run, 8 bytes of workspace per element of src), False
+    with float atomics, None = torch.are_deterministic_algorithms_enabled() when the op is called.
     """
     if _sweep_wants_grad("sweep_cost", ref, src, K, R, t, rays, cxcy, d_candi):
         dc = d_candi_tensor(d_candi, ref.device)
         cost, _, _ = _SweepFn.apply(ref, src, K, R, t, rays, cxcy, dc, sigma, _metric(feat_dist), ALGOS[algo], BLAS_MODES[blas],
-                                    True, False, False)
+                                    True, False, False, _deterministic(deterministic))
         return cost
     cost, _, _ = _native.sweep(ref, src, K, R, t, rays, cxcy, d_candi_tensor(d_candi, ref.device), sigma,
                                _metric(feat_dist), ALGOS[algo], want_cost=True, blas_mode=BLAS_MODES[blas])
@@ -66,15 +74,15 @@ def sweep_cost(ref, src, K, R, t, rays, cxcy, d_candi, sigma, feat_dist="L2", al
 
 
 def sweep_dpv(ref, src, K, R, t, rays, cxcy, d_candi, sigma, feat_dist="L2", algo="auto",
-              want_cost=False, want_logp=True, want_depth=True, blas=None):
+              want_cost=False, want_logp=True, want_depth=True, blas=None, deterministic=None):
     """Fused sweep -> log_softmax(dim=1) -> E[d].  Returns (cost|None, logp|None, depth|None).
 
-    models/packnet.py:380-394 + utils/img_utils.py:52-61 in one kernel.
+    models/packnet.py:380-394 + utils/img_utils.py:52-61 in one kernel.  deterministic: as sweep_cost.
     """
     if _sweep_wants_grad("sweep_dpv", ref, src, K, R, t, rays, cxcy, d_candi):
         dc = d_candi_tensor(d_candi, ref.device)
         return _SweepFn.apply(ref, src, K, R, t, rays, cxcy, dc, sigma, _metric(feat_dist), ALGOS[algo], BLAS_MODES[blas],
-                              want_cost, want_logp, want_depth)
+                              want_cost, want_logp, want_depth, _deterministic(deterministic))
     return _native.sweep(ref, src, K, R, t, rays, cxcy, d_candi_tensor(d_candi, ref.device), sigma,
                          _metric(feat_dist), ALGOS[algo], want_cost=want_cost, want_logp=want_logp,
                          want_depth=want_depth, blas_mode=BLAS_MODES[blas])
@@ -237,19 +245,20 @@ def lidar_depth(points, counts, M_velo2cam, intr, width, height, filtering=2, fi
     return {"dmap_imgsizes": dmap, "masks_imgsizes": mask.unsqueeze(1), "dmaps": dmap_q, "masks": mask_q.unsqueeze(1)}
 
 
-def depth_stereo_consistency(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
+def depth_stereo_consistency(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, deterministic=None):
     """depth_stereo_consistency_loss per item (losses/loss_blocks.py:147-171), one HIP pass: (value [B], count [B]).
 
     src_depth, tgt_depth [B,H,W] | [B,1,H,W]; src_mask likewise; Kinv [B,3,3] = intr^-1 and proj [B,3,4] = intr @ pose_target2src[:3]
     as utils.inverse_warp.warp_with_matrices takes them; pose_row [B,4] | [1,4] = the third row of the source-to-target pose; intr
     [B,3,3].  The mask (valid & lower two thirds & warped > 0) is formed from the sample positions of the HIP inverse_warp, bit for
     bit; count is its size per item, not differentiable; an item with an empty mask is NaN.  Differentiable with respect to both
-    depth maps (the source through an atomic scatter); everything else is data."""
+    depth maps (the source through an atomic scatter; deterministic, as sweep_cost's: an order-independent integer sum instead,
+    csrc/scatter_det.hip); everything else is data."""
     who = "depth_stereo_consistency"
     src_depth, tgt_depth, src_mask = (_squeeze_map(t) for t in (src_depth, tgt_depth, src_mask))
     if _wants_grad(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
         _refuse_data_grad(who, src_mask=src_mask, Kinv=Kinv, proj=proj, pose_row=pose_row, intr=intr)
-        return _DscFn.apply(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
+        return _DscFn.apply(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, _deterministic(deterministic))
     return _native.loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
 
 
@@ -375,20 +384,20 @@ class _SweepFn(torch.autograd.Function):
     the backward whenever logp or depth is returned (computed by the same fused call when the caller did not ask for it)."""
 
     @staticmethod
-    def forward(ctx, ref, src, K, R, t, rays, cxcy, dc, sigma, metric, algo, blas_mode, want_cost, want_logp, want_depth):
+    def forward(ctx, ref, src, K, R, t, rays, cxcy, dc, sigma, metric, algo, blas_mode, want_cost, want_logp, want_depth, deterministic):
         ctx.set_materialize_grads(False)
         keep_logp = want_logp or want_depth
         cost, logp, depth = _native.sweep(ref, src, K, R, t, rays, cxcy, dc, sigma, metric, algo, want_cost=want_cost,
                                           want_logp=keep_logp, want_depth=want_depth, blas_mode=blas_mode)
         ctx.save_for_backward(ref, src, K, R, t, rays, cxcy, dc, logp if keep_logp else None)
-        ctx.cfg = (sigma, metric, blas_mode)
+        ctx.cfg = (sigma, metric, blas_mode, deterministic)
         return cost, (logp if want_logp else None), depth
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cost, g_logp, g_depth):
         ref, src, K, R, t, rays, cxcy, dc, logp = ctx.saved_tensors
-        sigma, metric, blas_mode = ctx.cfg
+        sigma, metric, blas_mode, deterministic = ctx.cfg
         g = None
         if g_logp is not None or g_depth is not None:
             g = _native.dpv_reduce_backward(logp, dc, g_logp=g_logp, g_depth=g_depth)
@@ -398,8 +407,8 @@ class _SweepFn(torch.autograd.Function):
         g_ref = g_src = None
         if g is not None and (want_ref or want_src):
             g_ref, g_src = _native.sweep_backward(ref, src, K, R, t, rays, cxcy, dc, g, sigma, metric, want_ref=want_ref,
-                                                  want_src=want_src, blas_mode=blas_mode)
-        return (g_ref, g_src) + (None,) * 13
+                                                  want_src=want_src, blas_mode=blas_mode, deterministic=deterministic)
+        return (g_ref, g_src) + (None,) * 14
 
 
 class _DpvReduceFn(torch.autograd.Function):
@@ -499,8 +508,9 @@ class _DscFn(torch.autograd.Function):
     """depth_stereo_consistency under autograd: (value, count); the backward recomputes every pixel from the inputs."""
 
     @staticmethod
-    def forward(ctx, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
+    def forward(ctx, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, deterministic):
         ctx.set_materialize_grads(False)
+        ctx.deterministic = deterministic
         value, count = _native.loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
         ctx.save_for_backward(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, count)
         ctx.mark_non_differentiable(count)
@@ -511,10 +521,11 @@ class _DscFn(torch.autograd.Function):
     def backward(ctx, g_value, _g_count):
         want_src, want_tgt = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if g_value is None or not (want_src or want_tgt):
-            return (None,) * 7
+            return (None,) * 8
         *inputs, count = ctx.saved_tensors
-        g_src, g_tgt = _native.loss_dsc_backward(*inputs, count, g_value, want_src=want_src, want_tgt=want_tgt)
-        return (g_src, g_tgt) + (None,) * 5
+        g_src, g_tgt = _native.loss_dsc_backward(*inputs, count, g_value, want_src=want_src, want_tgt=want_tgt,
+                                                 deterministic=ctx.deterministic)
+        return (g_src, g_tgt) + (None,) * 6
 
 
 class _RscFn(torch.autograd.Function):

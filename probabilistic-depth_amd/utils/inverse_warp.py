@@ -6,8 +6,9 @@ intrinsics @ pose :200) stays in torch on the device -- a few dozen flops per ba
 own autograd -- and the per-pixel back-projection, projection and sampling run in one HIP kernel
 (pdepth_inverse_warp_f32; 'bilinear' and 'nearest', zeros padding).  The reference uses this function in its training
 losses, under autograd (losses/loss_blocks.py:116,151): when an input requires grad the call goes through
-_InverseWarpFn, whose backward is pdepth_inverse_warp_backward_f32 (image gradient by atomic scatter, gradient of the
-projected point per pixel) followed by the small products that carry it to the depth map, the pose and the intrinsics.
+_InverseWarpFn, whose backward is pdepth_inverse_warp_backward_f32 (image gradient by atomic scatter -- under
+torch.use_deterministic_algorithms(True) pdepth_inverse_warp_backward_det_f32: an order-independent integer sum, the same
+bits from run to run --, gradient of the projected point per pixel) followed by the small products that carry it to the depth map, the pose and the intrinsics.
 """
 import torch
 
@@ -47,10 +48,10 @@ class _InverseWarpFn(torch.autograd.Function):
     """(img, depth, Kinv, proj) -> (warped, valid): the HIP kernels with the chain rule of pixel2cam / cam2pixel."""
 
     @staticmethod
-    def forward(ctx, img, depth, Kinv, proj, mode):
+    def forward(ctx, img, depth, Kinv, proj, mode, deterministic):
         out, valid = _native.inverse_warp(img, depth, Kinv, proj, mode)
         ctx.save_for_backward(img, depth, Kinv, proj)
-        ctx.mode = mode
+        ctx.mode, ctx.deterministic = mode, deterministic
         ctx.mark_non_differentiable(valid)
         return out, valid
 
@@ -62,7 +63,7 @@ class _InverseWarpFn(torch.autograd.Function):
         g_img = g_depth = g_Kinv = g_proj = None
         if need_img or need_pt:
             g_img, g_pc = _native.inverse_warp_backward(img, depth, Kinv, proj, g_out.float(), ctx.mode,
-                                                        want_img=need_img, want_point=need_pt)
+                                                        want_img=need_img, want_point=need_pt, deterministic=ctx.deterministic)
         if need_pt:
             B, _, H, W = img.shape
             ys, xs = torch.meshgrid(torch.arange(H, device=img.device, dtype=torch.float32),
@@ -82,7 +83,7 @@ class _InverseWarpFn(torch.autograd.Function):
             g_depth = torch.zeros_like(depth) if ctx.needs_input_grad[1] else None
             g_Kinv = torch.zeros_like(Kinv) if ctx.needs_input_grad[2] else None
             g_proj = torch.zeros_like(proj) if ctx.needs_input_grad[3] else None
-        return g_img, g_depth, g_Kinv, g_proj, None
+        return g_img, g_depth, g_Kinv, g_proj, None, None
 
 
 def inverse_warp(img, depth, pose, intrinsics, mode="bilinear", rotation_mode="euler", padding_mode="zeros"):
@@ -104,11 +105,14 @@ def inverse_warp(img, depth, pose, intrinsics, mode="bilinear", rotation_mode="e
     return warp_with_matrices(img, depth, intrinsics.inverse(), proj, mode)
 
 
-def warp_with_matrices(img, depth, Kinv, proj, mode="bilinear"):
+def warp_with_matrices(img, depth, Kinv, proj, mode="bilinear", deterministic=None):
     """inverse_warp from the two matrices it derives: Kinv [B,3,3] = intrinsics^-1, proj [B,3,4] = intrinsics @ pose[:3].
-    For callers that form them without a host check (losses/: torch.inverse reads its status back from the device)."""
+    For callers that form them without a host check (losses/: torch.inverse reads its status back from the device).
+    deterministic: how the backward sums the image gradient (True: integers, order-independent; False: float atomics; None:
+    torch.are_deterministic_algorithms_enabled() at the call, which is what inverse_warp passes)."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (img, depth, Kinv, proj)):
-        return _InverseWarpFn.apply(img.float(), depth.float(), Kinv, proj, mode)
+        det = torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
+        return _InverseWarpFn.apply(img.float(), depth.float(), Kinv, proj, mode, det)
     return _native.inverse_warp(img.float(), depth.float(), Kinv, proj, mode)
 
 

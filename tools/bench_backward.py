@@ -2,6 +2,7 @@
 as PyTorch-ROCm autograd on the GPU (the oracle's formula: plane_coords grid + F.grid_sample + distance, on device tensors).
 
     python tools/bench_backward.py [--shapes headline,training,config5] [--reps 20] [--warmup 3]
+    python tools/bench_backward.py --deterministic [--reps 50]
 
 Prints ONE JSON line: per shape the median over --reps calls (device events, after --warmup calls) of
   fwd_ms / bwd_ms      : ops.sweep_cost with features that require grad / cost.backward(g_cost) (g_ref and g_src);
@@ -11,6 +12,12 @@ Prints ONE JSON line: per shape the median over --reps calls (device events, aft
                          plane groups of every 16 x 16 tile, C channels; texels the group never touched are skipped at run time,
                          planes whose box does not fit add their taps directly), from the shapes and the grouping rule of the
                          kernel evaluated on the sample positions of the call.
+
+--deterministic: ONE JSON line with, per shape (B = 4, V = 1, C = 67, D = 64 at 64 x 128 -- the sweep a model step runs -- and at
+256 x 512), the g_src pass alone (_native.sweep_backward, want_ref=False) of the float-atomic path (csrc/sweep_bwd.hip) and of the
+deterministic one (csrc/sweep_bwd_det.hip: clear + bounds pre-pass + scatter + convert, the workspace allocation included) in the
+same run, the two alternating call by call: atomic_ms / det_ms = medians over --reps calls each (device events), workspace_bytes,
+and max_rel_diff between the two results.
 """
 import argparse
 import json
@@ -139,14 +146,53 @@ def bench_shape(name, s, reps, warmup, dev):
                 torch_bwd_ms=round(tfb - tf, 3), torch_chunk_planes=chunk, atomic_bytes=atomic_bytes(d, s))
 
 
+DET_SHAPES = {
+    "model_step": dict(B=4, V=1, C=67, D=64, H=64, W=128, pose="mono"),
+    "headline": SHAPES["headline"],
+}
+
+
+def bench_deterministic(s, reps, warmup, dev):
+    import ctypes
+    b = synth.make_batch(77, s["B"], C=s["C"], D=s["D"], H=s["H"], W=s["W"], V=s["V"], pose=s["pose"])
+    d = {k: (v.to(dev) if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
+    dc = ops.d_candi_tensor(d["d_candi"], dev)
+    gcost = torch.randn(s["B"], s["D"], s["H"], s["W"], device=dev)
+    args = (d["ref"], d["src"], d["K"], d["R"], d["t"], d["rays"], d["cxcy"], dc, gcost, 10.0)
+    run = {det: (lambda det=det: _native.sweep_backward(*args, want_ref=False, deterministic=det)[1]) for det in (False, True)}
+    for _ in range(warmup):
+        run[False](), run[True]()
+    torch.cuda.synchronize()
+    ms = {False: [], True: []}
+    for _ in range(reps):
+        for det in (False, True):   # the variants alternate
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run[det]()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[det].append(e0.elapsed_time(e1))
+    ga, gd = run[False](), run[True]()
+    desc = _native.SweepDesc(s["B"], s["V"], s["C"], s["D"], s["H"], s["W"], 0, 1, 0, 10.0, 0, 0, 0)
+    return dict(shape=s, atomic_ms=round(float(np.median(ms[False])), 4), det_ms=round(float(np.median(ms[True])), 4),
+                workspace_bytes=int(_native.load().pdepth_sweep_backward_det_workspace_bytes(ctypes.byref(desc))),
+                max_rel_diff=float((ga - gd).abs().max() / ga.abs().max()), same_bits_twice=bool(torch.equal(gd, run[True]())))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--deterministic", action="store_true", help="time the g_src pass of the atomic and the deterministic path")
     ap.add_argument("--shapes", default="headline,training,config5")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     out = {"device": torch.cuda.get_device_name(0)}
+    if a.deterministic:
+        for name, s in DET_SHAPES.items():
+            out[name] = bench_deterministic(s, a.reps if a.reps != 20 else 50, a.warmup, dev)
+        print(json.dumps(out))
+        return
     for name in a.shapes.split(","):
         out[name] = bench_shape(name, SHAPES[name], a.reps, a.warmup, dev)
     print(json.dumps(out))
