@@ -66,5 +66,40 @@ __device__ __forceinline__ void det_add(unsigned long long* dst, float q, int S)
 // the sum back in fp32 (two roundings at most, see above)
 __device__ __forceinline__ float det_to_float(long long acc, int S) { return (float)__builtin_ldexp((double)acc, -S); }
 
+// ---- the workspace of an integer sum: a 256-byte-rounded header of `words` uint32 per batch item (the maxima the exponent is
+// derived from), then one int64 per element of the result, [B][per_item] --------------------------------------------------------
+inline size_t det_header_bytes(int B, int words) { return ((size_t)B * words * sizeof(uint32_t) + 255) / 256 * 256; }
+inline size_t det_workspace_bytes(int B, int words, size_t per_item) {
+    return det_header_bytes(B, words) + ((size_t)B * per_item * sizeof(long long) + 255) / 256 * 256;
+}
+inline unsigned long long* det_accumulator(void* workspace, int B, int words) {
+    return reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + det_header_bytes(B, words));
+}
+
+// accumulator -> fp32.  Exponent: WORDS (header words per item) and int operator()(const uint32_t* item_header), the S the scatter
+// used for the item; an item of EXP_ZERO is 0, an item of EXP_NONFINITE is NaN in every element.
+// grid (blocks of 256 elements of an item, B)
+template <class Exponent>
+__global__ __launch_bounds__(256) void det_convert_kernel(Exponent exponent, const uint32_t* __restrict__ hdr, const long long* __restrict__ acc,
+                                                          float* __restrict__ out, size_t per_item) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= per_item) return;
+    const int b = blockIdx.y;
+    const int S = exponent(hdr + Exponent::WORDS * b);
+    const size_t at = (size_t)b * per_item + i;
+    out[at] = S == EXP_ZERO ? 0.0f : S == EXP_NONFINITE ? __uint_as_float(0x7fc00000u) : det_to_float(acc[at], S);
+}
+
+// (returns the error of a launch before it, if one is pending, without launching)
+template <class Exponent>
+inline hipError_t det_convert(void* workspace, int B, size_t per_item, Exponent exponent, float* out, hipStream_t stream) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(det_convert_kernel<Exponent>, dim3((unsigned)((per_item + 255) / 256), B), dim3(256), 0, stream, exponent,
+                       static_cast<const uint32_t*>(workspace),
+                       reinterpret_cast<const long long*>(det_accumulator(workspace, B, Exponent::WORDS)), out, per_item);
+    return hipGetLastError();
+}
+
 }  // namespace fixed
 }  // namespace pdepth

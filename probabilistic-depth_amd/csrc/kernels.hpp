@@ -129,12 +129,9 @@ hipError_t launch_lidar_depth(const float* points, const int* counts, const floa
 // sweep_bwd.hip: gradient of the cost volume with respect to the NCHW features (either output may be nullptr, not both;
 // grad_src [B,V,C,H,W] contiguous, zeroed by the launcher; grad_ref [B,C,H,W] contiguous)
 hipError_t launch_sweep_backward(const SweepArgs& a, const float* grad_cost, float* grad_ref, float* grad_src, hipStream_t stream);
-// the tile edge and the texels of the LDS box image of the g_src pass: sweep_bwd.hip and sweep_bwd_det.hip group the planes of a
-// (tile, view) pair alike (both assert their constants against these)
-constexpr int SWEEP_BWD_TILE = 16;
-constexpr int SWEEP_BWD_BOX_CAP = 2048;
-// sweep_bwd_det.hip: grad_src of the above as an order-independent sum (fixed_accum.hpp): the same contributions, quantised per
-// batch item and added as 64-bit integers in the workspace, then converted; the same bits from call to call
+// sweep_bwd_det.hip: grad_src of the above as an order-independent sum (fixed_accum.hpp): the same contributions (one kernel body,
+// sweep_bwd_body.hpp), quantised per batch item and added as 64-bit integers in the workspace, then converted; the same bits from
+// call to call
 size_t sweep_backward_det_workspace_bytes(int B, int V, int C, int H, int W);
 hipError_t launch_sweep_backward_det(const SweepArgs& a, const float* grad_cost, float* grad_src, void* workspace, hipStream_t stream);
 

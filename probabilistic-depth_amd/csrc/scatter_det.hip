@@ -27,11 +27,14 @@ namespace {
 
 using namespace fixed;
 
-size_t header_bytes(int B) { return ((size_t)B * sizeof(uint32_t) + 255) / 256 * 256; }
-size_t workspace_bytes(int B, size_t per_item) { return header_bytes(B) + (B * per_item * sizeof(long long) + 255) / 256 * 256; }
-unsigned long long* accumulator(void* workspace, int B) {
-    return reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + header_bytes(B));
-}
+// the header word of an item is the maximum of |q| over its contributions; n: the N of the scatter's exponent
+struct MaxExponent {
+    static constexpr int WORDS = 1;
+    long long n;
+    __device__ int operator()(const uint32_t* h) const { return det_scale_exponent(__uint_as_float(h[0]), n); }
+};
+size_t workspace_bytes(int B, size_t per_item) { return det_workspace_bytes(B, MaxExponent::WORDS, per_item); }
+unsigned long long* accumulator(void* workspace, int B) { return det_accumulator(workspace, B, MaxExponent::WORDS); }
 
 // the maximum of a wave's |q| bits into the item's header word (every lane of the wave calls)
 __device__ __forceinline__ void put_max(uint32_t m, uint32_t* __restrict__ slot) {
@@ -117,25 +120,6 @@ __global__ __launch_bounds__(256) void inverse_warp_det_kernel(const float* __re
     if (PASS == 0) put_max(m, hdr + b);
 }
 
-// grid (blocks of 256 elements of an item, B); n: the N of the scatter's exponent
-__global__ __launch_bounds__(256) void det_convert_kernel(const uint32_t* __restrict__ hdr, const long long* __restrict__ acc,
-                                                          float* __restrict__ out, size_t per_item, long long n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= per_item) return;
-    const int b = blockIdx.y;
-    const int S = det_scale_exponent(__uint_as_float(hdr[b]), n);
-    const size_t at = (size_t)b * per_item + i;
-    out[at] = S == EXP_ZERO ? 0.0f : S == EXP_NONFINITE ? __uint_as_float(0x7fc00000u) : det_to_float(acc[at], S);
-}
-
-hipError_t convert(void* workspace, int B, size_t per_item, long long n, float* out, hipStream_t stream) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(det_convert_kernel, dim3((unsigned)((per_item + 255) / 256), B), dim3(256), 0, stream,
-                       static_cast<const uint32_t*>(workspace), reinterpret_cast<const long long*>(accumulator(workspace, B)), out, per_item, n);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 }  // namespace pdepth
@@ -184,7 +168,7 @@ int pdepth_loss_dsc_backward_det_f32(const float* src_depth, const float* tgt_de
     const dim3 grid((unsigned)((per_item + 255) / 256), B);
     hipLaunchKernelGGL(dsc_det_kernel<0>, grid, dim3(256), 0, s, a, count, g_value, hdr, acc);
     hipLaunchKernelGGL(dsc_det_kernel<1>, grid, dim3(256), 0, s, a, count, g_value, hdr, acc);
-    return launched(convert(workspace, B, per_item, 4ll * (long long)per_item, g_src_depth, s), who);
+    return launched(det_convert(workspace, B, per_item, MaxExponent{4ll * (long long)per_item}, g_src_depth, s), who);
 }
 
 int pdepth_inverse_warp_backward_det_f32(const float* img, const float* depth, const float* Kinv, const float* proj, const float* grad_out,
@@ -218,7 +202,7 @@ int pdepth_inverse_warp_backward_det_f32(const float* img, const float* depth, c
     };
     if (mode == PDEPTH_SAMPLE_BILINEAR) go(inverse_warp_det_kernel<0, 0>, inverse_warp_det_kernel<0, 1>);
     else go(inverse_warp_det_kernel<1, 0>, inverse_warp_det_kernel<1, 1>);
-    return launched(convert(workspace, B, per_item, 4ll * H * W, grad_img, s), who);
+    return launched(det_convert(workspace, B, per_item, MaxExponent{4ll * H * W}, grad_img, s), who);
 }
 
 }  // extern "C"

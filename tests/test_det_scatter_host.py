@@ -186,13 +186,20 @@ def test_ops_carry_the_keyword():
 
 
 def test_the_two_sweep_units_group_planes_alike():
-    """tests/util_sweep_backward.py restates the grouping from the constants of sweep_bwd.hip; sweep_bwd_det.hip takes the same
-    ones (both are pinned to kernels.hpp)."""
+    """Both units run the one body of sweep_bwd_body.hpp: neither has a tile edge, a box cap, sample positions or footprints of
+    its own, and the constants tests/util_sweep_backward.py restates the grouping from are the ones of that header."""
     import util_sweep_backward as U
     csrc = os.path.join(REPO, "probabilistic-depth_amd", "csrc")
-    k = open(os.path.join(csrc, "kernels.hpp")).read()
-    shared = tuple(int(re.search(r"constexpr int %s = (\d+);" % n, k).group(1)) for n in ("SWEEP_BWD_BOX_CAP", "SWEEP_BWD_TILE"))
-    assert shared == U.kernel_constants()
-    det = open(os.path.join(csrc, "sweep_bwd_det.hip")).read()
-    assert "BT = SWEEP_BWD_TILE;" in det and "BOX_CAP = SWEEP_BWD_BOX_CAP;" in det
-    assert "static_assert(BT == SWEEP_BWD_TILE && BOX_CAP == SWEEP_BWD_BOX_CAP" in open(os.path.join(csrc, "sweep_bwd.hip")).read()
+    body = open(os.path.join(csrc, "sweep_bwd_body.hpp")).read()
+    for unit in ("sweep_bwd.hip", "sweep_bwd_det.hip"):
+        text = open(os.path.join(csrc, unit)).read()
+        code = re.sub(r"//[^\n]*", "", text)   # (the header comments may speak of the helpers)
+        assert '#include "sweep_bwd_body.hpp"' in code, unit
+        assert re.search(r"sweep_bwd_body\s*<", code), unit
+        assert not re.search(r"\b(BT|BTHREADS|BOX_CAP|BCC|\w*TILE\w*)\s*=", code), unit
+        assert "plane_sample_pos" not in code and "make_footprint" not in code, unit
+        assert "plane_sample_pos(" not in text, unit
+    assert os.path.samefile(U.KERNEL, os.path.join(csrc, "sweep_bwd_body.hpp"))
+    declared = tuple(int(v) for n in ("BOX_CAP", "BT") for v in re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % n, body))
+    assert len(declared) == 2 and declared == U.kernel_constants()   # (each declared exactly once)
+    assert "SWEEP_BWD_TILE" not in open(os.path.join(csrc, "kernels.hpp")).read()

@@ -13,7 +13,7 @@ from pdepth_amd import ops, synth
 from oracle import ref_cpu as O
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = os.path.join(REPO, "probabilistic-depth_amd", "csrc", "sweep_bwd.hip")
+KERNEL = os.path.join(REPO, "probabilistic-depth_amd", "csrc", "sweep_bwd_body.hpp")   # the one body of both g_src paths
 
 
 def to_dev(b, dev):
@@ -101,12 +101,12 @@ def l1_allowance(b, gup, sigma, dev, tau=1e-5):
 
 # ---- the plane groups of the g_src pass, restated on the host ------------------------------------------------------------
 def kernel_constants():
-    """(BOX_CAP, BT) as csrc/sweep_bwd.hip declares them: the cases below are chosen against these two numbers."""
+    """(BOX_CAP, BT) as csrc/sweep_bwd_body.hpp declares them: the cases below are chosen against these two numbers."""
     text = open(KERNEL).read()
     found = []
     for name in ("BOX_CAP", "BT"):
         m = re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
-        assert m, "csrc/sweep_bwd.hip no longer declares 'constexpr int %s = <number>;'" % name
+        assert m, "csrc/sweep_bwd_body.hpp no longer declares 'constexpr int %s = <number>;'" % name
         found.append(int(m.group(1)))
     return tuple(found)
 

@@ -39,7 +39,7 @@ SHAPES = {
     "training": dict(B=2, V=1, C=67, D=64, H=64, W=96, pose="mono"),
     "config5": dict(B=1, V=4, C=67, D=128, H=512, W=1024, pose="stereo"),
 }
-TILE, BOX_CAP = 16, 2048   # csrc/sweep_bwd.hip: BT, BOX_CAP
+TILE, BOX_CAP = 16, 2048   # csrc/sweep_bwd_body.hpp: BT, BOX_CAP
 
 
 def timed(fn, reps, warmup):
