@@ -61,7 +61,8 @@ extern "C" {
                                 *    pdepth_dpv_fuse_backward_f32; pdepth_lidar_depth_workspace_bytes, pdepth_lidar_depth_f32;
                                 *    pdepth_loss_terms_workspace_bytes, pdepth_loss_{dsc,rsc,dc,smooth}_f32 and their _backward_f32;
                                 *    PDEPTH_DTYPE_F16 / PDEPTH_DTYPE_BF16, pdepth_dpv_reduce_ex_lp, pdepth_dpv_reduce_backward_lp;
-                                *    pdepth_det_scale_exponent and the three _backward_det_f32 entries with their _det_workspace_bytes */
+                                *    pdepth_det_scale_exponent and the three _backward_det_f32 entries with their _det_workspace_bytes;
+                                *    pdepth_warp_feature_backward_f32, pdepth_warp_feature_backward_det_f32 and its _det_workspace_bytes */
 
 enum {
     PDEPTH_OK = 0,
@@ -682,6 +683,37 @@ size_t pdepth_inverse_warp_backward_det_workspace_bytes(int32_t B, int32_t C, in
 int pdepth_inverse_warp_backward_det_f32(const float *img, const float *depth, const float *Kinv, const float *proj,
                                          const float *grad_out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t mode,
                                          float *grad_img, float *grad_point, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Backward of pdepth_warp_feature_f32 with respect to src: the fourth scattered gradient, in both forms.
+ *
+ * The forward is linear in src: out[b,v,k,y,x] = bilinear(src[b,v,k], pos_k(b,v,y,x)), zeros padding, align_corners=False, channel k
+ * sampled at plane k.  Nothing of it is saved:
+ *     grad_src[b,v,k,t] = sum over the samples (y,x) of grad_out[b,v,k,y,x] w_tap(t),   over the at most 4 in-bounds taps of each.
+ * Positions, taps and weights are the forward's, bit for bit (one per-sample chain for both kernels).  The taps follow ATen's
+ * grid_sampler_2d backward: an in-bounds tap receives g w even when w == 0 (an infinite g leaves a NaN there), an out-of-bounds tap
+ * receives nothing, and a non-finite position has no tap.
+ *
+ * desc is read as pdepth_warp_feature_f32 reads it (C == D planes, algo, blas_mode); src_vstride = D H W and src_bstride = V D H W
+ * describe grad_src, which must be contiguous [B,V,D,H,W], as grad_out is.  D <= 512, H W <= 2^30, B <= 65535; grad_src may not
+ * alias grad_out.
+ *   pdepth_warp_feature_backward_f32      float atomics into grad_src (zeroed by the call on the stream): the last bits depend on
+ *                                         the order in which the adds arrive; a non-finite grad_out stays in the texels it reaches.
+ *   pdepth_warp_feature_backward_det_f32  the order-independent sum described above: q_i = g w_tap, M_b = the exact maximum of
+ *                                         |q_i| over item b (a first run of the chain), N = H W (a sample puts at most one of its
+ *                                         taps on a texel of its own (b,v,k) image).  M_b == 0: the item is exactly 0.  A NaN or
+ *                                         an infinity among the q_i of an item: NaN in EVERY element of that item, every other
+ *                                         item untouched.
+ *                                         Workspace: roundup256(4 B) + roundup256(8 B V D H W) bytes, 256-byte aligned, cleared by
+ *                                         the call (B = 4, V = 2, D = 64, 64 x 128: 33.6 MB); the query returns 0 for sizes out of
+ *                                         range; missing, too small or misaligned: PDEPTH_E_WORKSPACE.
+ */
+int pdepth_warp_feature_backward_f32(const pdepth_sweep_desc *desc, const pdepth_camera *cam, const float *d_candi,
+                                     const float *grad_out, float *grad_src, void *stream);
+size_t pdepth_warp_feature_backward_det_workspace_bytes(const pdepth_sweep_desc *desc);
+int pdepth_warp_feature_backward_det_f32(const pdepth_sweep_desc *desc, const pdepth_camera *cam, const float *d_candi,
+                                         const float *grad_out, float *grad_src, void *workspace, size_t workspace_bytes,
+                                         void *stream);
 
 #ifdef __cplusplus
 }

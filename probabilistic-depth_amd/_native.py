@@ -95,6 +95,9 @@ _SIGNATURES = {
     "pdepth_loss_dsc_backward_det_f32": (c_int, [_P] * 6 + [_I] + [_P] * 3 + [_I] * 3 + [_P] * 3 + [_Z, _P]),
     "pdepth_inverse_warp_backward_det_workspace_bytes": (_Z, [_I] * 4),
     "pdepth_inverse_warp_backward_det_f32": (c_int, [_P] * 5 + [_I] * 5 + [_P] * 3 + [_Z, _P]),
+    "pdepth_warp_feature_backward_f32": (c_int, [_DESC, _CAM] + [_P] * 4),
+    "pdepth_warp_feature_backward_det_workspace_bytes": (_Z, [_DESC]),
+    "pdepth_warp_feature_backward_det_f32": (c_int, [_DESC, _CAM] + [_P] * 4 + [_Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # The loss, loss-term, metrics, fusion-backward, LiDAR and deterministic-backward entries live in objects of their own: part of an entry's name -> the source file.  The
@@ -102,6 +105,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # loads, and a call of such an entry on it raises (_entry)
 _SOURCE_OF_ENTRY = {"_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
+                    "_warp_feature_backward_": "csrc/warp_bwd.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -658,6 +662,37 @@ def warp_feature(src, K, R, t, rays, cxcy, d_candi, blas_mode=None):
     _check(rc, lib)
     del keep
     return out
+
+
+def warp_feature_backward(g_out, K, R, t, rays, cxcy, d_candi, blas_mode=None, deterministic=False):
+    """g_out [B,V,D,H,W] -> g_src [B,V,D,H,W], the gradient of warp_feature with respect to src (the forward is linear in src:
+    nothing of it is needed): pdepth_warp_feature_backward_f32, summed with float atomics (last bits depend on the order of
+    arrival) unless deterministic: pdepth_warp_feature_backward_det_f32 sums it as 64-bit integers in a workspace of 8 bytes per
+    element, allocated here -- the same bits from call to call (a non-finite g_out makes that item's g_src NaN throughout:
+    include/pdepth.h)."""
+    who = "warp_feature_backward"
+    lib = load()
+    _dev(g_out, "g_out")
+    if g_out.dim() != 5:
+        raise RuntimeError(f"{who}: g_out must be [B,V,D,H,W]")
+    B, V, D, H, W = g_out.shape
+    if d_candi.numel() != D:
+        raise RuntimeError(f"{who}: d_candi has {d_candi.numel()} entries, g_out has D={D}")
+    g_out, d_candi = g_out.contiguous(), d_candi.contiguous()
+    cam, keep = _camera(K, R, t, rays, cxcy, B, V, H * W)
+    desc = SweepDesc(B, V, D, D, H, W, 0, 0, _blas(blas_mode), 1.0, 0, V * D * H * W, D * H * W)   # (algo 0: as warp_feature)
+    g_src = torch.empty_like(g_out)
+    dev = g_out.device
+    args = (ctypes.byref(desc), ctypes.byref(cam), _dev(d_candi, "d_candi"), g_out.data_ptr(), g_src.data_ptr())
+    with _on_device(dev):
+        if deterministic:
+            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_warp_feature_backward_det_workspace_bytes")(ctypes.byref(desc)), dev)
+            rc = _entry(lib, "pdepth_warp_feature_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
+        else:
+            rc = _entry(lib, "pdepth_warp_feature_backward_f32")(*args, _stream(dev))
+    _check(rc, lib)
+    del keep
+    return g_src
 
 
 def sample_coords(K, R, t, rays, cxcy, d_candi, H, W, blas_mode=None, algo=ALGO_AUTO):

@@ -57,6 +57,20 @@ __device__ __forceinline__ uint32_t wave_max_bits(uint32_t v) {
     return v;
 }
 
+// the maximum of a wave's |q| bits into an item's header word (every lane of the wave calls)
+__device__ __forceinline__ void put_max(uint32_t m, uint32_t* __restrict__ slot) {
+    m = wave_max_bits(m);
+    if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(slot, m);
+}
+
+// the exponent of a scatter whose header word of an item is the exact maximum of |q| over its contributions (scatter_det.hip,
+// warp_bwd.hip); n: the most contributions one destination can receive
+struct MaxExponent {
+    static constexpr int WORDS = 1;
+    long long n;
+    __device__ int operator()(const uint32_t* h) const { return det_scale_exponent(__uint_as_float(h[0]), n); }
+};
+
 // rn(2^S q): the product is exact in double, the rounding is to nearest, ties to even
 __device__ __forceinline__ long long det_quantise(float q, int S) { return (long long)__builtin_rint(__builtin_ldexp((double)q, S)); }
 

@@ -138,6 +138,11 @@ hipError_t launch_sweep_backward_det(const SweepArgs& a, const float* grad_cost,
 // warp.hip
 hipError_t launch_warp_feature(const SweepArgs& a, float* out, hipStream_t stream);
 hipError_t launch_sample_coords(const SweepArgs& a, float* ix, float* iy, hipStream_t stream);
+// warp_bwd.hip: gradient of launch_warp_feature with respect to src (grad_out, grad_src [B,V,D,H,W] contiguous; a.src is not read):
+// float atomics into grad_src, zeroed by the launcher, or -- _det -- an order-independent integer sum in the workspace
+hipError_t launch_warp_feature_backward(const SweepArgs& a, const float* grad_out, float* grad_src, hipStream_t stream);
+size_t warp_feature_backward_det_workspace_bytes(int B, int V, int D, int H, int W);
+hipError_t launch_warp_feature_backward_det(const SweepArgs& a, const float* grad_out, float* grad_src, void* workspace, hipStream_t stream);
 
 // ufield.hip
 size_t ufield_workspace_bytes(int B, int H, int W);

@@ -27,20 +27,9 @@ namespace {
 
 using namespace fixed;
 
-// the header word of an item is the maximum of |q| over its contributions; n: the N of the scatter's exponent
-struct MaxExponent {
-    static constexpr int WORDS = 1;
-    long long n;
-    __device__ int operator()(const uint32_t* h) const { return det_scale_exponent(__uint_as_float(h[0]), n); }
-};
+// the header word of an item is the maximum of |q| over its contributions (fixed_accum.hpp: MaxExponent, put_max)
 size_t workspace_bytes(int B, size_t per_item) { return det_workspace_bytes(B, MaxExponent::WORDS, per_item); }
 unsigned long long* accumulator(void* workspace, int B) { return det_accumulator(workspace, B, MaxExponent::WORDS); }
-
-// the maximum of a wave's |q| bits into the item's header word (every lane of the wave calls)
-__device__ __forceinline__ void put_max(uint32_t m, uint32_t* __restrict__ slot) {
-    m = wave_max_bits(m);
-    if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(slot, m);
-}
 
 // PASS 0: maximum of |v|; PASS 1: scatter.  grid (blocks of 256 pixels, B)
 template <int PASS>

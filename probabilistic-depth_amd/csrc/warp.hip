@@ -8,33 +8,26 @@
 
 #include "geometry.hpp"
 #include "kernels.hpp"
+#include "warp_sample.hpp"
 
 namespace pdepth {
 
-// grid (pixel blocks, V * nchunk, B): a thread takes planes chunk, chunk + nchunk, ... of its pixel -- on the model's small
-// maps (64x128) one thread per pixel walking all D planes leaves the chip a block per CU and a chain of dependent gathers.
+using namespace warp_sample;
+
+// grid (pixel blocks, V * nchunk, B): a thread takes planes chunk, chunk + nchunk, ... of its pixel (warp_sample.hpp, with the
+// per-sample chain the backward of warp_bwd.hip shares)
 __global__ __launch_bounds__(256) void warp_feature_kernel(SweepArgs a, int nchunk, float* __restrict__ out) {
     const int HW = a.H * a.W;
     const int pix = blockIdx.x * 256 + threadIdx.x;
     if (pix >= HW) return;
     const int v = blockIdx.y / nchunk, chunk = blockIdx.y - v * nchunk;
     const int b = blockIdx.z;
-    ViewXform xf;
-    make_view_xform(a.K + b * 9, a.R + ((size_t)b * a.V + v) * 9, a.t + ((size_t)b * a.V + v) * 3, a.blas_mode, xf);
-    float t2a, t2b, t2c;
-    ray_term2(xf, a.rays[((size_t)b * 3 + 0) * HW + pix], a.rays[((size_t)b * 3 + 1) * HW + pix],
-              a.rays[((size_t)b * 3 + 2) * HW + pix], t2a, t2b, t2c);
-    const float cx = a.cxcy[b * 2 + 0], cy = a.cxcy[b * 2 + 1];
-    const float half_w = (float)a.W / 2.0f, half_h = (float)a.H / 2.0f;
-    const float rcx = refined_rcp(cx), rcy = refined_rcp(cy);
+    PixelChain c;
+    make_pixel_chain(a, b, v, pix, c);
     const float* srcv = a.src + (size_t)b * a.src_bstride + (size_t)v * a.src_vstride;
     float* o = out + (((size_t)b * a.V + v) * a.D) * HW + pix;
     for (int k = chunk; k < a.D; k += nchunk) {
-        float ix, iy;
-        // (the fast divide chain is bit-identical to the IEEE one wherever a tap can land inside the image: geometry.hpp)
-        if (a.fast_div) plane_sample_pos_fast(xf, t2a, t2b, t2c, a.d_candi[k], cx, cy, rcx, rcy, half_w, half_h, ix, iy);
-        else plane_sample_pos(xf, t2a, t2b, t2c, a.d_candi[k], cx, cy, half_w, half_h, ix, iy);
-        const Footprint f = make_footprint(ix, iy, a.W, a.H);
+        const Footprint f = plane_footprint(a, c, k);
         const float* s = srcv + (size_t)k * HW + (f.y0 * a.W + f.x0);
         const float vnw = (f.mask & 1u) ? s[0] : 0.0f;
         const float vne = (f.mask & 2u) ? s[1] : 0.0f;
@@ -55,32 +48,21 @@ __global__ __launch_bounds__(256) void sample_coords_kernel(SweepArgs a, float* 
     if (pix >= HW) return;
     const int v = blockIdx.y;
     const int b = blockIdx.z;
-    ViewXform xf;
-    make_view_xform(a.K + b * 9, a.R + ((size_t)b * a.V + v) * 9, a.t + ((size_t)b * a.V + v) * 3, a.blas_mode, xf);
-    float t2a, t2b, t2c;
-    ray_term2(xf, a.rays[((size_t)b * 3 + 0) * HW + pix], a.rays[((size_t)b * 3 + 1) * HW + pix],
-              a.rays[((size_t)b * 3 + 2) * HW + pix], t2a, t2b, t2c);
-    const float cx = a.cxcy[b * 2 + 0], cy = a.cxcy[b * 2 + 1];
-    const float half_w = (float)a.W / 2.0f, half_h = (float)a.H / 2.0f;
+    PixelChain c;
+    make_pixel_chain(a, b, v, pix, c);
     const size_t base = (((size_t)b * a.V + v) * a.D) * HW + pix;
-    const float rcx = refined_rcp(cx), rcy = refined_rcp(cy);
     for (int k = 0; k < a.D; ++k) {
         float ix, iy;
-        if (a.fast_div) plane_sample_pos_fast(xf, t2a, t2b, t2c, a.d_candi[k], cx, cy, rcx, rcy, half_w, half_h, ix, iy);
-        else plane_sample_pos(xf, t2a, t2b, t2c, a.d_candi[k], cx, cy, half_w, half_h, ix, iy);
+        if (a.fast_div) plane_sample_pos_fast(c.xf, c.t2a, c.t2b, c.t2c, a.d_candi[k], c.cx, c.cy, c.rcx, c.rcy, c.half_w, c.half_h, ix, iy);
+        else plane_sample_pos(c.xf, c.t2a, c.t2b, c.t2c, a.d_candi[k], c.cx, c.cy, c.half_w, c.half_h, ix, iy);
         oix[base + (size_t)k * HW] = ix;
         oiy[base + (size_t)k * HW] = iy;
     }
 }
 
 hipError_t launch_warp_feature(const SweepArgs& a, float* out, hipStream_t stream) {
-    const int pixblocks = (a.H * a.W + 255) / 256;
-    long long nchunk = 2048 / ((long long)pixblocks * a.V * a.B);   // at least ~8 blocks per CU
-    nchunk = nchunk < 1 ? 1 : nchunk > 16 ? 16 : nchunk;
-    if (nchunk > a.D) nchunk = a.D;
-    if ((long long)a.V * nchunk > 65535) nchunk = 1;
-    dim3 grid(pixblocks, a.V * (int)nchunk, a.B);
-    hipLaunchKernelGGL(warp_feature_kernel, grid, dim3(256), 0, stream, a, (int)nchunk, out);
+    const int nchunk = plane_chunks(a);
+    hipLaunchKernelGGL(warp_feature_kernel, grid(a, nchunk), dim3(256), 0, stream, a, nchunk, out);
     return hipGetLastError();
 }
 

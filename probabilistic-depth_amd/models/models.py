@@ -236,13 +236,13 @@ class _SweepFeatures:
 
 
 class BaseModel(nn.Module):
-    """Host model.  nmodes "default" and "default_upsample" train: with grad mode on, the sweep, the DPV reductions and the
-    DPV fusion run through their HIP backward passes (ops: gradients with respect to the feature maps and the volumes; the
-    sweep then takes the concatenated NCHW features; the sparse depth maps and masks of the fusion are data), so forward +
-    loss.backward() work as in the reference's training loop (trainer/default_trainer.py:87-169).
-    nmode "default_feedback" is inference-only: warp_feature has no backward and raises if an input requires grad while
-    grad mode is on; wrap that call in torch.no_grad() as the reference's evaluation loop does
-    (trainer/default_trainer.py:171)."""
+    """Host model.  All three nmodes -- "default", "default_upsample" and "default_feedback" -- train: with grad mode on, the
+    sweep, the DPV reductions, the DPV fusion and the feedback path's warp_feature run through their HIP backward passes (ops:
+    gradients with respect to the feature maps and the volumes; the sweep then takes the concatenated NCHW features; the
+    sparse depth maps and masks of the fusion are data), so forward + loss.backward() work as in the reference's training loop
+    (trainer/default_trainer.py:87-169).  In "default_feedback" the caller detaches prev_output between frames, as that loop
+    does (trainer/default_trainer.py:144-146).  sweep_deterministic selects the bit-reproducible sums of the sweep's and the
+    warp's scattered gradients."""
 
     def __init__(self, cfg, id):
         super().__init__()
@@ -356,8 +356,9 @@ class BaseModel(nn.Module):
         cost_volumes = self._sweep(feats, model_input)
         K, poses, rays, cxcy = self._camera(model_input)
         # all views incl. the reference (identity pose), channel i warped with plane i (models.py:613-629)
+        det = {} if self.sweep_deterministic is None else {"deterministic": self.sweep_deterministic}   # (None: the op's default)
         warped = ops.warp_feature(raw.float(), K, poses[:, :, :3, :3], poses[:, :, :3, 3], rays, cxcy, model_input["d_candi"],
-                                  blas=self.sweep_blas)
+                                  blas=self.sweep_blas, differentiable=True, **det)
         BV = self._low_res_dpv(cost_volumes, model_input["d_candi"])
         last = [feats[:, -1, :-3], half[:, -1]]
         first = [feats[:, 0, :-3], half[:, 0]]

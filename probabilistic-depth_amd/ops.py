@@ -303,10 +303,21 @@ def dpv_moments(dpv, d_candi, BV_log=True):
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
 
 
-def warp_feature(src, K, R, t, rays, cxcy, d_candi, blas=None):
-    """[B,V,D,H,W] diagonal warp (warping/homography.py:137-168, batched)."""
-    return _native.warp_feature(src, K, R, t, rays, cxcy, d_candi_tensor(d_candi, src.device),
-                                blas_mode=BLAS_MODES[blas])
+def warp_feature(src, K, R, t, rays, cxcy, d_candi, blas=None, differentiable=False, deterministic=None):
+    """[B,V,D,H,W] diagonal warp (warping/homography.py:137-168, batched).
+
+    differentiable=False (the default): the no-grad kernel call, which refuses a src that requires grad while grad mode is on.
+    differentiable=True: when src requires grad the call runs under autograd -- the same forward kernel, bit for bit, and the
+    backward of csrc/warp_bwd.hip with respect to src (the geometry and the candidates are data and are refused when they
+    require grad); when nothing requires grad it is the no-grad call.
+    deterministic: the gradient of src as an order-independent integer sum (bit-reproducible) instead of float atomics,
+    None = torch.are_deterministic_algorithms_enabled() when the op is called."""
+    dc = d_candi_tensor(d_candi, src.device)
+    if differentiable:
+        _refuse_grad("warp_feature", K=K, R=R, t=t, rays=rays, cxcy=cxcy, d_candi=d_candi)
+        if _wants_grad(src):
+            return _WarpFeatureFn.apply(src, K, R, t, rays, cxcy, dc, BLAS_MODES[blas], _deterministic(deterministic))
+    return _native.warp_feature(src, K, R, t, rays, cxcy, dc, blas_mode=BLAS_MODES[blas])
 
 
 def sample_coords(K, R, t, rays, cxcy, d_candi, H, W, blas=None, algo=_native.ALGO_AUTO):
@@ -337,9 +348,11 @@ def dpv_fuse(logp, dmaps, masks, d_candi, var=0.3, eps=None, want_fused=True, wa
 # ---- autograd ---------------------------------------------------------------------------------------------------------------
 # The public functions above take the autograd path only when grad mode is on and a feature / volume input requires grad;
 # every other call runs the no-grad code unchanged.  The Functions' forwards call the same _native forwards (same algo), so
-# values are bit-identical to the no-grad call; their backwards are the HIP kernels of csrc/sweep_bwd.hip, csrc/dpv_bwd.hip and
-# csrc/dpv_fuse_bwd.hip.
-# Differentiable: the feature maps (ref, NCHW src), logits, addend, the DPV of dpv_expect, the log-DPV of dpv_fuse.  Not differentiable: the geometry
+# values are bit-identical to the no-grad call; their backwards are the HIP kernels of csrc/sweep_bwd.hip, csrc/dpv_bwd.hip,
+# csrc/dpv_fuse_bwd.hip and csrc/warp_bwd.hip.  warp_feature alone takes that path only on request (differentiable=True: the model
+# and the reference-signature wrapper pass it); its plain call keeps refusing a src that requires grad.
+# Differentiable: the feature maps (ref, NCHW src), logits, addend, the DPV of dpv_expect, the log-DPV of dpv_fuse, the src of
+# warp_feature.  Not differentiable: the geometry
 # (K, R, t, rays, cxcy, d_candi -- the reference's training takes them from the data loader), which is refused when it
 # requires grad.  Every backward is once_differentiable: a second-order gradient through a HIP backward raises, it is not a constant.
 
@@ -409,6 +422,30 @@ class _SweepFn(torch.autograd.Function):
             g_ref, g_src = _native.sweep_backward(ref, src, K, R, t, rays, cxcy, dc, g, sigma, metric, want_ref=want_ref,
                                                   want_src=want_src, blas_mode=blas_mode, deterministic=deterministic)
         return (g_ref, g_src) + (None,) * 14
+
+
+class _WarpFeatureFn(torch.autograd.Function):
+    """warp_feature(differentiable=True) under autograd.  The warp is linear in src: the backward needs the geometry only, and
+    returns a gradient in src's shape (an expanded view is summed over by autograd)."""
+
+    @staticmethod
+    def forward(ctx, src, K, R, t, rays, cxcy, dc, blas_mode, deterministic):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(K, R, t, rays, cxcy, dc)
+        ctx.cfg = (blas_mode, deterministic)
+        with torch.no_grad():   # (the kernel of the no-grad call: the same bits)
+            return _native.warp_feature(src, K, R, t, rays, cxcy, dc, blas_mode=blas_mode)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        if g_out is None:
+            return (None,) * 9
+        K, R, t, rays, cxcy, dc = ctx.saved_tensors
+        blas_mode, deterministic = ctx.cfg
+        g = _native.warp_feature_backward(g_out.float().contiguous(), K, R, t, rays, cxcy, dc, blas_mode=blas_mode,
+                                          deterministic=deterministic)
+        return (g,) + (None,) * 8
 
 
 class _DpvReduceFn(torch.autograd.Function):

@@ -44,7 +44,7 @@ def est_swp_volume_v4(feat_img_ref, feat_img_src, d_candi, R, t, cam_intrinsic, 
 def warp_feature(feat_img_src, d_candi, R, t, cam_intrinsic, blas=None):
     r"""
     feat_img_src - NVCHW tensor (N == 1, C == len(d_candi)); channel i is warped with plane i
-    returns [1, V, C, H, W]
+    returns [1, V, C, H, W]; differentiable in feat_img_src, like the reference's (csrc/warp_bwd.hip)
     """
     if feat_img_src.shape[0] != 1:
         raise Exception("Warped Accum Error")
@@ -53,7 +53,7 @@ def warp_feature(feat_img_src, d_candi, R, t, cam_intrinsic, blas=None):
     K, rays, cxcy = _camera_tensors(cam_intrinsic, device)
     R = R.to(device=device, dtype=torch.float32).reshape(1, V, 3, 3)
     t = t.to(device=device, dtype=torch.float32).reshape(1, V, 3)
-    return ops.warp_feature(feat_img_src, K, R, t, rays, cxcy, d_candi, blas=blas)
+    return ops.warp_feature(feat_img_src, K, R, t, rays, cxcy, d_candi, blas=blas, differentiable=True)
 
 
 def get_rel_extrinsicM(ext_ref, ext_src):
