@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dpv_fuse_math.hpp"
+#include "fixed_accum.hpp"
 #include "geometry.hpp"
 #include "inverse_warp_math.hpp"
 #include "kernels.hpp"
@@ -488,7 +489,8 @@ hipError_t launch_correlation_backward(const float* x1, const float* x2, const f
 // (like ATen's grid_sampler backward) and the gradient with respect to the projected point (X, Y, Z) written per
 // pixel; the 3x3 / 3x4 algebra behind it (depth, pose, intrinsics) is a handful of small matmuls on the host side.
 // ---------------------------------------------------------------------------------------------------
-// The per-pixel chain (WarpSample, warp_sample, warp_valid, nearest_tap) is inverse_warp_math.hpp, shared with loss_terms.hip.
+// The per-pixel chain (warp_sample, warp_valid, nearest_tap; tap_mask, load_texels, bilinear_value and its derivatives, point_grad;
+// the scatter bodies scatter_taps / scatter_sample) is inverse_warp_math.hpp, shared with loss_terms.hip and scatter_det.hip.
 
 template <int MODE>   // 0 bilinear, 1 nearest
 __global__ __launch_bounds__(256) void inverse_warp_kernel(const float* __restrict__ img,
@@ -510,14 +512,8 @@ __global__ __launch_bounds__(256) void inverse_warp_kernel(const float* __restri
         return;
     }
     const float* ib = img + (size_t)b * C * HW + (q.y0 * W + q.x0);
-    for (int c = 0; c < C; ++c) {
-        const float* p = ib + (size_t)c * HW;
-        const float v00 = (q.finite && q.xi0 && q.yi0) ? p[0] : 0.0f;
-        const float v01 = (q.finite && q.xi1 && q.yi0) ? p[1] : 0.0f;
-        const float v10 = (q.finite && q.xi0 && q.yi1) ? p[W] : 0.0f;
-        const float v11 = (q.finite && q.xi1 && q.yi1) ? p[W + 1] : 0.0f;
-        ob[(size_t)c * HW] = __builtin_fmaf(v11, q.se, __builtin_fmaf(v10, q.sw, __builtin_fmaf(v01, q.ne, v00 * q.nw)));
-    }
+    const TapMask taps = tap_mask(q);
+    for (int c = 0; c < C; ++c) ob[(size_t)c * HW] = bilinear_value(q, load_texels(ib + (size_t)c * HW, taps, W));
 }
 
 // grad_img [B,C,H,W] (zeroed by the launcher, atomics; may be NULL), grad_pc [B,3,H,W] = dL/d(X, Y, Z) of the
@@ -536,42 +532,28 @@ __global__ __launch_bounds__(256) void inverse_warp_bwd_kernel(const float* __re
     const int y = pix / W, x = pix - y * W;
     const WarpSample q = warp_sample(Kinv + b * 9, proj + b * 12, x, y, depth[(size_t)b * HW + pix], H, W);
     const float* gb = go + (size_t)b * C * HW + pix;
+    const long long image0 = (long long)b * C * HW;
+    fixed::FloatAtomics sink{grad_img};
     float gix = 0.0f, giy = 0.0f;
     if (MODE == 1) {
-        const int tap = nearest_tap(q, H, W);
-        if (grad_img && tap >= 0)
-            for (int c = 0; c < C; ++c) atomicAdd(grad_img + ((size_t)b * C + c) * HW + tap, gb[(size_t)c * HW]);
+        if (grad_img) scatter_sample<1>(q, true, gb, image0, C, H, W, sink);
     } else {
-        const size_t base = (size_t)b * C * HW + (q.y0 * W + q.x0);
-        const bool t00 = q.finite && q.xi0 && q.yi0, t01 = q.finite && q.xi1 && q.yi0;
-        const bool t10 = q.finite && q.xi0 && q.yi1, t11 = q.finite && q.xi1 && q.yi1;
+        // the channel loop of scatter_sample<0>, kept here: one load of g and of the texels feeds the position gradient and the scatter
+        const long long base = image0 + (q.y0 * W + q.x0);
+        const TapMask taps = tap_mask(q);
         for (int c = 0; c < C; ++c) {
             const float g = gb[(size_t)c * HW];
-            const float* p = img + base + (size_t)c * HW;
-            const float v00 = t00 ? p[0] : 0.0f, v01 = t01 ? p[1] : 0.0f, v10 = t10 ? p[W] : 0.0f, v11 = t11 ? p[W + 1] : 0.0f;
-            // d out / d ix = (v01 - v00) s + (v11 - v10) n,  d out / d iy = (v10 - v00) e + (v11 - v01) w
-            gix = __builtin_fmaf(g, __builtin_fmaf(v11 - v10, q.n, (v01 - v00) * q.s), gix);
-            giy = __builtin_fmaf(g, __builtin_fmaf(v11 - v01, q.w, (v10 - v00) * q.e), giy);
-            if (grad_img) {
-                float* gi = grad_img + base + (size_t)c * HW;
-                if (t00) atomicAdd(gi, g * q.nw);
-                if (t01) atomicAdd(gi + 1, g * q.ne);
-                if (t10) atomicAdd(gi + W, g * q.sw);
-                if (t11) atomicAdd(gi + W + 1, g * q.se);
-            }
+            const Texels v = load_texels(img + base + (long long)c * HW, taps, W);
+            gix = __builtin_fmaf(g, bilinear_d_ix(q, v), gix);
+            giy = __builtin_fmaf(g, bilinear_d_iy(q, v), giy);
+            if (grad_img) scatter_taps(q, taps, base + (long long)c * HW, W, g, sink);
         }
     }
     if (grad_pc) {
-        // ix = ((xn + 1) W - 1) / 2, xn = 2 (X / Z) / (W - 1) - 1, Z = max(pz, 1e-3) (clamp passes the gradient for pz >= 1e-3)
-        float gX = 0.0f, gY = 0.0f, gZ = 0.0f;
-        if (MODE == 0 && q.finite) {
-            const float gxn = gix * ((float)W / 2.0f), gyn = giy * ((float)H / 2.0f);
-            gX = gxn * 2.0f / ((float)(W - 1) * q.Z);
-            gY = gyn * 2.0f / ((float)(H - 1) * q.Z);
-            if (q.pz >= 1e-3f) gZ = -(gX * q.X + gY * q.Y) / q.Z;
-        }
+        PointGrad gp{0.0f, 0.0f, 0.0f};
+        if (MODE == 0 && q.finite) gp = point_grad(q, gix, giy, H, W);
         float* o = grad_pc + (size_t)b * 3 * HW + pix;
-        o[0] = gX; o[HW] = gY; o[2 * (size_t)HW] = gZ;
+        o[0] = gp.X; o[HW] = gp.Y; o[2 * (size_t)HW] = gp.Z;
     }
 }
 

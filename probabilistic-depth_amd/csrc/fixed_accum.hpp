@@ -1,4 +1,6 @@
-// Order-independent sums of fp32 contributions: exact integer accumulation (sweep_bwd_det.hip, scatter_det.hip).
+// Order-independent sums of fp32 contributions: exact integer accumulation.  Users: sweep_bwd_det.hip (exponent from a bound, its
+// own policies in sweep_bwd_body.hpp); scatter_det.hip and warp_bwd.hip (exponent from the exact maximum: the sinks,
+// max_exponent_pass and max_exponent_scatter below); extras.hip and loss_terms.hip take FloatAtomics for the same scatter bodies.
 //
 // Float addition is not associative, integer addition is.  A contribution q (fp32) is scaled by 2^S (exact: the product is
 // formed in double, whose exponent range holds every fp32 times every 2^S chosen below), rounded to the nearest integer, ties to
@@ -18,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace pdepth {
 namespace fixed {
@@ -63,8 +66,8 @@ __device__ __forceinline__ void put_max(uint32_t m, uint32_t* __restrict__ slot)
     if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(slot, m);
 }
 
-// the exponent of a scatter whose header word of an item is the exact maximum of |q| over its contributions (scatter_det.hip,
-// warp_bwd.hip); n: the most contributions one destination can receive
+// the exponent of a scatter whose header word of an item is the exact maximum of |q| over its contributions (max_exponent_pass);
+// n: the most contributions one destination can receive
 struct MaxExponent {
     static constexpr int WORDS = 1;
     long long n;
@@ -79,6 +82,44 @@ __device__ __forceinline__ void det_add(unsigned long long* dst, float q, int S)
 
 // the sum back in fp32 (two roundings at most, see above)
 __device__ __forceinline__ float det_to_float(long long acc, int S) { return (float)__builtin_ldexp((double)acc, -S); }
+
+// ---- the sinks of a scatter body: where a contribution q to element `at` of the gradient goes.  A body written against
+// add(long long at, float q) forms the same q, bit for bit, on the atomic path and in both passes of the integer sum. ------------
+struct FloatAtomics {   // atomicAdd(float*) into the gradient, zeroed first: the last bits depend on the order of arrival
+    float* __restrict__ dst;
+    __device__ __forceinline__ void add(long long at, float q) { atomicAdd(dst + at, q); }
+};
+struct MaxOfAbs {   // pass 0: the maximum of |q| of this lane
+    uint32_t m;
+    __device__ __forceinline__ void add(long long, float q) { m = max(m, abs_bits(q)); }
+};
+struct IntegerSum {   // pass 1: rn(2^S q) into the int64 accumulator
+    unsigned long long* __restrict__ acc;
+    int S;   // the exponent of the workgroup's batch item
+    __device__ __forceinline__ void add(long long at, float q) { det_add(acc + at, q, S); }
+};
+
+// One pass of a max-exponent scatter for this workgroup's batch item: body(sink) hands the lane's contributions to sink.add.
+//   PASS 0  the maximum of |q| into the item's header word (atomicMax: order-independent, a NaN or an infinity wins it);
+//   PASS 1  S = det_scale_exponent(header, n), n the most contributions one destination can receive, then the same contributions
+//           quantised with S and added to acc.
+// Every lane of every wave of the workgroup must reach this call: put_max shuffles across the wave, so a lane without a pixel
+// runs the body on a shadow pixel and adds nothing instead of returning early.  On a non-exponent (EXP_ZERO, EXP_NONFINITE) the
+// whole workgroup leaves -- the exponent is per item and a workgroup serves one item -- and the convert pass writes that item.
+template <int PASS, class Body>
+__device__ __forceinline__ void max_exponent_pass(uint32_t* __restrict__ item_header, unsigned long long* __restrict__ acc, long long n,
+                                                  Body body) {
+    if (PASS == 0) {
+        MaxOfAbs sink{0u};
+        body(sink);
+        put_max(sink.m, item_header);
+    } else {
+        const int S = det_scale_exponent(__uint_as_float(*item_header), n);
+        if (S == EXP_ZERO || S == EXP_NONFINITE) return;
+        IntegerSum sink{acc, S};
+        body(sink);
+    }
+}
 
 // ---- the workspace of an integer sum: a 256-byte-rounded header of `words` uint32 per batch item (the maxima the exponent is
 // derived from), then one int64 per element of the result, [B][per_item] --------------------------------------------------------
@@ -113,6 +154,23 @@ inline hipError_t det_convert(void* workspace, int B, size_t per_item, Exponent 
                        static_cast<const uint32_t*>(workspace),
                        reinterpret_cast<const long long*>(det_accumulator(workspace, B, Exponent::WORDS)), out, per_item);
     return hipGetLastError();
+}
+
+// The host side of a max-exponent scatter: clear the workspace (header and accumulator), pass 0, pass 1, convert into `out`
+// [B][per_item].  launch(pass, hdr, acc) launches the gradient's kernel of pass decltype(pass)::value, whose workgroups call
+// max_exponent_pass<PASS>(hdr + b, acc, n, ...) with the same n: kernel and caller take it from one function of the gradient's,
+// since a scatter and a convert that disagree on it differ by a power of two, silently.  The caller has checked the workspace
+// (det_workspace_bytes(B, MaxExponent::WORDS, per_item)); nothing else clears it.
+template <class Launch>
+inline hipError_t max_exponent_scatter(void* workspace, int B, size_t per_item, long long n, float* out, hipStream_t stream,
+                                       Launch launch) {
+    hipError_t e = hipMemsetAsync(workspace, 0, det_workspace_bytes(B, MaxExponent::WORDS, per_item), stream);
+    if (e != hipSuccess) return e;
+    uint32_t* hdr = static_cast<uint32_t*>(workspace);
+    unsigned long long* acc = det_accumulator(workspace, B, MaxExponent::WORDS);
+    launch(std::integral_constant<int, 0>{}, hdr, acc);
+    launch(std::integral_constant<int, 1>{}, hdr, acc);
+    return det_convert(workspace, B, per_item, MaxExponent{n}, out, stream);
 }
 
 }  // namespace fixed

@@ -25,7 +25,7 @@
 // backward 4 HW (1 + 3) with the neighbours from cache, backward + 4 HW written.
 //
 // Gradient rules are torch's: sign(0) = 0 behind abs, a clamp passes the gradient on min <= x <= max, masks / valid / taps are
-// constants.  Only the src_depth gradient of dsc is scattered (atomicAdd on fp32, like inverse_warp_bwd_kernel<1>); every other
+// constants.  Only the src_depth gradient of dsc is scattered (dsc_scatter into FloatAtomics: atomicAdd on fp32); every other
 // gradient is written by the thread that owns the element: the same bits from call to call.
 //
 // Pixel reduction: as loss.hip -- a workgroup (256 pixels) writes two partial sums into the workspace, a second launch of one
@@ -34,6 +34,7 @@
 
 #include "capi_util.hpp"
 #include "dpv_lanes.hpp"
+#include "fixed_accum.hpp"
 #include "inverse_warp_math.hpp"
 #include "kernels.hpp"
 #include "loss_terms_math.hpp"
@@ -77,7 +78,10 @@ __global__ __launch_bounds__(256) void loss_dsc_bwd_kernel(DscArgs g, const floa
     const int b = blockIdx.y;
     const DscGrad d = dsc_pixel_grad(g, count, g_value, b, pix);
     if (g_tgt) g_tgt[(size_t)b * HW + pix] = d.g_tgt;
-    if (g_src && d.tap >= 0 && d.v != 0.0f) atomicAdd(g_src + (size_t)b * HW + d.tap, d.v);
+    if (g_src) {
+        fixed::FloatAtomics sink{g_src};
+        dsc_scatter(d, (long long)b * HW, sink);
+    }
 }
 
 // ---- RGB stereo consistency ----------------------------------------------------------------------------------------------------
@@ -104,19 +108,17 @@ __device__ __forceinline__ RscPixel rsc_pixel(const RscArgs& g, int b, int pix, 
     p.q = warp_sample(g.Kinv + b * 9, g.proj + b * 12, x, y, g.depth[(size_t)b * HW + pix], H, W);
     const WarpSample& q = p.q;
     p.m = (warp_valid(q) && y >= H / 3) ? 1.0f : 0.0f;
-    const bool t00 = q.finite && q.xi0 && q.yi0, t01 = q.finite && q.xi1 && q.yi0;
-    const bool t10 = q.finite && q.xi0 && q.yi1, t11 = q.finite && q.xi1 && q.yi1;
+    const TapMask taps = tap_mask(q);
     const float* ib = g.src + (size_t)b * 3 * HW + (q.y0 * W + q.x0);
     const float* tb = g.tgt + (size_t)b * 3 * HW + pix;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float* s = ib + (size_t)c * HW;
-        const float v00 = t00 ? s[0] : 0.0f, v01 = t01 ? s[1] : 0.0f, v10 = t10 ? s[W] : 0.0f, v11 = t11 ? s[W + 1] : 0.0f;
-        const float warped = __builtin_fmaf(v11, q.se, __builtin_fmaf(v10, q.sw, __builtin_fmaf(v01, q.ne, v00 * q.nw)));
+        const Texels v = load_texels(ib + (size_t)c * HW, taps, W);
+        const float warped = bilinear_value(q, v);
         p.d[c] = tb[(size_t)c * HW] * p.m - warped * p.m;
         if (GRAD) {
-            p.gx[c] = __builtin_fmaf(v11 - v10, q.n, (v01 - v00) * q.s);
-            p.gy[c] = __builtin_fmaf(v11 - v01, q.w, (v10 - v00) * q.e);
+            p.gx[c] = bilinear_d_ix(q, v);
+            p.gy[c] = bilinear_d_iy(q, v);
         }
     }
     return p;
@@ -134,8 +136,8 @@ __global__ __launch_bounds__(256) void loss_rsc_kernel(RscArgs g, int B, float* 
     block_partial(num, den, part, B);
 }
 
-// The chain of inverse_warp_bwd_kernel<0> and the products behind it (the gradient of the projected point, of the camera
-// point, of the depth), per pixel in one thread.
+// The position gradient as inverse_warp_bwd_kernel<0> forms it (inverse_warp_math.hpp: the derivatives of the bilinear value,
+// point_grad) and the products behind it (the gradient of the camera point, of the depth), per pixel in one thread.
 __global__ __launch_bounds__(256) void loss_rsc_bwd_kernel(RscArgs g, const float* __restrict__ count, const float* __restrict__ g_value,
                                                            float* __restrict__ g_depth) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
@@ -155,17 +157,13 @@ __global__ __launch_bounds__(256) void loss_rsc_bwd_kernel(RscArgs g, const floa
     }
     float out = 0.0f;
     if (q.finite) {
-        // ix = ((xn + 1) W - 1) / 2, xn = 2 (X / Z) / (W - 1) - 1, Z = max(pz, 1e-3) (the clamp passes the gradient for pz >= 1e-3)
-        const float gxn = gix * ((float)W / 2.0f), gyn = giy * ((float)H / 2.0f);
-        const float gX = gxn * 2.0f / ((float)(W - 1) * q.Z);
-        const float gY = gyn * 2.0f / ((float)(H - 1) * q.Z);
-        const float gZ = q.pz >= FLOOR ? -(gX * q.X + gY * q.Y) / q.Z : 0.0f;
+        const PointGrad gp = point_grad(q, gix, giy, H, W);
         const float* ki = g.Kinv + b * 9;
         const float* pr = g.proj + b * 12;
         const float fx = (float)x, fy = (float)y;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const float gcam = __builtin_fmaf(pr[8 + j], gZ, __builtin_fmaf(pr[4 + j], gY, pr[j] * gX));
+            const float gcam = __builtin_fmaf(pr[8 + j], gp.Z, __builtin_fmaf(pr[4 + j], gp.Y, pr[j] * gp.X));
             const float cam0 = __builtin_fmaf(ki[j * 3 + 2], 1.0f, __builtin_fmaf(ki[j * 3 + 1], fy, ki[j * 3 + 0] * fx));
             out = __builtin_fmaf(gcam, cam0, out);
         }

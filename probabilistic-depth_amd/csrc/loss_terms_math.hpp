@@ -1,6 +1,6 @@
 // The per-pixel arithmetic of the loss terms that more than one unit evaluates: the clamps, the relative difference and its
 // derivatives, and the chain of the depth stereo consistency term (loss_terms.hip: forward and backward; scatter_det.hip: the
-// order-independent sum of its src_depth gradient).  Both units see the same bits of every pixel.
+// order-independent sum of its src_depth gradient, through the same dsc_scatter).  Both units see the same bits of every pixel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,7 +10,7 @@ namespace pdepth {
 
 namespace {
 
-constexpr float FLOOR = 1e-3f;   // the clamp of every depth that enters a quotient
+constexpr float FLOOR = 1e-3f;   // the clamp of every depth that enters a quotient (the warp's own: Z_FLOOR)
 
 // torch.clamp(min=lo) / torch.clamp(0, 1): a NaN stays a NaN
 __device__ __forceinline__ float clamp_min(float x, float lo) { return x < lo ? lo : x; }
@@ -109,6 +109,12 @@ __device__ __forceinline__ DscGrad dsc_pixel_grad(const DscArgs& g, const float*
         d.v = gw * p.dmoved;
     }
     return d;
+}
+
+// the contribution of one pixel to g_src [B,H,W] through a sink (fixed_accum.hpp); item0 = b H W
+template <class Sink>
+__device__ __forceinline__ void dsc_scatter(const DscGrad& d, long long item0, Sink& sink) {
+    if (d.tap >= 0 && d.v != 0.0f) sink.add(item0 + d.tap, d.v);
 }
 
 }  // namespace

@@ -2,10 +2,12 @@
 // consistency term (loss_terms.hip: loss_dsc_bwd_kernel) and grad_img of inverse_warp (extras.hip: inverse_warp_bwd_kernel, both
 // sampling modes).  The same bits from call to call, and an item's result does not depend on its neighbours in the batch.
 //
-// Both are one-thread-per-pixel kernels, so the per-pixel chain (loss_terms_math.hpp, inverse_warp_math.hpp: the expressions of
-// the atomic kernels, in their order) simply runs twice:
+// Both are one-thread-per-pixel kernels, and each has one scatter body -- dsc_scatter (loss_terms_math.hpp), scatter_sample
+// (inverse_warp_math.hpp) -- which the atomic kernels call with FloatAtomics and the kernels here with the sinks of the two passes
+// (fixed_accum.hpp: max_exponent_pass on the device, max_exponent_scatter on the host): the contributions are the atomic path's
+// bit for bit because they are formed by the same code.
 //   pass 0  the exact maximum of |q| over the contributions of an item (atomicMax over the bit patterns of |q|: order-independent,
-//           a NaN or an infinity wins it) -> S_b = det_scale_exponent(max, N), N = 4 H W (pixels x taps);
+//           a NaN or an infinity wins it) -> S_b = det_scale_exponent(max, N), N = 4 H W (pixels x taps: max_contributions);
 //   pass 1  the same contributions, quantised with S_b and added to the int64 accumulator (global_atomic_add_x2);
 //   convert accumulator -> fp32.  An item whose maximum is 0 is 0; an item with a non-finite contribution is NaN in every element
 //           (an integer cannot hold a NaN; the atomic path confines it to the texels it reaches), every other item is untouched.
@@ -29,7 +31,10 @@ using namespace fixed;
 
 // the header word of an item is the maximum of |q| over its contributions (fixed_accum.hpp: MaxExponent, put_max)
 size_t workspace_bytes(int B, size_t per_item) { return det_workspace_bytes(B, MaxExponent::WORDS, per_item); }
-unsigned long long* accumulator(void* workspace, int B) { return det_accumulator(workspace, B, MaxExponent::WORDS); }
+
+// the most contributions one element of either gradient can receive: every pixel of the map, four taps each (the kernels' and
+// the convert pass's exponents both come from it)
+__host__ __device__ inline long long max_contributions(int H, int W) { return 4ll * H * W; }
 
 // PASS 0: maximum of |v|; PASS 1: scatter.  grid (blocks of 256 pixels, B)
 template <int PASS>
@@ -38,20 +43,9 @@ __global__ __launch_bounds__(256) void dsc_det_kernel(DscArgs g, const float* __
     const int pix = blockIdx.x * 256 + threadIdx.x;
     const int HW = g.H * g.W;
     const int b = blockIdx.y;
-    float v = 0.0f;
-    int tap = -1;
-    if (pix < HW) {
-        const DscGrad d = dsc_pixel_grad(g, count, g_value, b, pix);
-        tap = d.tap;
-        v = tap >= 0 ? d.v : 0.0f;
-    }
-    if (PASS == 0) {
-        put_max(abs_bits(v), hdr + b);
-    } else {
-        const int S = det_scale_exponent(__uint_as_float(hdr[b]), 4ll * HW);
-        if (S == EXP_ZERO || S == EXP_NONFINITE) return;
-        if (tap >= 0 && v != 0.0f) det_add(acc + (size_t)b * HW + tap, v, S);
-    }
+    DscGrad d{0.0f, 0.0f, -1};   // a lane past the map: no tap
+    if (pix < HW) d = dsc_pixel_grad(g, count, g_value, b, pix);
+    max_exponent_pass<PASS>(hdr + b, acc, max_contributions(g.H, g.W), [&](auto& sink) { dsc_scatter(d, (long long)b * HW, sink); });
 }
 
 // grad_img of inverse_warp_bwd_kernel<MODE>: q = g (nearest) / g w_t (bilinear) at the in-bounds taps
@@ -66,47 +60,9 @@ __global__ __launch_bounds__(256) void inverse_warp_det_kernel(const float* __re
     const int pc = live ? pix : HW - 1;   // dead lanes shadow the last pixel and add nothing
     const int y = pc / W, x = pc - y * W;
     const WarpSample q = warp_sample(Kinv + b * 9, proj + b * 12, x, y, depth[(size_t)b * HW + pc], H, W);
-    const float* gb = go + (size_t)b * C * HW + pc;
-    int S = 0;
-    if (PASS == 1) {
-        S = det_scale_exponent(__uint_as_float(hdr[b]), 4ll * HW);
-        if (S == EXP_ZERO || S == EXP_NONFINITE) return;
-    }
-    uint32_t m = 0u;
-    if (MODE == 1) {
-        const int tap = live ? nearest_tap(q, H, W) : -1;
-        if (tap >= 0) {
-            for (int c = 0; c < C; ++c) {
-                const float g = gb[(size_t)c * HW];
-                if (PASS == 0) m = max(m, abs_bits(g));
-                else det_add(acc + ((size_t)b * C + c) * HW + tap, g, S);
-            }
-        }
-    } else {
-        const size_t base = (size_t)b * C * HW + (q.y0 * W + q.x0);
-        const bool ok = live && q.finite;
-        const bool t00 = ok && q.xi0 && q.yi0, t01 = ok && q.xi1 && q.yi0;
-        const bool t10 = ok && q.xi0 && q.yi1, t11 = ok && q.xi1 && q.yi1;
-        if (t00 || t01 || t10 || t11) {
-            for (int c = 0; c < C; ++c) {
-                const float g = gb[(size_t)c * HW];
-                const float q00 = g * q.nw, q01 = g * q.ne, q10 = g * q.sw, q11 = g * q.se;
-                if (PASS == 0) {
-                    if (t00) m = max(m, abs_bits(q00));
-                    if (t01) m = max(m, abs_bits(q01));
-                    if (t10) m = max(m, abs_bits(q10));
-                    if (t11) m = max(m, abs_bits(q11));
-                } else {
-                    unsigned long long* gi = acc + base + (size_t)c * HW;
-                    if (t00) det_add(gi, q00, S);
-                    if (t01) det_add(gi + 1, q01, S);
-                    if (t10) det_add(gi + W, q10, S);
-                    if (t11) det_add(gi + W + 1, q11, S);
-                }
-            }
-        }
-    }
-    if (PASS == 0) put_max(m, hdr + b);
+    const long long image0 = (long long)b * C * HW;
+    max_exponent_pass<PASS>(hdr + b, acc, max_contributions(H, W),
+                            [&](auto& sink) { scatter_sample<MODE>(q, live, go + image0 + pc, image0, C, H, W, sink); });
 }
 
 }  // namespace
@@ -149,15 +105,12 @@ int pdepth_loss_dsc_backward_det_f32(const float* src_depth, const float* tgt_de
     }
     if (!g_src_depth) return PDEPTH_OK;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes(B, per_item), s);
-    if (e != hipSuccess) return launched(e, who);
     const DscArgs a{src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, pose_batched ? 4 : 0, H, W};
-    uint32_t* hdr = static_cast<uint32_t*>(workspace);
-    unsigned long long* acc = accumulator(workspace, B);
     const dim3 grid((unsigned)((per_item + 255) / 256), B);
-    hipLaunchKernelGGL(dsc_det_kernel<0>, grid, dim3(256), 0, s, a, count, g_value, hdr, acc);
-    hipLaunchKernelGGL(dsc_det_kernel<1>, grid, dim3(256), 0, s, a, count, g_value, hdr, acc);
-    return launched(det_convert(workspace, B, per_item, MaxExponent{4ll * (long long)per_item}, g_src_depth, s), who);
+    auto launch = [&](auto pass, uint32_t* hdr, unsigned long long* acc) {
+        hipLaunchKernelGGL(dsc_det_kernel<decltype(pass)::value>, grid, dim3(256), 0, s, a, count, g_value, hdr, acc);
+    };
+    return launched(max_exponent_scatter(workspace, B, per_item, max_contributions(H, W), g_src_depth, s, launch), who);
 }
 
 int pdepth_inverse_warp_backward_det_f32(const float* img, const float* depth, const float* Kinv, const float* proj, const float* grad_out,
@@ -180,18 +133,13 @@ int pdepth_inverse_warp_backward_det_f32(const float* img, const float* depth, c
             return rc;
     }
     if (!grad_img) return PDEPTH_OK;
-    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes(B, per_item), s);
-    if (e != hipSuccess) return launched(e, who);
-    uint32_t* hdr = static_cast<uint32_t*>(workspace);
-    unsigned long long* acc = accumulator(workspace, B);
     const dim3 grid((unsigned)(((size_t)H * W + 255) / 256), B);
-    auto go = [&](auto k0, auto k1) {
-        hipLaunchKernelGGL(k0, grid, dim3(256), 0, s, depth, Kinv, proj, grad_out, C, H, W, hdr, acc);
-        hipLaunchKernelGGL(k1, grid, dim3(256), 0, s, depth, Kinv, proj, grad_out, C, H, W, hdr, acc);
+    auto launch = [&](auto pass, uint32_t* hdr, unsigned long long* acc) {
+        constexpr int PASS = decltype(pass)::value;
+        auto kern = mode == PDEPTH_SAMPLE_BILINEAR ? inverse_warp_det_kernel<0, PASS> : inverse_warp_det_kernel<1, PASS>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, depth, Kinv, proj, grad_out, C, H, W, hdr, acc);
     };
-    if (mode == PDEPTH_SAMPLE_BILINEAR) go(inverse_warp_det_kernel<0, 0>, inverse_warp_det_kernel<0, 1>);
-    else go(inverse_warp_det_kernel<1, 0>, inverse_warp_det_kernel<1, 1>);
-    return launched(det_convert(workspace, B, per_item, MaxExponent{4ll * H * W}, grad_img, s), who);
+    return launched(max_exponent_scatter(workspace, B, per_item, max_contributions(H, W), grad_img, s, launch), who);
 }
 
 }  // extern "C"

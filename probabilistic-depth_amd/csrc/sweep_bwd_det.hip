@@ -4,8 +4,8 @@
 // The contributions are those of the g_src pass of sweep_bwd.hip, bit for bit, by construction: both kernels are the one body of
 // sweep_bwd_body.hpp (sample positions and footprints, the per-channel chain, the 16 x 16 tiles, per-plane boxes, plane groups
 // staged through an LDS box image, direct adds for a plane whose box alone exceeds the cap, the channel tail).  What differs is
-// the policy (IntegerSum, fixed_accum.hpp): a contribution q is scaled by 2^S_b, rounded to an integer and added with integer
-// atomics -- ds_add_u64 into the box image, global_atomic_add_x2 into the accumulator of the workspace --, 4 channels per pass,
+// the policy (sweep_bwd::IntegerSum, over fixed_accum.hpp): a contribution q is scaled by 2^S_b, rounded to an integer and added
+// with integer atomics -- ds_add_u64 into the box image, global_atomic_add_x2 into the accumulator of the workspace --, 4 channels per pass,
 // and a last pass converts the accumulator into g_src.
 //
 // Launch sequence, all on the caller's stream, no host synchronisation, no copy to the host:
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(BTHREADS) void sweep_bwd_det_kernel(SweepArgs a, co
                                                                  unsigned long long* __restrict__ acc) {
     const int S = ItemExponent(a, METRIC)(hdr + HDR_WORDS * blockIdx.y);
     if (S == EXP_ZERO || S == EXP_NONFINITE) return;   // (the whole workgroup: the convert pass writes this item)
-    sweep_bwd_body<METRIC, false>(a, gcost, nullptr, acc, IntegerSum{S});
+    sweep_bwd_body<METRIC, false>(a, gcost, nullptr, acc, sweep_bwd::IntegerSum{S});
 }
 
 }  // namespace
@@ -105,11 +105,11 @@ hipError_t launch_sweep_backward_det(const SweepArgs& a, const float* grad_cost,
     const unsigned nblk = (unsigned)(want < 512 ? want : 512);
     hipLaunchKernelGGL(sweep_det_bounds_kernel, dim3(nblk, a.B, a.metric == 0 ? 3 : 1), dim3(256), 0, stream, a, grad_cost, hdr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    const size_t lds = lds_bytes<IntegerSum>(a.D);
+    const size_t lds = lds_bytes<sweep_bwd::IntegerSum>(a.D);
     auto go = [&](auto kern) -> hipError_t {
         hipError_t err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (err != hipSuccess) return err;
-        hipLaunchKernelGGL(kern, grid<IntegerSum>(a), dim3(BTHREADS), lds, stream, a, grad_cost, hdr, acc);
+        hipLaunchKernelGGL(kern, grid<sweep_bwd::IntegerSum>(a), dim3(BTHREADS), lds, stream, a, grad_cost, hdr, acc);
         return hipGetLastError();
     };
     e = a.metric == 0 ? go(sweep_bwd_det_kernel<0>) : go(sweep_bwd_det_kernel<1>);

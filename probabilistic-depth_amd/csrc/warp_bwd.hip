@@ -8,17 +8,15 @@
 // follow ATen's grid_sampler_2d backward: an in-bounds tap receives g w even when w == 0 (an infinite g then leaves a NaN there),
 // an out-of-bounds tap receives nothing, a non-finite position has no tap (mask 0).
 //
-// One body (warp_bwd_body), three sinks for a contribution q = g w:
+// One body (warp_bwd_body) for a contribution q = g w, handed to one of the three sinks of fixed_accum.hpp:
 //   FloatAtomics  atomicAdd(float*) into g_src, zeroed on the stream first (one global_atomic_add_f32, no compare-and-swap loop).
 //                 The grid is the forward's: the lanes of a wave are 64 consecutive pixels of one plane, whose taps fall on
 //                 contiguous texel segments for the model's poses.  16 bytes of adds per sample: 67 MB at B = 4, V + 1 = 2, D = 64,
 //                 64 x 128.  The last bits depend on the order of arrival.
-//   MaxOfAbs      pass 0 of the deterministic path: the exact maximum of |q| per batch item, atomicMax over the bit patterns
-//                 (order-independent; a NaN or an infinity wins it) -> S_b = det_scale_exponent(max, N), N = H W: a sample puts at
-//                 most one of its taps on any texel of its own (b,v,k) image.
-//   IntegerSum    pass 1: rn(2^S_b q) added to the int64 accumulator of the workspace (fixed_accum.hpp), then det_convert.  An item
-//                 whose maximum is 0 is exactly 0; an item with a non-finite contribution is NaN in every element; every other
-//                 item is untouched by it -- as the other _det entries (scatter_det.hip).
+//   MaxOfAbs, IntegerSum  the two passes of the deterministic path (max_exponent_pass, max_exponent_scatter): S_b from the exact
+//                 maximum of |q| of the item and N = H W -- a sample puts at most one of its taps on any texel of its own
+//                 (b,v,k) image.  An item whose maximum is 0 is exactly 0; an item with a non-finite contribution is NaN in every
+//                 element; every other item is untouched by it -- as the other _det entries (scatter_det.hip).
 // Workspace of the deterministic path: a 256-byte-rounded header of 4 bytes per item, then one int64 per element of g_src.
 #include <hip/hip_runtime.h>
 
@@ -36,19 +34,8 @@ using namespace warp_sample;
 
 constexpr int MAX_PLANES = 512;   // as the sweep's backward
 
-struct FloatAtomics {
-    float* __restrict__ dst;
-    __device__ __forceinline__ void add(long long at, float q) { atomicAdd(dst + at, q); }
-};
-struct MaxOfAbs {
-    uint32_t m;
-    __device__ __forceinline__ void add(long long, float q) { m = max(m, abs_bits(q)); }
-};
-struct IntegerSum {
-    unsigned long long* __restrict__ acc;
-    int S;   // the exponent of the workgroup's batch item
-    __device__ __forceinline__ void add(long long at, float q) { det_add(acc + at, q, S); }
-};
+// the most contributions a texel can receive (the kernel's and the convert pass's exponents both come from it)
+__host__ __device__ inline long long max_contributions(const SweepArgs& a) { return (long long)a.H * a.W; }
 
 // One thread: the pixel blockIdx.x * 256 + threadIdx.x of view v = blockIdx.y / nchunk of item blockIdx.z, planes chunk,
 // chunk + nchunk, ...  `at` is an element of the contiguous [B,V,D,H,W] gradient; only in-bounds taps are formed, so every index
@@ -87,17 +74,7 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(SweepArgs a, int nchunk, 
 template <int PASS>
 __global__ __launch_bounds__(256) void warp_bwd_det_kernel(SweepArgs a, int nchunk, const float* __restrict__ gout, uint32_t* __restrict__ hdr,
                                                            unsigned long long* __restrict__ acc) {
-    const int b = blockIdx.z;
-    if (PASS == 0) {
-        MaxOfAbs sink{0u};
-        warp_bwd_body(a, nchunk, gout, sink);
-        put_max(sink.m, hdr + b);
-    } else {
-        const int S = det_scale_exponent(__uint_as_float(hdr[b]), (long long)a.H * a.W);
-        if (S == EXP_ZERO || S == EXP_NONFINITE) return;   // (the whole workgroup: the convert pass writes this item)
-        IntegerSum sink{acc, S};
-        warp_bwd_body(a, nchunk, gout, sink);
-    }
+    max_exponent_pass<PASS>(hdr + blockIdx.z, acc, max_contributions(a), [&](auto& sink) { warp_bwd_body(a, nchunk, gout, sink); });
 }
 
 size_t per_item(const SweepArgs& a) { return (size_t)a.V * a.D * a.H * a.W; }
@@ -117,14 +94,11 @@ size_t warp_feature_backward_det_workspace_bytes(int B, int V, int D, int H, int
 }
 
 hipError_t launch_warp_feature_backward_det(const SweepArgs& a, const float* grad_out, float* grad_src, void* workspace, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(workspace, 0, warp_feature_backward_det_workspace_bytes(a.B, a.V, a.D, a.H, a.W), stream);
-    if (e != hipSuccess) return e;
-    uint32_t* hdr = static_cast<uint32_t*>(workspace);
-    unsigned long long* acc = det_accumulator(workspace, a.B, MaxExponent::WORDS);
     const int nchunk = plane_chunks(a);
-    hipLaunchKernelGGL(warp_bwd_det_kernel<0>, grid(a, nchunk), dim3(256), 0, stream, a, nchunk, grad_out, hdr, acc);
-    hipLaunchKernelGGL(warp_bwd_det_kernel<1>, grid(a, nchunk), dim3(256), 0, stream, a, nchunk, grad_out, hdr, acc);
-    return det_convert(workspace, a.B, per_item(a), MaxExponent{(long long)a.H * a.W}, grad_src, stream);
+    auto launch = [&](auto pass, uint32_t* hdr, unsigned long long* acc) {
+        hipLaunchKernelGGL(warp_bwd_det_kernel<decltype(pass)::value>, grid(a, nchunk), dim3(256), 0, stream, a, nchunk, grad_out, hdr, acc);
+    };
+    return max_exponent_scatter(workspace, a.B, per_item(a), max_contributions(a), grad_src, stream, launch);
 }
 
 }  // namespace pdepth

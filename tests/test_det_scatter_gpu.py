@@ -335,16 +335,28 @@ def _warp_torch(img, depth, Kinv, proj, mode, dtype):
     return out, (((xn + 1) * W - 1) / 2).reshape(B, H, W), (((yn + 1) * H - 1) / 2).reshape(B, H, W), pc[:, 2].reshape(B, H, W)
 
 
+def _many_to_one_case():
+    """A 32 x 48 image projected with an eighth of the focal lengths: (inputs of util_warps, Kinv, proj)."""
+    B, C, H, W = 2, 3, 32, 48
+    c = UW._iw_inputs(6131, B, C, H, W)
+    pose = UW._pose44(B, UW._T3[:2], UW._A3[:2])
+    return c, torch.inverse(c["K"].double()).float(), _eighth(torch.matmul(c["K"], pose[:, :3]))
+
+
+def _many_to_one_g_img(dev, c, Kinv, proj, mode, gup, deterministic):
+    img = c["img"].to(dev).requires_grad_(True)
+    out, _ = iv.warp_with_matrices(img, c["depth"].to(dev), Kinv.to(dev), proj.to(dev), mode, deterministic=deterministic)
+    (out * gup.to(dev)).sum().backward()
+    return img.grad.cpu()
+
+
 @pytest.mark.parametrize("mode", UW.MODES)
 def test_inverse_warp_many_to_one(dev, mode):
     """A 32 x 48 image projected with an eighth of the focal lengths: about 4 x 6 texels take every contribution.  g_img against
     float64 under the bound of tests/test_warps_gpu.py -- max(4 e_ref, 4 eps32 max|f64|), e_ref the float32 evaluation of the
     same chain in torch, the upstream gradient zero off util_warps.stable_mask --, and three calls with the same bits."""
-    B, C, H, W = 2, 3, 32, 48
-    c = UW._iw_inputs(6131, B, C, H, W)
-    pose = UW._pose44(B, UW._T3[:2], UW._A3[:2])
-    Kinv = torch.inverse(c["K"].double()).float()
-    proj = _eighth(torch.matmul(c["K"], pose[:, :3]))
+    c, Kinv, proj = _many_to_one_case()
+    B, C, H, W = c["img"].shape
     img64 = c["img"].double().requires_grad_(True)
     out64, ix, iy, pz = _warp_torch(img64, c["depth"], Kinv, proj, mode, torch.float64)
     M = UW.stable_mask(ix.detach(), iy.detach(), pz.detach(), H, W, mode)
@@ -359,10 +371,7 @@ def test_inverse_warp_many_to_one(dev, mode):
     assert float(M.double().mean()) > 0.9 and 0 < hit <= B * 8 * 12, (float(M.double().mean()), hit)
 
     def run(deterministic):
-        img = c["img"].to(dev).requires_grad_(True)
-        out, _ = iv.warp_with_matrices(img, c["depth"].to(dev), Kinv.to(dev), proj.to(dev), mode, deterministic=deterministic)
-        (out * gup.to(dev)).sum().backward()
-        return img.grad.cpu()
+        return _many_to_one_g_img(dev, c, Kinv, proj, mode, gup, deterministic)
 
     got, atomic = run(True), run(False)
     err = float((got.double() - want).abs().max())
@@ -370,6 +379,21 @@ def test_inverse_warp_many_to_one(dev, mode):
           % (mode, hit, err, float((atomic.double() - want).abs().max()), e_ref, bound))
     assert err <= bound
     assert torch.equal(run(True), got) and torch.equal(run(True), got)
+
+
+def test_inverse_warp_many_to_one_atomic_and_deterministic_agree_to_the_bit(dev):
+    """Both paths run one scatter body, so where float addition is exact they must agree to the bit: the many-to-one case in
+    nearest mode with an upstream gradient of integers in [-8, 8].  Every contribution is then an integer and a texel receives
+    at most H W = 1536 of them: |sum| <= 12 288 < 2^24, the float atomic sum is exact in any order and so is the integer sum.
+    (No such input exists in bilinear mode: g w is not exactly summable.)"""
+    c, Kinv, proj = _many_to_one_case()
+    gup = torch.randint(-8, 9, tuple(c["img"].shape), generator=torch.Generator().manual_seed(6131)).float()
+    assert bool((gup != 0).any()) and float(gup.abs().max()) <= 8.0
+    atomic = _many_to_one_g_img(dev, c, Kinv, proj, "nearest", gup, False)
+    det = _many_to_one_g_img(dev, c, Kinv, proj, "nearest", gup, True)
+    print("many-to-one/nearest, integer gradient: %d texels non-zero, max |g_img| %.0f" % (int((det != 0).sum()), float(det.abs().max())))
+    assert bool((det != 0).any())
+    assert torch.equal(atomic, det)
 
 
 # ---- the model ----------------------------------------------------------------------------------------------------------------
