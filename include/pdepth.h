@@ -62,7 +62,8 @@ extern "C" {
                                 *    pdepth_loss_terms_workspace_bytes, pdepth_loss_{dsc,rsc,dc,smooth}_f32 and their _backward_f32;
                                 *    PDEPTH_DTYPE_F16 / PDEPTH_DTYPE_BF16, pdepth_dpv_reduce_ex_lp, pdepth_dpv_reduce_backward_lp;
                                 *    pdepth_det_scale_exponent and the three _backward_det_f32 entries with their _det_workspace_bytes;
-                                *    pdepth_warp_feature_backward_f32, pdepth_warp_feature_backward_det_f32 and its _det_workspace_bytes */
+                                *    pdepth_warp_feature_backward_f32, pdepth_warp_feature_backward_det_f32 and its _det_workspace_bytes;
+                                *    pdepth_ssim_f32, pdepth_ssim_backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -714,6 +715,33 @@ size_t pdepth_warp_feature_backward_det_workspace_bytes(const pdepth_sweep_desc 
 int pdepth_warp_feature_backward_det_f32(const pdepth_sweep_desc *desc, const pdepth_camera *cam, const float *d_candi,
                                          const float *grad_out, float *grad_src, void *workspace, size_t workspace_bytes,
                                          void *stream);
+
+/*
+ * SSIM distance between two images and its gradients (csrc/ssim.hip): SSIM(x, y, md) of losses/loss_blocks.py:47-66, the
+ * photometric term of losses/flow_loss.py:13-27.
+ *
+ * x, y [B,C,H,W] fp32 contiguous -> out [B,C,H-2md,W-2md], md = 1, 2 or 3, one value per window of n = (2 md + 1)^2 pixels (valid
+ * windows only, as AvgPool2d(2 md + 1, 1, 0) places them).  Per window, with the sums divided by n:
+ *     s_x = e_xx - m_x^2,  s_y = e_yy - m_y^2,  s_xy = e_xy - m_x m_y,
+ *     A1 = 2 m_x m_y + C1,  A2 = 2 s_xy + C2,  B1 = m_x^2 + m_y^2 + C1,  B2 = s_x + s_y + C2,   C1 = 1e-4, C2 = 9e-4,
+ *     S = A1 A2 / (B1 B2),   out = clamp((1 - S) / 2, 0, 1).
+ * fp32 throughout, one rounding per operation, each window sum one running sum over its pixels in row-major order (the order of
+ * ATen's average pooling): the same bits from call to call.  The form is the reference's symmetric one: where x and y are equal bit for bit, out is
+ * exactly 0.  A NaN stays a NaN through the clamp.
+ *
+ * Backward: g_out [B,C,H-2md,W-2md] -> g_x, g_y [B,C,H,W]; either may be NULL, not both, and a NULL one is not stored.  The clamp
+ * passes the gradient on 0 <= (1 - S) / 2 <= 1, both edges included (torch.clamp's rule): a window that sits exactly on an edge
+ * -- two all-zero patches, S == 1 -- passes it.  Nothing of the forward is kept: each window's chain is recomputed from x and y,
+ * with the forward's bits, and every pixel gathers the (2 md + 1)^2 windows that contain it in a fixed order.  No atomics: two
+ * calls give the same bits, and a call for one gradient gives the bits of the call for both.  Where x and y are equal bit for bit
+ * both gradients are exactly 0.  The outputs may not alias each other or an input.
+ *
+ * B * C <= 65535 (a plane per grid z), H, W >= 2 md + 1, H * W <= 2^30, H <= 1048560; md outside 1..3: PDEPTH_E_ARG.  One launch
+ * each on `stream`; nothing is allocated, nothing waits for the host.
+ */
+int pdepth_ssim_f32(const float *x, const float *y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t md, float *out, void *stream);
+int pdepth_ssim_backward_f32(const float *x, const float *y, const float *g_out, int32_t B, int32_t C, int32_t H, int32_t W,
+                             int32_t md, float *g_x, float *g_y, void *stream);
 
 #ifdef __cplusplus
 }

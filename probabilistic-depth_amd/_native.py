@@ -98,14 +98,16 @@ _SIGNATURES = {
     "pdepth_warp_feature_backward_f32": (c_int, [_DESC, _CAM] + [_P] * 4),
     "pdepth_warp_feature_backward_det_workspace_bytes": (_Z, [_DESC]),
     "pdepth_warp_feature_backward_det_f32": (c_int, [_DESC, _CAM] + [_P] * 4 + [_Z, _P]),
+    "pdepth_ssim_f32": (c_int, [_P] * 2 + [_I] * 5 + [_P] * 2),
+    "pdepth_ssim_backward_f32": (c_int, [_P] * 3 + [_I] * 5 + [_P] * 3),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, loss-term, metrics, fusion-backward, LiDAR and deterministic-backward entries live in objects of their own: part of an entry's name -> the source file.  The
+# The loss, loss-term, metrics, fusion-backward, LiDAR, deterministic-backward and SSIM entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
 _SOURCE_OF_ENTRY = {"_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
-                    "_warp_feature_backward_": "csrc/warp_bwd.hip",
+                    "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -1274,6 +1276,56 @@ def loss_smooth_backward(depth, rgb, g_value):
                                                             _stream(depth.device))
     _check(rc, lib)
     return g
+
+
+# ---- SSIM (ops.ssim) ---------------------------------------------------------------------------------------------------------------
+SSIM_MD = (1, 2, 3)   # the window half-widths the kernels are built for
+
+
+def _ssim_args(who, x, y, md):
+    """((B, C, H, W), x, y) of an SSIM call: two [B,C,H,W] device tensors of one shape, as contiguous fp32."""
+    if md not in SSIM_MD:
+        raise NotImplementedError(f"{who}: md={md}: the HIP kernels are built for md = 1, 2 and 3")
+    x, y = _maps(who, x=x, y=y)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise RuntimeError(f"{who}: x and y must be two [B,C,H,W] tensors of one shape, got {list(x.shape)} and {list(y.shape)}")
+    B, C, H, W = x.shape
+    if B < 1 or C < 1:
+        raise RuntimeError(f"{who}: x and y must be [B,C,H,W] with B, C >= 1, got {list(x.shape)}")
+    if H < 2 * md + 1 or W < 2 * md + 1:
+        raise RuntimeError(f"{who}: H={H}, W={W}: a window of md={md} needs H and W of at least {2 * md + 1}")
+    return (B, C, H, W), x, y
+
+
+def ssim(x, y, md=1):
+    """x, y [B,C,H,W] -> dist [B,C,H-2md,W-2md]: pdepth_ssim_f32 on the current stream."""
+    who = "ssim"
+    _no_autograd(who, x, y)
+    (B, C, H, W), x, y = _ssim_args(who, x, y, md)
+    lib = load()
+    out = torch.empty((B, C, H - 2 * md, W - 2 * md), dtype=torch.float32, device=x.device)
+    with _on_device(x.device):
+        rc = _entry(lib, "pdepth_ssim_f32")(x.data_ptr(), y.data_ptr(), B, C, H, W, md, out.data_ptr(), _stream(x.device))
+    _check(rc, lib)
+    return out
+
+
+def ssim_backward(x, y, g_out, md=1, want_x=True, want_y=True):
+    """g_out [B,C,H-2md,W-2md] -> (g_x [B,C,H,W] | None, g_y [B,C,H,W] | None): pdepth_ssim_backward_f32."""
+    who = "ssim_backward"
+    (B, C, H, W), x, y = _ssim_args(who, x, y, md)
+    _shape(g_out, (B, C, H - 2 * md, W - 2 * md), "g_out", who)
+    (g_out,) = _maps(who, g_out=g_out)
+    if not (want_x or want_y):
+        raise RuntimeError(f"{who}: no gradient requested")
+    lib = load()
+    g_x = torch.empty_like(x) if want_x else None
+    g_y = torch.empty_like(y) if want_y else None
+    with _on_device(x.device):
+        rc = _entry(lib, "pdepth_ssim_backward_f32")(x.data_ptr(), y.data_ptr(), g_out.data_ptr(), B, C, H, W, md, _ptr(g_x), _ptr(g_y),
+                                                     _stream(x.device))
+    _check(rc, lib)
+    return g_x, g_y
 
 
 # ---- evaluation metrics (ops.depth_metrics) -----------------------------------------------------------------------------------

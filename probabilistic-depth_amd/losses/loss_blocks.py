@@ -84,14 +84,34 @@ def edge_aware_smoothness_loss(pred_disp, img, max_scales):
     return loss
 
 
-def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, pose_target2src, intr, viz=False, per_item=False):
+def SSIM(x, y, md=1):
+    """clamp((1 - SSIM(x, y)) / 2, 0, 1) over (2 md + 1)^2 windows, [B,C,H,W] -> [B,C,H-2md,W-2md] (loss_blocks.py:47-66): one HIP
+    pass forward, one backward (ops.ssim; md = 1, 2 or 3)."""
+    return ops.ssim(x, y, md)
+
+
+def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, pose_target2src, intr, viz=False, per_item=False,
+                                ssim_weight=0.0, ssim_md=1):
     """Photometric error between the target image and the source image warped into it with the target's depth map, over the
     pixels that land inside the source and lie below the top third (loss_blocks.py:114-145).  rgb [B,3,H,W], depth [B,H,W],
-    pose [1,4,4] | [B,4,4], intr [B,3,3].  viz is accepted and ignored (the reference opens a window)."""
+    pose [1,4,4] | [B,4,4], intr [B,3,3].  viz is accepted and ignored (the reference opens a window).
+
+    ssim_weight = w != 0 mixes in the SSIM distance the reference carries commented out (loss_blocks.py:128-129, where it suggests
+    0.85), composed as its flow loss composes the photometric pieces (losses/flow_loss.py:13-27): with m the mask,
+        (1 - w) mean_on_mask(|tgt m - warped m|, m) + w mean(SSIM(warped m, tgt m, ssim_md)) / mean(m),
+    the means per item with per_item.  With w == 0 the SSIM is not evaluated: the L1 term alone, with the bits it has always had."""
     warped, valid = _warp(src_rgb_img, target_depth_map, pose_target2src, intr, "bilinear")
     mask = (valid & _lower_two_thirds(valid.shape, src_rgb_img.device)).float().unsqueeze(1)
     diff = (target_rgb_img * mask - warped * mask).abs()
-    return mean_on_mask(diff, mask, per_item)
+    photo = mean_on_mask(diff, mask, per_item)
+    if ssim_weight == 0:
+        return photo
+    dist = SSIM(warped * mask, target_rgb_img * mask, ssim_md)
+    if per_item:
+        structural = dist.reshape(dist.shape[0], -1).mean(1) / mask.reshape(mask.shape[0], -1).mean(1)
+    else:
+        structural = dist.mean() / mask.mean()
+    return (1.0 - ssim_weight) * photo + ssim_weight * structural
 
 
 def depth_stereo_consistency_loss(src_depth_img, target_depth_img, src_depth_mask, target_depth_mask, pose_target2src, intr,

@@ -16,6 +16,12 @@ With fused_terms=True the consistency and smoothness terms (dc, dsc, rsc, smooth
 (ops.depth_consistency, depth_stereo_consistency, rgb_stereo_consistency, edge_aware_smoothness) instead of the torch compositions
 of loss_blocks.py.  The camera matrices they take are formed with the helpers the compositions use (_inv3, intr @ pose[:3]), once
 per (intrinsics, pose) pair of the call, so the masks keep their bits.  The default is the composition.
+
+cfg.loss.rsc_ssim = w (absent: 0) mixes the SSIM distance into the two RGB consistency terms, rsc and rsc_low, over windows of half-width
+cfg.loss.rsc_ssim_md (absent: 1): (1 - w) L1 + w SSIM / mean(mask) per item, loss_blocks.rgb_stereo_consistency_loss; the reference's
+commented-out line (loss_blocks.py:128-129) suggests 0.85.  The fused rsc pass has no SSIM: with fused_terms=True and w != 0 the rsc
+term is the composition (the HIP warp and the HIP SSIM, ops.ssim), the other fused terms stay fused.  With the key absent or 0 no path
+changes.
 """
 import torch
 import torch.nn as nn
@@ -125,20 +131,22 @@ class BaseLoss(nn.Module):
                                                                     pose_src2target=pose_l2r, per_item=True).sum()
 
         rgb_l, rgb_r = tgt_l["rgb"][:, -1], tgt_r["rgb"][:, -1]
+        ssim_w, ssim_md = getattr(mul, "rsc_ssim", 0.0), getattr(mul, "rsc_ssim_md", 1)
+        photo = {"ssim_weight": ssim_w, "ssim_md": ssim_md} if ssim_w != 0 else {}
         rsc_loss = 0
-        if mul.rsc_mul != 0 and fused:
+        if mul.rsc_mul != 0 and fused and ssim_w == 0:
             rsc_loss = (ops.rgb_stereo_consistency(rgb_r, rgb_l, large["l"], *camera(tgt_l["intrinsics_up"], pose_l2r))[0].sum() +
                         ops.rgb_stereo_consistency(rgb_l, rgb_r, large["r"], *camera(tgt_r["intrinsics_up"], pose_r2l))[0].sum())
         elif mul.rsc_mul != 0:
-            rsc_loss = (rgb_stereo_consistency_loss(rgb_r, rgb_l, large["l"], pose_l2r, tgt_l["intrinsics_up"], per_item=True).sum() +
-                        rgb_stereo_consistency_loss(rgb_l, rgb_r, large["r"], pose_r2l, tgt_r["intrinsics_up"], per_item=True).sum())
+            rsc_loss = (rgb_stereo_consistency_loss(rgb_r, rgb_l, large["l"], pose_l2r, tgt_l["intrinsics_up"], per_item=True, **photo).sum() +
+                        rgb_stereo_consistency_loss(rgb_l, rgb_r, large["r"], pose_r2l, tgt_r["intrinsics_up"], per_item=True, **photo).sum())
 
         rsc_low_loss = 0
         if mul.rsc_low_mul != 0:
             low_l = F.interpolate(rgb_l, scale_factor=0.25, mode="bilinear")
             low_r = F.interpolate(rgb_r, scale_factor=0.25, mode="bilinear")
-            rsc_low_loss = (rgb_stereo_consistency_loss(low_r, low_l, small["l"], pose_l2r, tgt_l["intrinsics"], per_item=True).sum() +
-                            rgb_stereo_consistency_loss(low_l, low_r, small["r"], pose_r2l, tgt_r["intrinsics"], per_item=True).sum())
+            rsc_low_loss = (rgb_stereo_consistency_loss(low_r, low_l, small["l"], pose_l2r, tgt_l["intrinsics"], per_item=True, **photo).sum() +
+                            rgb_stereo_consistency_loss(low_l, low_r, small["r"], pose_r2l, tgt_r["intrinsics"], per_item=True, **photo).sum())
 
         smooth_loss = 0
         if mul.smooth_mul != 0 and fused:

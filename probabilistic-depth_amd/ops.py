@@ -298,6 +298,18 @@ def edge_aware_smoothness(depth, rgb):
     return _native.loss_smooth(depth, rgb)
 
 
+def ssim(x, y, md=1):
+    """SSIM distance of two images (losses/loss_blocks.py:47-66), one HIP pass: x, y [B,C,H,W] -> clamp((1 - SSIM) / 2, 0, 1)
+    [B,C,H-2md,W-2md], one value per (2 md + 1)^2 window, md = 1, 2 or 3 (another md: NotImplementedError; H or W below 2 md + 1: a
+    RuntimeError that names the sizes).  The inputs go through .float().contiguous().  Where x and y are equal bit for bit the
+    result is exactly 0.  Differentiable with respect to x and / or y (csrc/ssim.hip: a gather, the same bits from call to call);
+    the kernel is asked only for the gradients that are needed, and the forward under autograd is the no-grad kernel call."""
+    md = int(md)
+    if _wants_grad(x, y):
+        return _SsimFn.apply(x, y, md)
+    return _native.ssim(x, y, md)
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
@@ -619,6 +631,27 @@ class _SmoothFn(torch.autograd.Function):
         if g_value is None or not ctx.needs_input_grad[0]:
             return None, None
         return _native.loss_smooth_backward(*ctx.saved_tensors, g_value), None
+
+
+class _SsimFn(torch.autograd.Function):
+    """ssim under autograd."""
+
+    @staticmethod
+    def forward(ctx, x, y, md):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, y)
+        ctx.md = md
+        return _native.ssim(x, y, md)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_out is None or not (want_x or want_y):
+            return None, None, None
+        x, y = ctx.saved_tensors
+        g_x, g_y = _native.ssim_backward(x, y, g_out, ctx.md, want_x=want_x, want_y=want_y)
+        return (g_x.to(x.dtype) if want_x else None), (g_y.to(y.dtype) if want_y else None), None
 
 
 class _CorrelationFn(torch.autograd.Function):
