@@ -28,8 +28,9 @@
 //       statistics put it outside the domain of the distance form (guard below), is evaluated directly by the same
 //       workgroup behind the view loop, in the reference's own form on the packed features.
 //   scheduling.  Persistent workgroups pull pixel blocks -- 16 pixels, 16x1 or 8x2: the four of a 16x4 tile are consecutive
-//       items -- from per-XCD queues (balanced half-bands, stealing), one item ahead; thread 0 decodes the next item once for
-//       the workgroup, under the current block's pixel loads, into a record in LDS that every wave starts the block from.
+//       items -- from per-XCD queues (balanced half-bands, stealing), one item ahead; the queue thread (lane 0 of the wave
+//       with the short share of the texel blocks) decodes the next item once for the workgroup, while the other waves multiply
+//       their last blocks, into a record in LDS that every wave starts the block from.
 //       Launches of up to six items per resident workgroup have no queue: a workgroup per item.  The last workgroup to
 //       leave zeroes the queue counters: a call on an already packed source is this one launch.
 #include <hip/hip_runtime.h>
@@ -96,7 +97,7 @@ struct __attribute__((aligned(16))) DistLds {
     int ctab[2][64 * 2];         // per cell row (modulo 64): (min, max) x0; two sets, alternating by pass
     int ired[2][2];              // min / max cell row of the pass; two sets
     int brow[MAXB + 2];          // per block of the pass: its row (written alike by every wave, read back by the same wave)
-    v4i rec[2];                  // decoded work item, current / next (ItemRec below: thread 0 writes, every wave reads)
+    v4i rec[2];                  // decoded work item, current / next (the item record below: the queue thread writes, every wave reads)
     int iflag;                   // the batch item in work: 1 = fp16 overflow in the pack, 2 = outside the domain (guard)
     unsigned char wide[64];      // per batch item: pixel blocks are 16x1 (else 8x2)
 };
@@ -124,6 +125,10 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
 #endif
     if (poison_on_foreign_layout(da.a, da.queue, LAYOUT_DIST16)) return;
     const int tid = threadIdx.x;
+    // The QUEUE THREAD (sweep_dist_knobs.hpp): lane 0 of wave DIST_QUEUE_WAVE pops, resolves, decodes and publishes the items,
+    // counts the direct blocks and leaves for the workgroup -- the state of all that lives in its registers.
+    constexpr int QT = 64 * DIST_QUEUE_WAVE;
+    static_assert(DIST_QUEUE_WAVE >= 0 && DIST_QUEUE_WAVE < 4, "a workgroup has four waves");
 
     {
         const float* dc = KARG(const float*, a.d_candi);
@@ -176,7 +181,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     };
     // floor(nn / dd) for 0 <= nn < 2^22, 0 < dd (an integer divide costs ~40 dependent instructions)
     auto fdiv = [](int nn, int dd) { return (int)(((float)nn + 0.5f) * __builtin_amdgcn_rcpf((float)dd)); };
-    // (thread 0 only, in publish(): no wave decodes an item for itself)
+    // (the queue thread only, in publish(): no wave decodes an item for itself)
     auto decode = [&](int item, int& b_, int& tx_, int& ty_, int& sub_) {
         const int ntile = KARG(int, ntile), tiles_x = KARG(int, tiles_x), H = KARG(int, a.H);
         const int qq = ntile >> 3, rr8 = ntile & 7;
@@ -214,18 +219,19 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     // the pass (alternating), bit 2 = the pixel inputs of the next item are on their way to the zone (below), bits 3.. = 1 + the
     // batch item whose tables (means, homography terms, camera constants) are in LDS
     int state = 0;
-    int n_direct = 0;     // (thread 0) pixel blocks evaluated directly
-    // The queue runs one item ahead: (thread 0) the atomic that pops item i + 1 is issued a block ahead, its result is resolved,
+    int n_direct = 0;     // (the queue thread) pixel blocks evaluated directly
+    // The queue runs one item ahead: (the queue thread) the atomic that pops item i + 1 is issued a block ahead, its result is resolved,
     // DECODED and published in LDS (L.rec) in front of the LAST barrier of item i -- the workgroup goes from one pixel block to
     // the next without a barrier of the queue's own, and no wave decodes an item for itself.
-    int got_own = (tid == 0 && !ONE_EACH) ? atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1) : (int)(blockIdx.x >> 3);
-    // resolve_next(): at the top of the block (record_next() below says why), at any rate BEFORE the block's stores are issued -- the result of the atomic is waited for with a vmcnt, and memory
-    // operations complete in issue order: behind the stores that wait is the stores' whole latency, for thread 0's wave and, at
-    // the next barrier, for the workgroup (2 us per pixel block when it was there).
+    int got_own = (tid == QT && !ONE_EACH) ? atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1) : (int)(blockIdx.x >> 3);
+    // resolve_next(): right in front of record_next() (which says where), at any rate BEFORE the block's stores are issued -- the
+    // result of the atomic is waited for with a vmcnt, and memory operations complete in issue order: behind the stores that wait
+    // is the stores' whole latency, for the queue thread's wave and, at the next barrier, for the workgroup (2 us per pixel block
+    // when it was there).
     int next_item = -1;
-    // ("thread 0" asked of a value the optimiser cannot see through: the lane mask of `tid == 0` is not kept across the kernel)
-    auto resolve_next = [&]() { if (opaque_v((int)threadIdx.x) == 0) next_item = ONE_EACH ? -1 : resolve(got_own); };
-    // The item record: thread 0 decodes an item ONCE for the workgroup and leaves in LDS what the top of the item needs of it --
+    // ("the queue thread" asked of a value the optimiser cannot see through: the lane mask of `tid == QT` is not kept across the kernel)
+    auto resolve_next = [&]() { if (opaque_v((int)threadIdx.x) == QT) next_item = ONE_EACH ? -1 : resolve(got_own); };
+    // The item record: the queue thread decodes an item ONCE for the workgroup and leaves in LDS what the top of the item needs of it --
     //   .x  the raw item (queue << 28 | index), -1: every queue is dry (nothing else of the record is valid then)
     //   .y  the batch item b
     //   .z  (y0 << 16) | x0: the first pixel of the block, the tile's block (sub) and the item's block shape applied
@@ -235,7 +241,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     // a scalar round trip, three or four reciprocal divisions and the half-band arithmetic: profiles/r10_item_record/).
     // L.wide is complete behind the __syncthreads() above.
     constexpr int REC_WIDE = 1, REC_BELOW = 2, REC_FIRST = 4;
-    auto publish = [&](int slot, int item) {   // (thread 0, in front of a workgroup barrier)
+    auto publish = [&](int slot, int item) {   // (the queue thread, in front of a workgroup barrier)
         v4i r = v4i{item, 0, 0, 0};
         if (item >= 0) {
             int b, tx, ty, sub;
@@ -249,23 +255,30 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         L.rec[slot] = r;
     };
     // record_next(): the next item's record into the slot the current item does not use -- nobody has read that slot since the top
-    // of the previous item, several barriers back.  Where (DIST_DECODE_EARLY): right behind resolve_next(), which then stands
-    // at the top of the item behind the issue of the block's pixel loads (the pop it reads was waited for at the end of the
-    // previous block: PDEPTH_POP_WAIT), so that thread 0's decode runs while every wave waits for those loads anyway; and the
-    // pop of the item after the next is issued there as well: it has the whole block to return, and the waits for it at the
-    // end of the block find it done.  (Not with the prefetch, whose counted wait at the top of a block counts the vector-memory
-    // operations behind the DMA: the pop stays in publish_next().)  Else in publish_next(), in front of the block's last
-    // barrier, with resolve_next() in front of the block's stores.  profiles/r10_item_record/ has both.
+    // of the previous item, several barriers back.  Where (DIST_DECODE_EARLY): right behind resolve_next(), and
+    //   2 (the product)  in the item's FIRST PASS, behind the queue wave's last texel block and in front of the pass's second
+    //      barrier.  The decode is ~1 900 cycles of one wave; at the top of the item the other three waited them out at the
+    //      first barrier, block after block (per-wave stamps: profiles/r13_wave_roles/).  The queue wave is the LAST wave in the
+    //      order of the Y shares -- the one that takes the remainder of ceil(nb / 4) blocks each: it decodes while the other
+    //      three still multiply.  (Counting the decode as one to four blocks of that wave's share, so that the others take
+    //      more, was slower on the headline.)
+    //   1  at the top of the item behind the issue of the block's pixel loads (the pop it reads was waited for at the end of
+    //      the previous block: PDEPTH_POP_WAIT);
+    //   0  in publish_next(), in front of the block's last barrier, with resolve_next() in front of the block's stores
+    //      (profiles/r10_item_record/ has 0 and 1).
+    // With 1 and 2 the pop of the item after the next is issued there as well: it has the rest of the block to return, and the
+    // waits for it at the end of the block find it done.  (Not with the prefetch, whose counted wait at the top of a block counts
+    // the vector-memory operations behind the DMA: the pop stays in publish_next().)
     constexpr bool EARLY = DIST_DECODE_EARLY != 0;
     constexpr bool POP_EARLY = EARLY && DIST_PREFETCH == 0;
-    auto record_next = [&]() {
-        if (opaque_v((int)threadIdx.x) == 0) {
-            publish(state & 1, next_item);
-            if (POP_EARLY && !ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
+    auto record_next = [&](bool decode = true, bool pop = true) {   // (the two halves apart: DIST_DECODE_EARLY == 2)
+        if (opaque_v((int)threadIdx.x) == QT) {
+            if (decode) publish(state & 1, next_item);
+            if (pop && POP_EARLY && !ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
         }
     };
-    auto publish_next = [&]() {   // (thread 0, in front of a workgroup barrier)
-        if (opaque_v((int)threadIdx.x) == 0) {
+    auto publish_next = [&]() {   // (the queue thread, in front of a workgroup barrier)
+        if (opaque_v((int)threadIdx.x) == QT) {
             if (!EARLY) publish(state & 1, next_item);
             if (!POP_EARLY && !ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
         }
@@ -323,7 +336,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         dma_pixels(wave, b, (min(y, H - 1) * W + min(x, W - 1)) * 4);
         state |= 4;
     };
-    if (tid == 0) {
+    if (tid == QT) {
         publish(0, ONE_EACH ? (got_own < items_of(xcd) ? (xcd << 28) | got_own : -1) : resolve(got_own));
         if (!ONE_EACH && !own_done) got_own = atomicAdd(&KARG(int*, qcnt)[xcd * KARG(int, qstride)], 1);
     }
@@ -340,7 +353,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         // (a plain LDS read: behind the barrier's memory clobber it cannot be hoisted.  Through a volatile generic pointer --
         //  round 5 -- it was a FLAT load, and a flat load is waited for with vmcnt(0): every item began by waiting out the
         //  previous pixel block's stores, 2 us per item)
-        const v4i rec = L.rec[state & 1];   // (one 16-byte read: the item as thread 0 decoded it)
+        const v4i rec = L.rec[state & 1];   // (one 16-byte read: the item as the queue thread decoded it)
         state ^= 1;
         const int pf = state & 4;   // (the item's pixel inputs are on their way to the zone)
         state ^= pf;
@@ -399,7 +412,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                     }
                 }
             }
-            if (EARLY) { resolve_next(); record_next(); }   // (thread 0: under the latency of the loads above)
+            if (DIST_DECODE_EARLY == 1) { resolve_next(); record_next(); }   // (the queue thread: under the latency of the loads above)
             DSTAMP(1)   // item set-up, pixel loads issued
             // (the pixel loads above are in flight while the tables of a new batch item are built: where every workgroup runs ONE
             //  item -- the model-real shapes -- that is a memory round trip off a 13 us launch)
@@ -491,11 +504,12 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                     // (the item's first block marks it and counts ALL its blocks for the diagnostics: the count is merged into
                     //  the workspace by a compare-and-swap chain per workgroup at the end of the kernel -- one per pixel block was
                     //  0.9 ms of serialised atomics on a routed launch)
-                    if (opaque_v((int)threadIdx.x) == 0 && (recfl & REC_FIRST)) {
+                    if (opaque_v((int)threadIdx.x) == QT && (recfl & REC_FIRST)) {
                         reinterpret_cast<int*>(const_cast<float*>(KARG(const float*, stats)) + (size_t)b * STATS_STRIDE + STATS_FLAGS)[1] = 1;
                         n_direct += KARG(int, tiles_x) * (wide ? H : 2 * ((H + 1) >> 1));
                     }
-                    if (!EARLY) resolve_next();
+                    if (DIST_DECODE_EARLY != 1) resolve_next();
+                    if (DIST_DECODE_EARLY == 2) record_next();   // (the item has no pass to do it in)
                     publish_next();
                     PDEPTH_LDS_BARRIER();
                     PDEPTH_POP_WAIT(0);
@@ -760,7 +774,11 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             fetch(set, NAC - 1, soff);
                         };
                         // wave w: blocks w q .. w q + q - 1 (consecutive blocks: consecutive slots)
-                        const int q = (nb + 3) >> 2, b0 = wave * q, b1 = min(nb, b0 + q);
+                        // (the queue wave is the last in this order, the one with the remainder: record_next() says why.  Which wave
+                        //  multiplies a block changes no bit of Y.)
+                        const bool decode_here = DIST_DECODE_EARLY == 2 && v == 0 && h == 0 && attempt == 0;
+                        const int wsh = DIST_DECODE_EARLY == 2 ? (wave + 3 - DIST_QUEUE_WAVE) & 3 : wave;
+                        const int q = (nb + 3) >> 2, b0 = wsh * q, b1 = min(nb, b0 + q);
                         __builtin_amdgcn_s_setprio(1);   // (the matrix phase ahead of the other workgroups' vector phases)
                         if (go) {
 #pragma unroll
@@ -831,8 +849,14 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                                 }
                             }
                             DSTAMP(6)   // slots, loads + multiplications
-                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's Q records have landed in LDS
                         }
+                        // (DIST_DECODE_EARLY == 2: the queue thread's decode behind its wave's last Y block of the item's first pass -- the
+                        //  wave with the short share of the blocks has the time the others still multiply --, at the matrix phase's
+                        //  priority and under the Q records' way to LDS; the pop behind the wait for them, which else were one for
+                        //  the pop's round trip as well)
+                        if (decode_here) { resolve_next(); record_next(true, false); }
+                        if (go) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's Q records have landed in LDS
+                        if (decode_here) record_next(false, true);
                         __builtin_amdgcn_s_setprio(0);
                     }
                     DSTAMP(7)   // wait for the Q records
@@ -902,7 +926,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
 #pragma unroll 1
                 for (int vhh = 0; vhh < V * NH * 2; ++vhh) {
                     if (!(failmask >> vhh & 1u)) continue;
-                    if (tid == 0) ++n_direct;
+                    if (tid == QT) ++n_direct;
                     if ((wave >> 1) != (vhh & 1)) continue;   // (the planes of the other pair of waves; no barrier in this loop)
                     const int vh = vhh >> 1, v = vh / NH, h = vh - v * NH;
                     ViewXform xf;
@@ -982,16 +1006,19 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             if (logp_out || depth_out) {
                 // per wave: max, sum exp, sum d exp over its planes of pixel n; merged over the four waves through LDS
                 {
+                    // (the planes' numbers from a value the optimiser cannot trace back: formed at the top of the item and kept
+                    //  across it, one of them was a spilled register as soon as the decode stood inside the pass)
+                    const int tq4 = opaque_v(4 * tq);
                     float mx = -INFINITY;
 #pragma unroll
                     for (int j = 0; j < NC; ++j)
-                        mx = max_raw(mx, 64 * (j >> 2) + 4 * tq + (j & 3) < D ? cost[j] : -INFINITY);
+                        mx = max_raw(mx, 64 * (j >> 2) + tq4 + (j & 3) < D ? cost[j] : -INFINITY);
                     mx = max_raw(mx, xor16_f(mx));
                     mx = max_raw(mx, bperm_f(a32, mx));
                     float ssum = 0.0f, esum = 0.0f;
 #pragma unroll
                     for (int j = 0; j < NC; ++j) {
-                        const int k = 64 * (j >> 2) + 4 * tq + (j & 3);
+                        const int k = 64 * (j >> 2) + tq4 + (j & 3);
                         const float ek = k < D ? dist_exp(cost[j] - mx) : 0.0f;
                         ssum = ssum + ek;
                         esum = __builtin_fmaf(L.dcl[k], ek, esum);
@@ -1044,7 +1071,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     }   // items
 #undef PDEPTH_POP_WAIT
 #ifdef DIST_STAMPS
-    if ((threadIdx.x & 63) == 0)
+    if ((threadIdx.x & 63) == 0 && (DIST_STAMP_WAVE < 0 || (int)(threadIdx.x >> 6) == DIST_STAMP_WAVE))
         for (int i = 0; i < 12; ++i) atomicAdd(reinterpret_cast<unsigned long long*>(KARG(int*, queue) + 8) + i, stamp_acc[i]);
 #endif
 
@@ -1053,7 +1080,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
     // nothing was counted that needs resetting, and a returning atomic per workgroup on one address is what such a launch
     // cannot afford: a workgroup with direct passes -- rare -- adds them to the published count itself, tagged with the call's
     // nonce (a count left by another call is replaced).
-    if (opaque_v((int)threadIdx.x) == 0) {
+    if (opaque_v((int)threadIdx.x) == QT) {
         int* queue = KARG(int*, queue);
         const int nonce = KARG(int, nonce);
         if (ONE_EACH) {

@@ -27,7 +27,10 @@
 #define DIST_PREFETCH 0    // 1: the next pixel block's rays and reference features by LDS-DMA behind the current one's last barrier (bit-identical; 1.6 % slower on the item record, 5 % before it: profiles/r10_item_record/, r07_ab/)
 #endif
 #ifndef DIST_DECODE_EARLY
-#define DIST_DECODE_EARLY 1   // thread 0 decodes the next item and pops the one after it at the top of the current block, under its pixel loads (0: in front of the block's last barrier; headline alike, --pose stereo 1 % slower: profiles/r10_item_record/)
+#define DIST_DECODE_EARLY 2   // where the queue thread decodes the next item and pops the one after it: 2 = in the item's first pass, behind its wave's last texel block (the other waves still multiply); 1 = at the top of the block, under its pixel loads (the other waves wait at the first barrier: +2.1 % headline); 0 = in front of the block's last barrier (+2.3 %): profiles/r13_wave_roles/, r10_item_record/
+#endif
+#ifndef DIST_QUEUE_WAVE
+#define DIST_QUEUE_WAVE 3     // the wave whose lane 0 is the workgroup's queue thread (pops, resolves, decodes, publishes, counts, leaves); with DIST_DECODE_EARLY == 2 the last wave in the order of the texel-block shares, whichever it is (wave 0 there, with its full share: +2.2 % headline)
 #endif
 #ifndef DIST_ONE_EACH_X
 #define DIST_ONE_EACH_X 6  // a workgroup per item, no queue, up to this many items per resident workgroup (2 .. 24: the large shapes are indifferent; profiles/r06_ab/)
@@ -43,7 +46,12 @@
 #endif
 
 // phase stamps (-DDIST_STAMPS): shader-clock cycles per phase, summed per wave, added into the queue ints 8..31 on the way out
-// (every stamp is a scalar memory read and a wait for it: the phases stretch, their proportions are indicative only)
+// (every stamp is a scalar memory read and a wait for it: the phases stretch, their proportions are indicative only).
+// -DDIST_STAMP_WAVE=w: only wave w of every workgroup reports (four builds, four runs: tools/dbg/dist_stamps.py --libs puts
+// them side by side) -- the wave whose barrier stamp is near zero is the one the other three waited for
+#ifndef DIST_STAMP_WAVE
+#define DIST_STAMP_WAVE -1
+#endif
 #ifdef DIST_STAMPS
 #define DSTAMP(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); stamp_acc[i] += t_ - stamp_t; stamp_t = t_; }
 #elif defined(DIST_MARKS)   // static instruction census per phase (tools/dbg/isa_census.py)
