@@ -63,7 +63,8 @@ extern "C" {
                                 *    PDEPTH_DTYPE_F16 / PDEPTH_DTYPE_BF16, pdepth_dpv_reduce_ex_lp, pdepth_dpv_reduce_backward_lp;
                                 *    pdepth_det_scale_exponent and the three _backward_det_f32 entries with their _det_workspace_bytes;
                                 *    pdepth_warp_feature_backward_f32, pdepth_warp_feature_backward_det_f32 and its _det_workspace_bytes;
-                                *    pdepth_ssim_f32, pdepth_ssim_backward_f32 */
+                                *    pdepth_ssim_f32, pdepth_ssim_backward_f32;
+                                *    pdepth_loss_photo_workspace_bytes, pdepth_loss_photo_f32, pdepth_loss_photo_backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -742,6 +743,40 @@ int pdepth_warp_feature_backward_det_f32(const pdepth_sweep_desc *desc, const pd
 int pdepth_ssim_f32(const float *x, const float *y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t md, float *out, void *stream);
 int pdepth_ssim_backward_f32(const float *x, const float *y, const float *g_out, int32_t B, int32_t C, int32_t H, int32_t W,
                              int32_t md, float *g_x, float *g_y, void *stream);
+
+/*
+ * The photometric term in one pass each way (csrc/photo.hip): the bilinear warp of pdepth_loss_rsc_f32, its masked L1 distance and
+ * the SSIM distance of the masked images, per batch item -- rgb_stereo_consistency_loss (losses/loss_blocks.py:114-145) with the
+ * SSIM it carries commented out (:128-129) mixed in as the flow loss mixes it (losses/flow_loss.py:13-27).
+ *
+ * src_rgb, tgt_rgb [B,3,H,W], tgt_depth [B,H,W], Kinv [B,3,3], proj [B,3,4] as pdepth_loss_rsc_f32 takes them.  With
+ * m = valid & row >= H / 3 (the bits of pdepth_inverse_warp_f32's `valid`), x = warped m, y = tgt m, md = 1, 2 or 3,
+ * n_w = 3 (H - 2 md)(W - 2 md) and S the SSIM of pdepth_ssim_f32 over (x, y), in that order:
+ *     value = (1 - w) sum_c sum(|y_c - x_c| m) / (3 sum(m))  +  w (sum_windows clamp((1 - S) / 2, 0, 1) / n_w) / (sum(m) / (H W))
+ *     count = sum(m)
+ * w = ssim_weight, a double as the Python number it comes from: the factors are (float)w and (float)(1 - w), the difference taken
+ * in double, as torch forms them.  A window has the bits it has in pdepth_ssim_f32 on the same x and y.  The products with the mask
+ * stay products: a NaN behind a zero mask makes its item NaN; an empty mask is 0 / 0 = NaN for its item alone.
+ * Forward: one launch (a workgroup per 64 x 16 tile of an item; nothing per-pixel is written) and the sum of the workgroups' three
+ * partial sums per item in a fixed order, in double.  No atomics: two calls give the same bits.
+ *   workspace: pdepth_loss_photo_workspace_bytes(B, H, W) bytes (12 bytes per tile and item), 256-byte aligned; 0 for sizes out of
+ *   range.  A workspace that is missing, too small or misaligned is PDEPTH_E_WORKSPACE.
+ * Backward: g_tgt_depth [B,H,W] and nothing else, in one launch that recomputes from the inputs; it takes the forward's count, which
+ * like the mask mean is a constant of the gradient.  Per pixel p and channel c, with d_c = y_c - x_c and n = (2 md + 1)^2:
+ *     g_warped_c = -(1 - w) g / (3 count) sign0(d_c) m  +  m sum_{windows containing p} (P + Q x_p + R y_p) / n
+ * P, Q, R the coefficients of pdepth_ssim_backward_f32 with G = -1/2 g w / (n_w count / (H W)) on the windows that pass the clamp
+ * (0 <= (1 - S) / 2 <= 1, both edges included) and 0 elsewhere; then through the sample position as pdepth_loss_rsc_backward_f32.
+ * Every pixel gathers its windows in a fixed order: two calls give the same bits.
+ * B <= 65535, H, W >= 2 md + 1, H * W <= 2^24, H <= 1048560; md outside 1..3: PDEPTH_E_ARG.  Nothing is allocated, nothing waits
+ * for the host.
+ */
+size_t pdepth_loss_photo_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_loss_photo_f32(const float *src_rgb, const float *tgt_rgb, const float *tgt_depth, const float *Kinv, const float *proj,
+                          int32_t B, int32_t H, int32_t W, double ssim_weight, int32_t md, float *value, float *count,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int pdepth_loss_photo_backward_f32(const float *src_rgb, const float *tgt_rgb, const float *tgt_depth, const float *Kinv,
+                                   const float *proj, const float *count, const float *g_value, int32_t B, int32_t H, int32_t W,
+                                   double ssim_weight, int32_t md, float *g_tgt_depth, void *stream);
 
 #ifdef __cplusplus
 }

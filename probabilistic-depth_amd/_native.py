@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 import numpy as np
 import torch
@@ -100,12 +100,15 @@ _SIGNATURES = {
     "pdepth_warp_feature_backward_det_f32": (c_int, [_DESC, _CAM] + [_P] * 4 + [_Z, _P]),
     "pdepth_ssim_f32": (c_int, [_P] * 2 + [_I] * 5 + [_P] * 2),
     "pdepth_ssim_backward_f32": (c_int, [_P] * 3 + [_I] * 5 + [_P] * 3),
+    "pdepth_loss_photo_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_loss_photo_f32": (c_int, [_P] * 5 + [_I] * 3 + [c_double, _I] + [_P] * 3 + [_Z, _P]),
+    "pdepth_loss_photo_backward_f32": (c_int, [_P] * 7 + [_I] * 3 + [c_double, _I] + [_P] * 2),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, loss-term, metrics, fusion-backward, LiDAR, deterministic-backward and SSIM entries live in objects of their own: part of an entry's name -> the source file.  The
+# The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward and SSIM entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
-_SOURCE_OF_ENTRY = {"_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
+_SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
                     "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
@@ -1198,6 +1201,51 @@ def loss_rsc_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count, g_value):
     with _on_device(dev):
         rc = _entry(lib, "pdepth_loss_rsc_backward_f32")(*(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W,
                                                          g.data_ptr(), _stream(dev))
+    _check(rc, lib)
+    return g
+
+
+def _photo_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, md):
+    """_rsc_args, and the window of the SSIM: md one of SSIM_MD, H and W of at least 2 md + 1."""
+    if md not in SSIM_MD:
+        raise NotImplementedError(f"{who}: md={md}: the HIP kernels are built for md = 1, 2 and 3")
+    _, H, W = _map_dims(who, tgt_depth, "tgt_depth")
+    if H < 2 * md + 1 or W < 2 * md + 1:
+        raise RuntimeError(f"{who}: H={H}, W={W}: a window of md={md} needs H and W of at least {2 * md + 1}")
+    return _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+
+
+def loss_photo(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, ssim_weight, md=1):
+    """-> (value [B], count [B]): pdepth_loss_photo_f32, the warp, the masked L1 and the SSIM distance in one pass (count = pixels
+    of the mask)."""
+    who = "loss_photo"
+    _no_autograd(who, tgt_depth)
+    (B, H, W), t = _photo_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, md)
+    lib = load()
+    dev = t[0].device
+    ws_bytes = _entry(lib, "pdepth_loss_photo_workspace_bytes")(B, H, W)
+    out = torch.empty((2, B), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_photo_f32")(*(x.data_ptr() for x in t), B, H, W, float(ssim_weight), md, out[0].data_ptr(),
+                                                  out[1].data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return out[0], out[1]
+
+
+def loss_photo_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count, g_value, ssim_weight, md=1):
+    """-> g_tgt_depth [B,H,W]: pdepth_loss_photo_backward_f32."""
+    who = "loss_photo_backward"
+    (B, H, W), t = _photo_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, md)
+    _shape(count, (B,), "count", who)
+    _shape(g_value, (B,), "g_value", who)
+    count, g_value = _maps(who, count=count, g_value=g_value)
+    lib = load()
+    dev = t[0].device
+    g = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_photo_backward_f32")(*(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W,
+                                                           float(ssim_weight), md, g.data_ptr(), _stream(dev))
     _check(rc, lib)
     return g
 

@@ -85,45 +85,7 @@ __global__ __launch_bounds__(256) void loss_dsc_bwd_kernel(DscArgs g, const floa
 }
 
 // ---- RGB stereo consistency ----------------------------------------------------------------------------------------------------
-struct RscArgs {
-    const float* src;      // [B,3,H,W] source image
-    const float* tgt;      // [B,3,H,W] target image
-    const float* depth;    // [B,H,W] target depth
-    const float* Kinv;
-    const float* proj;
-    int H, W;
-};
-
-struct RscPixel {
-    WarpSample q;
-    float m;
-    float d[3];            // tgt_c m - warped_c m
-    float gx[3], gy[3];    // d warped_c / d ix, d warped_c / d iy
-};
-
-template <bool GRAD>
-__device__ __forceinline__ RscPixel rsc_pixel(const RscArgs& g, int b, int pix, int x, int y) {
-    const int H = g.H, W = g.W, HW = H * W;
-    RscPixel p;
-    p.q = warp_sample(g.Kinv + b * 9, g.proj + b * 12, x, y, g.depth[(size_t)b * HW + pix], H, W);
-    const WarpSample& q = p.q;
-    p.m = (warp_valid(q) && y >= H / 3) ? 1.0f : 0.0f;
-    const TapMask taps = tap_mask(q);
-    const float* ib = g.src + (size_t)b * 3 * HW + (q.y0 * W + q.x0);
-    const float* tb = g.tgt + (size_t)b * 3 * HW + pix;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const Texels v = load_texels(ib + (size_t)c * HW, taps, W);
-        const float warped = bilinear_value(q, v);
-        p.d[c] = tb[(size_t)c * HW] * p.m - warped * p.m;
-        if (GRAD) {
-            p.gx[c] = bilinear_d_ix(q, v);
-            p.gy[c] = bilinear_d_iy(q, v);
-        }
-    }
-    return p;
-}
-
+// (the per-pixel chain and the camera products of the backward: loss_terms_math.hpp)
 __global__ __launch_bounds__(256) void loss_rsc_kernel(RscArgs g, int B, float* __restrict__ part) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     float num = 0.0f, den = 0.0f;
@@ -155,20 +117,7 @@ __global__ __launch_bounds__(256) void loss_rsc_bwd_kernel(RscArgs g, const floa
         gix = __builtin_fmaf(gw, p.gx[c], gix);
         giy = __builtin_fmaf(gw, p.gy[c], giy);
     }
-    float out = 0.0f;
-    if (q.finite) {
-        const PointGrad gp = point_grad(q, gix, giy, H, W);
-        const float* ki = g.Kinv + b * 9;
-        const float* pr = g.proj + b * 12;
-        const float fx = (float)x, fy = (float)y;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const float gcam = __builtin_fmaf(pr[8 + j], gp.Z, __builtin_fmaf(pr[4 + j], gp.Y, pr[j] * gp.X));
-            const float cam0 = __builtin_fmaf(ki[j * 3 + 2], 1.0f, __builtin_fmaf(ki[j * 3 + 1], fy, ki[j * 3 + 0] * fx));
-            out = __builtin_fmaf(gcam, cam0, out);
-        }
-    }
-    g_depth[(size_t)b * HW + pix] = out;
+    g_depth[(size_t)b * HW + pix] = rsc_depth_grad(g, b, x, y, q, gix, giy);
 }
 
 // ---- down-sample consistency ---------------------------------------------------------------------------------------------------

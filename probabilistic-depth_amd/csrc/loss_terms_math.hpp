@@ -1,6 +1,7 @@
 // The per-pixel arithmetic of the loss terms that more than one unit evaluates: the clamps, the relative difference and its
 // derivatives, and the chain of the depth stereo consistency term (loss_terms.hip: forward and backward; scatter_det.hip: the
-// order-independent sum of its src_depth gradient, through the same dsc_scatter).  Both units see the same bits of every pixel.
+// order-independent sum of its src_depth gradient, through the same dsc_scatter), and the chain of the RGB stereo consistency term
+// (loss_terms.hip: the L1 term; photo.hip: L1 and SSIM in one pass).  Every unit sees the same bits of every pixel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,6 +116,96 @@ __device__ __forceinline__ DscGrad dsc_pixel_grad(const DscArgs& g, const float*
 template <class Sink>
 __device__ __forceinline__ void dsc_scatter(const DscGrad& d, long long item0, Sink& sink) {
     if (d.tap >= 0 && d.v != 0.0f) sink.add(item0 + d.tap, d.v);
+}
+
+// ---- RGB stereo consistency ----------------------------------------------------------------------------------------------------
+// (loss_terms.hip: the L1 term; photo.hip: the same pixels with the SSIM distance of their windows)
+struct RscArgs {
+    const float* src;      // [B,3,H,W] source image
+    const float* tgt;      // [B,3,H,W] target image
+    const float* depth;    // [B,H,W] target depth
+    const float* Kinv;
+    const float* proj;
+    int H, W;
+};
+
+// the position of a pixel's sample, its mask and its in-bounds taps: what the three channels share
+struct RscSample {
+    WarpSample q;
+    float m;
+    TapMask taps;
+};
+__device__ __forceinline__ RscSample rsc_sample(const RscArgs& g, int b, int pix, int x, int y) {
+    const int H = g.H, W = g.W, HW = H * W;
+    RscSample s;
+    s.q = warp_sample(g.Kinv + b * 9, g.proj + b * 12, x, y, g.depth[(size_t)b * HW + pix], H, W);
+    s.m = (warp_valid(s.q) && y >= H / 3) ? 1.0f : 0.0f;
+    s.taps = tap_mask(s.q);
+    return s;
+}
+
+// one channel of a pixel: x = warped m, y = tgt m, d = y - x, and the derivatives of warped with respect to the position
+struct RscChannel {
+    float x, y, d, gx, gy;
+};
+template <bool GRAD>
+__device__ __forceinline__ RscChannel rsc_channel(const RscArgs& g, const RscSample& s, int b, int pix, int c) {
+    const int W = g.W, HW = g.H * W;
+    const WarpSample& q = s.q;
+    const Texels v = load_texels(g.src + ((size_t)b * 3 + c) * HW + (q.y0 * W + q.x0), s.taps, W);
+    const float warped = bilinear_value(q, v);
+    RscChannel r;
+    r.x = warped * s.m;
+    r.y = g.tgt[((size_t)b * 3 + c) * HW + pix] * s.m;
+    r.d = r.y - r.x;
+    r.gx = GRAD ? bilinear_d_ix(q, v) : 0.0f;
+    r.gy = GRAD ? bilinear_d_iy(q, v) : 0.0f;
+    return r;
+}
+
+struct RscPixel {
+    WarpSample q;
+    float m;
+    float x[3], y[3];      // warped_c m, tgt_c m
+    float d[3];            // tgt_c m - warped_c m
+    float gx[3], gy[3];    // d warped_c / d ix, d warped_c / d iy
+};
+
+template <bool GRAD>
+__device__ __forceinline__ RscPixel rsc_pixel(const RscArgs& g, int b, int pix, int x, int y) {
+    const RscSample s = rsc_sample(g, b, pix, x, y);
+    RscPixel p;
+    p.q = s.q;
+    p.m = s.m;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const RscChannel r = rsc_channel<GRAD>(g, s, b, pix, c);
+        p.x[c] = r.x;
+        p.y[c] = r.y;
+        p.d[c] = r.d;
+        p.gx[c] = r.gx;
+        p.gy[c] = r.gy;
+    }
+    return p;
+}
+
+// dL / d depth of pixel (x, y) from dL / d(ix, iy) of its sample: point_grad and the products behind it (the gradient of the
+// camera point, of the depth); a non-finite position passes nothing
+__device__ __forceinline__ float rsc_depth_grad(const RscArgs& g, int b, int x, int y, const WarpSample& q, float gix, float giy) {
+    float out = 0.0f;
+    if (q.finite) {
+        const PointGrad gp = point_grad(q, gix, giy, g.H, g.W);
+        const float* ki = g.Kinv + b * 9;
+        const float* pr = g.proj + b * 12;
+        const float fx = (float)x, fy = (float)y;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float gcam = __builtin_fmaf(pr[8 + j], gp.Z, __builtin_fmaf(pr[4 + j], gp.Y, pr[j] * gp.X));
+            const float cam0 = __builtin_fmaf(ki[j * 3 + 2], 1.0f, __builtin_fmaf(ki[j * 3 + 1], fy, ki[j * 3 + 0] * fx));
+            out = __builtin_fmaf(gcam, cam0, out);
+        }
+    }
+    return out;
 }
 
 }  // namespace

@@ -91,7 +91,7 @@ def SSIM(x, y, md=1):
 
 
 def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, pose_target2src, intr, viz=False, per_item=False,
-                                ssim_weight=0.0, ssim_md=1):
+                                ssim_weight=0.0, ssim_md=1, fused=False):
     """Photometric error between the target image and the source image warped into it with the target's depth map, over the
     pixels that land inside the source and lie below the top third (loss_blocks.py:114-145).  rgb [B,3,H,W], depth [B,H,W],
     pose [1,4,4] | [B,4,4], intr [B,3,3].  viz is accepted and ignored (the reference opens a window).
@@ -99,7 +99,21 @@ def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, p
     ssim_weight = w != 0 mixes in the SSIM distance the reference carries commented out (loss_blocks.py:128-129, where it suggests
     0.85), composed as its flow loss composes the photometric pieces (losses/flow_loss.py:13-27): with m the mask,
         (1 - w) mean_on_mask(|tgt m - warped m|, m) + w mean(SSIM(warped m, tgt m, ssim_md)) / mean(m),
-    the means per item with per_item.  With w == 0 the SSIM is not evaluated: the L1 term alone, with the bits it has always had."""
+    the means per item with per_item.  With w == 0 the SSIM is not evaluated: the L1 term alone, with the bits it has always had.
+
+    fused=True with w != 0: the same term as one HIP pass each way (ops.rgb_stereo_consistency, csrc/photo.hip) instead of the
+    composition below; the [B] vector with per_item, else the value of the single item (B == 1: the batch mean of the composition
+    and the item's mean are then one thing).  With w == 0 fused changes nothing."""
+    if fused and ssim_weight != 0:
+        B = src_rgb_img.shape[0]
+        if not per_item and B != 1:
+            raise RuntimeError("rgb_stereo_consistency_loss: fused=True returns per-item values; pass per_item=True for a batch "
+                               f"(B={B}), or one item at a time")
+        intr = intr.float()
+        proj = torch.matmul(intr, pose_target2src[:, 0:3, :].float()).expand(B, 3, 4)
+        value, _ = ops.rgb_stereo_consistency(src_rgb_img, target_rgb_img, target_depth_map, _inv3(intr).expand(B, 3, 3), proj,
+                                              ssim_weight=ssim_weight, ssim_md=ssim_md)
+        return value if per_item else value[0]
     warped, valid = _warp(src_rgb_img, target_depth_map, pose_target2src, intr, "bilinear")
     mask = (valid & _lower_two_thirds(valid.shape, src_rgb_img.device)).float().unsqueeze(1)
     diff = (target_rgb_img * mask - warped * mask).abs()

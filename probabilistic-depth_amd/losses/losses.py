@@ -19,9 +19,13 @@ per (intrinsics, pose) pair of the call, so the masks keep their bits.  The defa
 
 cfg.loss.rsc_ssim = w (absent: 0) mixes the SSIM distance into the two RGB consistency terms, rsc and rsc_low, over windows of half-width
 cfg.loss.rsc_ssim_md (absent: 1): (1 - w) L1 + w SSIM / mean(mask) per item, loss_blocks.rgb_stereo_consistency_loss; the reference's
-commented-out line (loss_blocks.py:128-129) suggests 0.85.  The fused rsc pass has no SSIM: with fused_terms=True and w != 0 the rsc
-term is the composition (the HIP warp and the HIP SSIM, ops.ssim), the other fused terms stay fused.  With the key absent or 0 no path
-changes.
+commented-out line (loss_blocks.py:128-129) suggests 0.85.  With fused_terms=True alone and w != 0 the rsc term stays the composition
+(the HIP warp and the HIP SSIM, ops.ssim), the other fused terms stay fused.  With the key absent or 0 no path changes.
+
+With fused_photo=True and w != 0 both RGB terms, rsc and rsc_low, are the single-pass photometric op instead (csrc/photo.hip,
+ops.rgb_stereo_consistency(..., ssim_weight=w, ssim_md=md): warp, L1 and SSIM in one launch each way), whatever fused_terms says;
+the low-resolution images still come from F.interpolate, the camera matrices from the helper the fused terms use.  With the key
+absent or 0, fused_photo changes nothing.  The default is False.
 """
 import torch
 import torch.nn as nn
@@ -37,12 +41,13 @@ def _stacked(labels):
 
 
 class BaseLoss(nn.Module):
-    def __init__(self, cfg, id, labels_from_depth=False, fused_terms=False):
+    def __init__(self, cfg, id, labels_from_depth=False, fused_terms=False, fused_photo=False):
         super().__init__()
         self.cfg = cfg
         self.id = id
         self.labels_from_depth = labels_from_depth
         self.fused_terms = fused_terms
+        self.fused_photo = fused_photo
 
     def _cross_entropy(self, volumes, tgt, label_key, depth_key, mask_key, d_candi):
         """(sum over the volumes and the items of the per-item cross-entropy, depth map [B,h,w] of the last volume)."""
@@ -133,8 +138,16 @@ class BaseLoss(nn.Module):
         rgb_l, rgb_r = tgt_l["rgb"][:, -1], tgt_r["rgb"][:, -1]
         ssim_w, ssim_md = getattr(mul, "rsc_ssim", 0.0), getattr(mul, "rsc_ssim_md", 1)
         photo = {"ssim_weight": ssim_w, "ssim_md": ssim_md} if ssim_w != 0 else {}
+        one_pass = self.fused_photo and ssim_w != 0
+
+        def photometric(src, tgt, depth, intr, pose):
+            return ops.rgb_stereo_consistency(src, tgt, depth, *camera(intr, pose), **photo)[0].sum()
+
         rsc_loss = 0
-        if mul.rsc_mul != 0 and fused and ssim_w == 0:
+        if mul.rsc_mul != 0 and one_pass:
+            rsc_loss = (photometric(rgb_r, rgb_l, large["l"], tgt_l["intrinsics_up"], pose_l2r) +
+                        photometric(rgb_l, rgb_r, large["r"], tgt_r["intrinsics_up"], pose_r2l))
+        elif mul.rsc_mul != 0 and fused and ssim_w == 0:
             rsc_loss = (ops.rgb_stereo_consistency(rgb_r, rgb_l, large["l"], *camera(tgt_l["intrinsics_up"], pose_l2r))[0].sum() +
                         ops.rgb_stereo_consistency(rgb_l, rgb_r, large["r"], *camera(tgt_r["intrinsics_up"], pose_r2l))[0].sum())
         elif mul.rsc_mul != 0:
@@ -145,6 +158,10 @@ class BaseLoss(nn.Module):
         if mul.rsc_low_mul != 0:
             low_l = F.interpolate(rgb_l, scale_factor=0.25, mode="bilinear")
             low_r = F.interpolate(rgb_r, scale_factor=0.25, mode="bilinear")
+        if mul.rsc_low_mul != 0 and one_pass:
+            rsc_low_loss = (photometric(low_r, low_l, small["l"], tgt_l["intrinsics"], pose_l2r) +
+                            photometric(low_l, low_r, small["r"], tgt_r["intrinsics"], pose_r2l))
+        elif mul.rsc_low_mul != 0:
             rsc_low_loss = (rgb_stereo_consistency_loss(low_r, low_l, small["l"], pose_l2r, tgt_l["intrinsics"], per_item=True, **photo).sum() +
                             rgb_stereo_consistency_loss(low_l, low_r, small["r"], pose_r2l, tgt_r["intrinsics"], per_item=True, **photo).sum())
 

@@ -262,17 +262,29 @@ def depth_stereo_consistency(src_depth, tgt_depth, src_mask, Kinv, proj, pose_ro
     return _native.loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
 
 
-def rgb_stereo_consistency(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
+def rgb_stereo_consistency(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, ssim_weight=0.0, ssim_md=1):
     """rgb_stereo_consistency_loss per item (losses/loss_blocks.py:114-145), one HIP pass: (value [B], count [B]).
 
     src_rgb, tgt_rgb [B,3,H,W]; tgt_depth [B,H,W] | [B,1,H,W]; Kinv, proj as above.  count = the pixels of the mask (valid & lower
-    two thirds); the value divides by 3 count.  Differentiable with respect to tgt_depth only, through the sample position."""
+    two thirds); the value divides by 3 count.  Differentiable with respect to tgt_depth only, through the sample position.
+
+    ssim_weight = w != 0: the photometric term, warp, L1 and SSIM in one pass each way (csrc/photo.hip), with m the mask
+        (1 - w) sum_c sum(|tgt_c m - warped_c m| m) / (3 count) + w mean(SSIM(warped m, tgt m, ssim_md)) / mean(m),
+    what loss_blocks.rgb_stereo_consistency_loss(..., ssim_weight=w, ssim_md=ssim_md, per_item=True) composes; ssim_md = 1, 2 or 3
+    (another: NotImplementedError; H or W below 2 ssim_md + 1: a RuntimeError that names the sizes).  The backward is a gather in a
+    fixed order: the same bits from call to call.  With w == 0 the call is the L1 pass it has always been, and ssim_md is ignored."""
     who = "rgb_stereo_consistency"
     tgt_depth = _squeeze_map(tgt_depth)
+    if ssim_weight == 0:
+        if _wants_grad(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
+            _refuse_data_grad(who, src_rgb=src_rgb, tgt_rgb=tgt_rgb, Kinv=Kinv, proj=proj)
+            return _RscFn.apply(src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+        return _native.loss_rsc(src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+    w, md = float(ssim_weight), int(ssim_md)
     if _wants_grad(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
         _refuse_data_grad(who, src_rgb=src_rgb, tgt_rgb=tgt_rgb, Kinv=Kinv, proj=proj)
-        return _RscFn.apply(src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
-    return _native.loss_rsc(src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
+        return _PhotoFn.apply(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, w, md)
+    return _native.loss_photo(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, w, md)
 
 
 def depth_consistency(large, small):
@@ -594,6 +606,26 @@ class _RscFn(torch.autograd.Function):
         if g_value is None or not ctx.needs_input_grad[2]:
             return (None,) * 5
         return None, None, _native.loss_rsc_backward(*ctx.saved_tensors, g_value), None, None
+
+
+class _PhotoFn(torch.autograd.Function):
+    """rgb_stereo_consistency with the SSIM mixed in, under autograd: (value, count); the backward recomputes from the inputs."""
+
+    @staticmethod
+    def forward(ctx, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, ssim_weight, md):
+        ctx.set_materialize_grads(False)
+        ctx.cfg = (ssim_weight, md)
+        value, count = _native.loss_photo(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, ssim_weight, md)
+        ctx.save_for_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count)
+        ctx.mark_non_differentiable(count)
+        return value, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, _g_count):
+        if g_value is None or not ctx.needs_input_grad[2]:
+            return (None,) * 7
+        return None, None, _native.loss_photo_backward(*ctx.saved_tensors, g_value, *ctx.cfg), None, None, None, None
 
 
 class _DcFn(torch.autograd.Function):
