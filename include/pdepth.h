@@ -372,8 +372,13 @@ int pdepth_dpv_fuse_backward_f32(const float *logp, const float *dmaps, const fl
  * kernel_size must be odd and (kernel_size-1)/2 <= max_displacement mod stride2 (beyond that the reference's kernel reads
  * outside its padded buffers); corr_multiply is accepted and ignored like in the reference kernel.  The configuration the
  * reference instantiates (kernel 1, stride1 1, pad_size = max_displacement <= 4*stride2: pwclite.py:123-125) runs
- * LDS-tiled fp32 kernels; everything else, and the fp16 entries (fp16 tensors, fp32 accumulation:
- * AT_DISPATCH_FLOATING_TYPES_AND_HALF at correlation_cuda_kernel.cu:352-369), a general gather kernel.
+ * tiled fp32 kernels as far as their tile fits the 160 KiB of LDS (forward: max_displacement <= 144; backward:
+ * max_displacement <= 17); beyond that, everything else, and the fp16 entries (fp16 tensors, fp32 accumulation:
+ * AT_DISPATCH_FLOATING_TYPES_AND_HALF at correlation_cuda_kernel.cu:352-369), a general gather kernel: which kernel serves
+ * a call is decided before anything is launched, and no accepted configuration is refused for its size of tile.
+ * Non-finite values: the zeros of the padding are multiplied, not skipped, as in the reference's padded buffers
+ * (correlation_cuda_kernel.cu:88-96): an inf or NaN of one input paired with padding of the other (or, in the backward, an
+ * inf or NaN of grad_output paired with padding) gives NaN, on every kernel and in both types alike.
  *   forward : input1, input2 [B,C,H,W] -> output;   backward: grad_output [B,ds*ds,oH,oW] -> grad_input1, grad_input2
  *   [B,C,H,W] (either may be NULL).
  */

@@ -316,7 +316,8 @@ int pdepth_correlation_forward_f32(const float* input1, const float* input2, int
     if (!input1 || !input2 || !output) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     int oH, oW;
     if (int rc = check_corr(who, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oH, &oW)) return rc;
-    if (corr_fast_path(pad_size, kernel_size, max_displacement, stride1, stride2))
+    if (corr_fast_path(pad_size, kernel_size, max_displacement, stride1, stride2) &&
+        pdepth::correlation_forward_fits(max_displacement / stride2, stride2))
         return launched(pdepth::launch_correlation_forward(input1, input2, B, C, H, W, max_displacement / stride2, stride2,
                                                            output, (hipStream_t)stream), who);
     return launched(pdepth::launch_correlation_general_forward(input1, input2, 0, B, C, H, W, pad_size, kernel_size, max_displacement,
@@ -332,7 +333,8 @@ int pdepth_correlation_backward_f32(const float* input1, const float* input2, co
     if (!input1 || !input2 || !grad_output || (!grad_input1 && !grad_input2)) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     int oH, oW;
     if (int rc = check_corr(who, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oH, &oW)) return rc;
-    if (corr_fast_path(pad_size, kernel_size, max_displacement, stride1, stride2))
+    if (corr_fast_path(pad_size, kernel_size, max_displacement, stride1, stride2) &&
+        pdepth::correlation_backward_fits(max_displacement / stride2, stride2))
         return launched(pdepth::launch_correlation_backward(input1, input2, grad_output, B, C, H, W, max_displacement / stride2,
                                                             stride2, grad_input1, grad_input2, (hipStream_t)stream), who);
     return launched(pdepth::launch_correlation_general_backward(input1, input2, grad_output, 0, B, C, H, W, pad_size, kernel_size,

@@ -2,7 +2,7 @@
 // correlation_cuda_kernel.cu:41-114; backward: the gradient of exactly that sum, which :116-300 compute over the padded
 // NHWC repacks), in fp32 and in fp16 I/O with fp32 accumulation (the reference dispatches AT_DISPATCH_FLOATING_TYPES_AND_HALF,
 // .cu:352-369).  The configuration the reference instantiates (kernel 1, stride1 1, pad = max_displacement: pwclite.py:123-125)
-// has its own LDS-tiled fp32 kernels in extras.hip; this file is the general path.
+// has its own LDS-tiled fp32 kernels in extras.hip, as far as their tiles fit the LDS; this file is the general path.
 //
 // Index arithmetic, as the reference's, in the coordinates of the zero-padded inputs (pad_size on every side):
 //     kr = (kernel_size - 1) / 2,  dr = max_displacement / stride2,  ds = 2 dr + 1,  border = kr + max_displacement
@@ -10,7 +10,9 @@
 //     (y1, x1) = (oy, ox) * stride1 + max_displacement          -- NOT + border: the reference's own offset
 //     out[b, (tj+dr)*ds + (ti+dr), oy, ox] = 1 / (k*k*C) * sum_{j,i in [-kr,kr]} sum_c
 //                                            in1p[b, c, y1+j, x1+i] * in2p[b, c, y1 + tj*stride2 + j, x1 + ti*stride2 + i]
-// No repack: a padded coordinate p maps to the image coordinate p - pad, zero outside.  Configurations whose indices
+// No repack: a padded coordinate p maps to the image coordinate p - pad, zero outside -- a zero that is multiplied, not a term
+// that is skipped: an inf or NaN paired with padding gives NaN, as in the reference's padded buffers (.cu:88-96), in the
+// forward and in both gradients (only a 0 * 0 of padding with padding is left out).  Configurations whose indices
 // would leave the padded buffer (the reference reads out of bounds there) are refused by the C ABI.
 //
 //   forward : thread = one output element, lanes along ox (coalesced reads when stride1 = 1), channels in a loop;
@@ -53,10 +55,13 @@ __global__ __launch_bounds__(256) void corr_general_fwd(const T* __restrict__ in
     for (int j = -g.kr; j <= g.kr; ++j)
         for (int i = -g.kr; i <= g.kr; ++i) {
             const int ya = y1 + j, xa = x1 + i, yb = y2 + j, xb = x2 + i;
-            if ((unsigned)ya >= (unsigned)g.H || (unsigned)xa >= (unsigned)g.W || (unsigned)yb >= (unsigned)g.H || (unsigned)xb >= (unsigned)g.W)
-                continue;   // a zero of the padding on either side
+            const bool ina = (unsigned)ya < (unsigned)g.H && (unsigned)xa < (unsigned)g.W, inb = (unsigned)yb < (unsigned)g.H && (unsigned)xb < (unsigned)g.W;
+            if (!ina && !inb) continue;   // 0 * 0 of the padding on both sides
             const long long pa = (long long)ya * g.W + xa, pb = (long long)yb * g.W + xb;
-            for (int c = 0; c < g.C; ++c) acc = __builtin_fmaf(ldf(a, c * HW + pa), ldf(c2, c * HW + pb), acc);
+            if (ina && inb)
+                for (int c = 0; c < g.C; ++c) acc = __builtin_fmaf(ldf(a, c * HW + pa), ldf(c2, c * HW + pb), acc);
+            else   // a zero of the padding on one side, MULTIPLIED like the reference's padded buffer: 0 * inf = NaN
+                for (int c = 0; c < g.C; ++c) acc = __builtin_fmaf(ina ? ldf(a, c * HW + pa) : ldf(c2, c * HW + pb), 0.0f, acc);
         }
     stf(out, idx, acc * g.inv_n);
 }
@@ -76,8 +81,9 @@ __global__ __launch_bounds__(256) void corr_general_bwd(const T* __restrict__ ot
             // the partner texel in the other input, and the window centre (y1, x1) in padded coordinates of an output that
             // pairs this element with it through kernel offset (j, i)
             const int yo = WHICH == 1 ? y + tj * g.s2 : y - tj * g.s2, xo = WHICH == 1 ? x + ti * g.s2 : x - ti * g.s2;
-            if ((unsigned)yo >= (unsigned)g.H || (unsigned)xo >= (unsigned)g.W) continue;
-            const float ov = ldf(o, (long long)yo * g.W + xo);
+            // outside the image the partner is a zero of the padding, MULTIPLIED like in the reference's padded buffer: a
+            // gradient of inf or NaN there gives NaN
+            const float ov = ((unsigned)yo < (unsigned)g.H && (unsigned)xo < (unsigned)g.W) ? ldf(o, (long long)yo * g.W + xo) : 0.0f;
             const int tc = (tj + g.dr) * g.ds + (ti + g.dr);
             for (int j = -g.kr; j <= g.kr; ++j) {
                 const int y1 = (WHICH == 1 ? y : yo) + g.pad - j - g.md;   // = oy * stride1

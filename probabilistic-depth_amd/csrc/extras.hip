@@ -218,6 +218,23 @@ constexpr int CT = 16;       // tile edge
 constexpr int CCH = 8;       // channels per chunk
 constexpr int RMAX = 4;      // max displacement radius (in units of stride2)
 
+// Dynamic LDS of the two tiled kernels, stated once: the launchers below and the dispatch of capi.hip (through the two
+// predicates) read it here.  Above 64 KiB a launch opts in with hipFuncSetAttribute; above CORR_LDS_CAP (the CU's 160 KiB)
+// there is no launch: capi.hip asks the predicates BEFORE it launches anything and gives such a call to the general kernels.
+//   forward  (scalar kernel): (8 * 16 * (16 + 2 md) + 8 * 256) * 4 bytes -- over 64 KiB from md = 49, over the cap from md = 145
+//   backward                : 2 * 8 * (16 + 2 md)^2 * 4 bytes            -- over 64 KiB from md = 9,  over the cap from md = 18
+constexpr size_t CORR_LDS_CAP = 160 * 1024;
+static size_t correlation_forward_lds(int radius, int stride2) {
+    const size_t TW = (size_t)CT + 2 * (size_t)radius * (size_t)stride2;
+    return ((size_t)CCH * CT * TW + (size_t)CCH * 256) * sizeof(float);
+}
+static size_t correlation_backward_lds(int radius, int stride2) {
+    const size_t TWH = (size_t)CT + 2 * (size_t)radius * (size_t)stride2;
+    return (size_t)2 * CCH * TWH * TWH * sizeof(float);
+}
+bool correlation_forward_fits(int radius, int stride2) { return correlation_forward_lds(radius, stride2) <= CORR_LDS_CAP; }
+bool correlation_backward_fits(int radius, int stride2) { return correlation_backward_lds(radius, stride2) <= CORR_LDS_CAP; }
+
 template <int R>
 __global__ __launch_bounds__(256) void correlation_fwd_kernel(const float* __restrict__ x1,
                                                               const float* __restrict__ x2, int C, int H, int W,
@@ -364,9 +381,8 @@ hipError_t launch_correlation_forward(const float* x1, const float* x2, int B, i
     }
     const int ND = 2 * radius + 1;
     dim3 grid((W + CT - 1) / CT, (H + CT - 1) / CT, B * ND);
-    const int TW = CT + 2 * radius * stride2;
-    const size_t lds = (size_t)(CCH * CT * TW + CCH * 256) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = correlation_forward_lds(radius, stride2);
+    if (lds > CORR_LDS_CAP) return hipErrorInvalidValue;   // (capi.hip never sends such a call here)
     auto go_launch = [&](auto kern) -> hipError_t {
         if (lds > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -434,8 +450,8 @@ __global__ __launch_bounds__(256) void correlation_bwd_kernel(const float* __res
             const int dx = (j - r) * s2;
             const float* gd = gb + (size_t)(i * nd + j) * HW;
             if (WANT1) {
-                // x2 position paired with (y, x); outside the image the staged tile holds zeros, but the reference sum
-                // skips those terms -- adding +-0 leaves every partial sum unchanged
+                // x2 position paired with (y, x); outside the image the staged tile holds the zeros of the reference's padded
+                // buffer and the term is multiplied through like there: +-0 for a finite gradient, NaN for inf or NaN
                 const float g = inside ? gd[y * W + x] : 0.0f;
                 const float* p = t2 + (ty + halo + dy) * TWH + (tx + halo + dx);
 #pragma unroll
@@ -463,9 +479,8 @@ __global__ __launch_bounds__(256) void correlation_bwd_kernel(const float* __res
 
 hipError_t launch_correlation_backward(const float* x1, const float* x2, const float* go, int B, int C, int H, int W,
                                        int radius, int stride2, float* g1, float* g2, hipStream_t stream) {
-    const int TWH = CT + 2 * radius * stride2;
-    const size_t lds = (size_t)2 * CCH * TWH * TWH * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = correlation_backward_lds(radius, stride2);
+    if (lds > CORR_LDS_CAP) return hipErrorInvalidValue;   // (capi.hip never sends such a call here)
     dim3 grid((W + CT - 1) / CT, (H + CT - 1) / CT, B * ((C + CCH - 1) / CCH));
     auto go_launch = [&](auto kern) -> hipError_t {
         if (lds > 64 * 1024) {

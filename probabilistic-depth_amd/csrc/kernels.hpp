@@ -159,6 +159,10 @@ hipError_t launch_dpv_fuse(const float* logp, const float* dmaps, const float* m
 hipError_t launch_correlation_forward(const float* x1, const float* x2, int B, int C, int H, int W, int radius,
                                       int stride2, float* out, hipStream_t stream);
 int correlation_max_radius();
+// whether the tiled kernels' LDS tile of a (radius, stride2) fits the CU (extras.hip states the arithmetic); the C entries ask
+// before they launch anything, and a configuration that does not fit runs the general kernels
+bool correlation_forward_fits(int radius, int stride2);
+bool correlation_backward_fits(int radius, int stride2);
 // correlation_general.hip: every configuration of the reference's kernel, fp32 or fp16 I/O (half != 0), fp32 accumulation
 bool correlation_output_size(int H, int W, int pad, int k, int md, int s1, int* oH, int* oW);
 hipError_t launch_correlation_general_forward(const void* x1, const void* x2, int half, int B, int C, int H, int W, int pad, int k, int md,
