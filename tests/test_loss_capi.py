@@ -60,8 +60,8 @@ def test_forward_validation():
     for var in (0.0, -1.0, float("nan")):
         rc, msg = _fwd(label=None, depth_gt=FAKE * 6, var=var)
         assert rc == 1 and "variance must be positive" in msg
-    rc, msg = _fwd(var=0.0)   # the variance belongs to the from-depth form only
-    assert rc != 1 or "variance" not in msg
+    rc, msg = _fwd(var=0.0, ws_bytes=0)   # the variance belongs to the from-depth form only: the call gets as far as its workspace
+    assert rc == 3 and "workspace" in msg
     rc, msg = _fwd(loss=None)
     assert rc == 1 and "null output pointer" in msg
     lib = _native.load()
