@@ -64,7 +64,8 @@ extern "C" {
                                 *    pdepth_det_scale_exponent and the three _backward_det_f32 entries with their _det_workspace_bytes;
                                 *    pdepth_warp_feature_backward_f32, pdepth_warp_feature_backward_det_f32 and its _det_workspace_bytes;
                                 *    pdepth_ssim_f32, pdepth_ssim_backward_f32;
-                                *    pdepth_loss_photo_workspace_bytes, pdepth_loss_photo_f32, pdepth_loss_photo_backward_f32 */
+                                *    pdepth_loss_photo_workspace_bytes, pdepth_loss_photo_f32, pdepth_loss_photo_backward_f32;
+                                *    pdepth_ternary_f32, pdepth_ternary_backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -782,6 +783,30 @@ int pdepth_loss_photo_f32(const float *src_rgb, const float *tgt_rgb, const floa
 int pdepth_loss_photo_backward_f32(const float *src_rgb, const float *tgt_rgb, const float *tgt_depth, const float *Kinv,
                                    const float *proj, const float *count, const float *g_value, int32_t B, int32_t H, int32_t W,
                                    double ssim_weight, int32_t md, float *g_tgt_depth, void *stream);
+
+/*
+ * Ternary census distance between two RGB images and its gradients (csrc/ternary.hip): TernaryLoss(im, im_warp, max_distance) of
+ * losses/loss_blocks.py:8-44, the third photometric piece of losses/flow_loss.py:13-27.
+ *
+ * x, y [B,3,H,W] fp32 contiguous -> out [B,1,H,W], md = 1, 2 or 3, K = 2 md + 1.  With I = ((0.2989 r + 0.5870 g) + 0.1140 b) 255
+ * of x and I' of y, and per offset o of the K x K patch
+ *     t = I(p+o) - I(p)    n = t / sqrt(0.81 + t^2)    (n' from I')    d = (n - n')^2    h = d / (0.1 + d)
+ * out(p) = (sum_o h) / K^2 where p is at least md from every border, and 0 elsewhere: no output that is kept reads outside the
+ * image.  Square roots and divisions are correctly rounded and nothing is contracted, so n, d and h have the bits of the float32
+ * reference; the sum runs over the offsets rows first.  Where x and y are equal bit for bit, out is exactly 0.
+ * Backward: g_out [B,1,H,W] -> g_x, g_y [B,3,H,W]; either may be NULL (not computed), not both.  With G = g_out / K^2 on the
+ * pixels at least md from every border and 0 elsewhere (outside the image too), and h's derivatives being odd in (t, t'),
+ *     g_I(p) = -sum_o (G(p) + G(p+o)) dh/dt,     dh/dt = a 0.81 / s^3,  dh/dt' = -a 0.81 / s'^3,  a = 0.2 (n - n') / (0.1 + d)^2,
+ * s = sqrt(0.81 + t^2); g_x = g_I 255 (0.2989, 0.5870, 0.1140), likewise g_y from I'.  Every pixel of the image gets a gradient,
+ * the border ring included (its pixels are neighbours of interior ones).  A gather that recomputes from the inputs, in a fixed
+ * order, no atomics: two calls give the same bits; where x and y are equal bit for bit both gradients are exactly 0.
+ *
+ * B <= 65535 (an item per grid z), H, W >= 2 md + 1, H * W <= 2^30, H <= 524280; md outside 1..3: PDEPTH_E_ARG; the outputs may
+ * not alias each other or an input.  One launch each on `stream`; nothing is allocated, nothing waits for the host.
+ */
+int pdepth_ternary_f32(const float *x, const float *y, int32_t B, int32_t H, int32_t W, int32_t md, float *out, void *stream);
+int pdepth_ternary_backward_f32(const float *x, const float *y, const float *g_out, int32_t B, int32_t H, int32_t W, int32_t md,
+                                float *g_x, float *g_y, void *stream);
 
 #ifdef __cplusplus
 }

@@ -103,14 +103,16 @@ _SIGNATURES = {
     "pdepth_loss_photo_workspace_bytes": (_Z, [_I] * 3),
     "pdepth_loss_photo_f32": (c_int, [_P] * 5 + [_I] * 3 + [c_double, _I] + [_P] * 3 + [_Z, _P]),
     "pdepth_loss_photo_backward_f32": (c_int, [_P] * 7 + [_I] * 3 + [c_double, _I] + [_P] * 2),
+    "pdepth_ternary_f32": (c_int, [_P] * 2 + [_I] * 4 + [_P] * 2),
+    "pdepth_ternary_backward_f32": (c_int, [_P] * 3 + [_I] * 4 + [_P] * 3),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward and SSIM entries live in objects of their own: part of an entry's name -> the source file.  The
+# The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM and census entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
 _SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
-                    "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip",
+                    "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip", "_ternary_": "csrc/ternary.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -1372,6 +1374,60 @@ def ssim_backward(x, y, g_out, md=1, want_x=True, want_y=True):
     with _on_device(x.device):
         rc = _entry(lib, "pdepth_ssim_backward_f32")(x.data_ptr(), y.data_ptr(), g_out.data_ptr(), B, C, H, W, md, _ptr(g_x), _ptr(g_y),
                                                      _stream(x.device))
+    _check(rc, lib)
+    return g_x, g_y
+
+
+# ---- ternary census distance (ops.ternary) ------------------------------------------------------------------------------------------
+TERNARY_MD = (1, 2, 3)   # the patch half-widths the kernels are built for
+
+
+def _ternary_args(who, x, y, md):
+    """((B, H, W), x, y) of a census call: two [B,3,H,W] device tensors of one shape, as contiguous fp32.  The shapes are judged
+    first, where the tensors live; the device last."""
+    if md not in TERNARY_MD:
+        raise NotImplementedError(f"{who}: md={md}: the HIP kernels are built for md = 1, 2 and 3")
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+    if x.dim() != 4 or x.shape != y.shape:
+        raise RuntimeError(f"{who}: x and y must be two [B,3,H,W] tensors of one shape, got {list(x.shape)} and {list(y.shape)}")
+    B, C, H, W = x.shape
+    if B < 1 or C != 3:
+        raise RuntimeError(f"{who}: x and y must be [B,3,H,W] RGB images with B >= 1, got {list(x.shape)} and {list(y.shape)}")
+    if H < 2 * md + 1 or W < 2 * md + 1:
+        raise RuntimeError(f"{who}: H={H}, W={W}: a patch of md={md} needs H and W of at least {2 * md + 1}")
+    x, y = _maps(who, x=x, y=y)
+    return (B, H, W), x, y
+
+
+def ternary(x, y, md=1):
+    """x, y [B,3,H,W] -> dist [B,1,H,W]: pdepth_ternary_f32 on the current stream."""
+    who = "ternary"
+    _no_autograd(who, x, y)
+    (B, H, W), x, y = _ternary_args(who, x, y, md)
+    lib = load()
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
+    with _on_device(x.device):
+        rc = _entry(lib, "pdepth_ternary_f32")(x.data_ptr(), y.data_ptr(), B, H, W, md, out.data_ptr(), _stream(x.device))
+    _check(rc, lib)
+    return out
+
+
+def ternary_backward(x, y, g_out, md=1, want_x=True, want_y=True):
+    """g_out [B,1,H,W] -> (g_x [B,3,H,W] | None, g_y [B,3,H,W] | None): pdepth_ternary_backward_f32."""
+    who = "ternary_backward"
+    (B, H, W), x, y = _ternary_args(who, x, y, md)
+    _shape(g_out, (B, 1, H, W), "g_out", who)
+    (g_out,) = _maps(who, g_out=g_out)
+    if not (want_x or want_y):
+        raise RuntimeError(f"{who}: no gradient requested")
+    lib = load()
+    g_x = torch.empty_like(x) if want_x else None
+    g_y = torch.empty_like(y) if want_y else None
+    with _on_device(x.device):
+        rc = _entry(lib, "pdepth_ternary_backward_f32")(x.data_ptr(), y.data_ptr(), g_out.data_ptr(), B, H, W, md, _ptr(g_x), _ptr(g_y),
+                                                        _stream(x.device))
     _check(rc, lib)
     return g_x, g_y
 

@@ -90,8 +90,14 @@ def SSIM(x, y, md=1):
     return ops.ssim(x, y, md)
 
 
+def TernaryLoss(im, im_warp, max_distance=1):
+    """Ternary census distance of two RGB images over (2 max_distance + 1)^2 patches, [B,3,H,W] -> [B,1,H,W], 0 within max_distance
+    of a border (loss_blocks.py:8-44): one HIP pass forward, one backward (ops.ternary; max_distance = 1, 2 or 3)."""
+    return ops.ternary(im, im_warp, max_distance)
+
+
 def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, pose_target2src, intr, viz=False, per_item=False,
-                                ssim_weight=0.0, ssim_md=1, fused=False):
+                                ternary_weight=0.0, ternary_md=1, ssim_weight=0.0, ssim_md=1, fused=False):
     """Photometric error between the target image and the source image warped into it with the target's depth map, over the
     pixels that land inside the source and lie below the top third (loss_blocks.py:114-145).  rgb [B,3,H,W], depth [B,H,W],
     pose [1,4,4] | [B,4,4], intr [B,3,3].  viz is accepted and ignored (the reference opens a window).
@@ -103,7 +109,15 @@ def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, p
 
     fused=True with w != 0: the same term as one HIP pass each way (ops.rgb_stereo_consistency, csrc/photo.hip) instead of the
     composition below; the [B] vector with per_item, else the value of the single item (B == 1: the batch mean of the composition
-    and the item's mean are then one thing).  With w == 0 fused changes nothing."""
+    and the item's mean are then one thing).  With w == 0 fused changes nothing.
+
+    ternary_weight = wt != 0 mixes in the third piece of that flow loss, the census distance, the same way: with ws = ssim_weight,
+        (1 - ws - wt) L1 + ws mean(SSIM) / mean(m) + wt mean(TernaryLoss(warped m, tgt m, ternary_md)) / mean(m),
+    a piece whose weight is 0 not evaluated.  With wt == 0 the op is not called and the path, and so the bits, are those above.
+    The single-pass op has no census term: fused=True with wt != 0 is a RuntimeError."""
+    if fused and ternary_weight != 0:
+        raise RuntimeError("rgb_stereo_consistency_loss: fused=True is the single-pass op (csrc/photo.hip), which has no census term; "
+                           f"ternary_weight={ternary_weight} needs fused=False")
     if fused and ssim_weight != 0:
         B = src_rgb_img.shape[0]
         if not per_item and B != 1:
@@ -118,14 +132,20 @@ def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, p
     mask = (valid & _lower_two_thirds(valid.shape, src_rgb_img.device)).float().unsqueeze(1)
     diff = (target_rgb_img * mask - warped * mask).abs()
     photo = mean_on_mask(diff, mask, per_item)
-    if ssim_weight == 0:
+    if ssim_weight == 0 and ternary_weight == 0:
         return photo
-    dist = SSIM(warped * mask, target_rgb_img * mask, ssim_md)
-    if per_item:
-        structural = dist.reshape(dist.shape[0], -1).mean(1) / mask.reshape(mask.shape[0], -1).mean(1)
-    else:
-        structural = dist.mean() / mask.mean()
-    return (1.0 - ssim_weight) * photo + ssim_weight * structural
+
+    def over_mask(dist):
+        if per_item:
+            return dist.reshape(dist.shape[0], -1).mean(1) / mask.reshape(mask.shape[0], -1).mean(1)
+        return dist.mean() / mask.mean()
+
+    total = (1.0 - ssim_weight - ternary_weight) * photo   # (wt == 0: the factor, and the operations below, are those of the SSIM mix alone)
+    if ssim_weight != 0:
+        total = total + ssim_weight * over_mask(SSIM(warped * mask, target_rgb_img * mask, ssim_md))
+    if ternary_weight != 0:
+        total = total + ternary_weight * over_mask(TernaryLoss(warped * mask, target_rgb_img * mask, ternary_md))
+    return total
 
 
 def depth_stereo_consistency_loss(src_depth_img, target_depth_img, src_depth_mask, target_depth_mask, pose_target2src, intr,

@@ -26,6 +26,12 @@ With fused_photo=True and w != 0 both RGB terms, rsc and rsc_low, are the single
 ops.rgb_stereo_consistency(..., ssim_weight=w, ssim_md=md): warp, L1 and SSIM in one launch each way), whatever fused_terms says;
 the low-resolution images still come from F.interpolate, the camera matrices from the helper the fused terms use.  With the key
 absent or 0, fused_photo changes nothing.  The default is False.
+
+cfg.loss.rsc_ternary = wt (absent: 0) mixes the ternary census distance (ops.ternary, csrc/ternary.hip) into the same two terms,
+over patches of half-width cfg.loss.rsc_ternary_md (absent: 1): (1 - w - wt) L1 + w SSIM / mean(mask) + wt census / mean(mask)
+per item.  The fused passes have no census term, so with wt != 0 both terms are the composition of
+loss_blocks.rgb_stereo_consistency_loss around the HIP warp and the HIP ops, whatever fused_terms and fused_photo say; the other
+fused terms stay fused.  With the key absent or 0 no path changes.
 """
 import torch
 import torch.nn as nn
@@ -138,7 +144,10 @@ class BaseLoss(nn.Module):
         rgb_l, rgb_r = tgt_l["rgb"][:, -1], tgt_r["rgb"][:, -1]
         ssim_w, ssim_md = getattr(mul, "rsc_ssim", 0.0), getattr(mul, "rsc_ssim_md", 1)
         photo = {"ssim_weight": ssim_w, "ssim_md": ssim_md} if ssim_w != 0 else {}
-        one_pass = self.fused_photo and ssim_w != 0
+        census_w = getattr(mul, "rsc_ternary", 0.0)
+        if census_w != 0:
+            photo.update(ternary_weight=census_w, ternary_md=getattr(mul, "rsc_ternary_md", 1))
+        one_pass = self.fused_photo and ssim_w != 0 and census_w == 0
 
         def photometric(src, tgt, depth, intr, pose):
             return ops.rgb_stereo_consistency(src, tgt, depth, *camera(intr, pose), **photo)[0].sum()
@@ -147,7 +156,7 @@ class BaseLoss(nn.Module):
         if mul.rsc_mul != 0 and one_pass:
             rsc_loss = (photometric(rgb_r, rgb_l, large["l"], tgt_l["intrinsics_up"], pose_l2r) +
                         photometric(rgb_l, rgb_r, large["r"], tgt_r["intrinsics_up"], pose_r2l))
-        elif mul.rsc_mul != 0 and fused and ssim_w == 0:
+        elif mul.rsc_mul != 0 and fused and ssim_w == 0 and census_w == 0:
             rsc_loss = (ops.rgb_stereo_consistency(rgb_r, rgb_l, large["l"], *camera(tgt_l["intrinsics_up"], pose_l2r))[0].sum() +
                         ops.rgb_stereo_consistency(rgb_l, rgb_r, large["r"], *camera(tgt_r["intrinsics_up"], pose_r2l))[0].sum())
         elif mul.rsc_mul != 0:

@@ -322,6 +322,20 @@ def ssim(x, y, md=1):
     return _native.ssim(x, y, md)
 
 
+def ternary(x, y, md=1):
+    """Ternary census distance of two RGB images (losses/loss_blocks.py:8-44), one HIP pass: x, y [B,3,H,W] -> [B,1,H,W], the mean
+    over the (2 md + 1)^2 offsets o of d / (0.1 + d), d = (n_o - n'_o)^2, n_o = t_o / sqrt(0.81 + t_o^2), t_o = I(p+o) - I(p) on the
+    grayscale times 255; 0 within md of a border.  md = 1, 2 or 3 (another md: NotImplementedError; C != 3, or H or W below
+    2 md + 1: a RuntimeError that names the shapes).  The inputs go through .float().contiguous().  Where x and y are equal bit for
+    bit the result and both gradients are exactly 0.  Differentiable with respect to x and / or y (csrc/ternary.hip: a gather, the
+    same bits from call to call); the kernel is asked only for the gradients that are needed, and the forward under autograd is
+    the no-grad kernel call."""
+    md = int(md)
+    if _wants_grad(x, y):
+        return _TernaryFn.apply(x, y, md)
+    return _native.ternary(x, y, md)
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
@@ -683,6 +697,27 @@ class _SsimFn(torch.autograd.Function):
             return None, None, None
         x, y = ctx.saved_tensors
         g_x, g_y = _native.ssim_backward(x, y, g_out, ctx.md, want_x=want_x, want_y=want_y)
+        return (g_x.to(x.dtype) if want_x else None), (g_y.to(y.dtype) if want_y else None), None
+
+
+class _TernaryFn(torch.autograd.Function):
+    """ternary under autograd."""
+
+    @staticmethod
+    def forward(ctx, x, y, md):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, y)
+        ctx.md = md
+        return _native.ternary(x, y, md)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_out is None or not (want_x or want_y):
+            return None, None, None
+        x, y = ctx.saved_tensors
+        g_x, g_y = _native.ternary_backward(x, y, g_out, ctx.md, want_x=want_x, want_y=want_y)
         return (g_x.to(x.dtype) if want_x else None), (g_y.to(y.dtype) if want_y else None), None
 
 
