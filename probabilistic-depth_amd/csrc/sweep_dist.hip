@@ -209,6 +209,12 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
         }
         ty_ = small_idx ? fdiv(tile, tiles_x) : tile / tiles_x;
         tx_ = tile - ty_ * tiles_x;
+        // NCHW entry: the queues hand out the batch items LAST TO FIRST.  The pack kernel has just written the packed source, item 0
+        // first; what is read first here is then what was written last -- the item likeliest to be in the Infinity Cache still,
+        // with the least traffic between its write and its read -- and the items written early are read late either way (the
+        // forward order put a whole pack and sweep of the other items between the write and the read of EVERY item).  Which
+        // item a block belongs to changes no bit of it.  A packed source was written by someone else, some time ago: as it was.
+        if (DIST_REV_BATCH && KARG(const float*, a.src) != nullptr) b_ = KARG(int, a.B) - 1 - b_;
     };
     // (when the grid covers every item -- small problems -- workgroup i takes item i of its XCD's band: no atomics.  Re-read from
     //  the kernel arguments where it is used: a flag that lives across the kernel is a scalar register pair spilled)

@@ -32,6 +32,9 @@
 #ifndef DIST_QUEUE_WAVE
 #define DIST_QUEUE_WAVE 3     // the wave whose lane 0 is the workgroup's queue thread (pops, resolves, decodes, publishes, counts, leaves); with DIST_DECODE_EARLY == 2 the last wave in the order of the texel-block shares, whichever it is (wave 0 there, with its full share: +2.2 % headline)
 #endif
+#ifndef DIST_REV_BATCH
+#define DIST_REV_BATCH 1      // 1: on the NCHW entry the queues hand out the batch items last to first -- the pack kernel wrote the last one last (bit-identical; headline -2.1 %, the sweep kernel 277 -> 272 us: profiles/r14_l2_warm/); 0: first to last
+#endif
 #ifndef DIST_ONE_EACH_X
 #define DIST_ONE_EACH_X 6  // a workgroup per item, no queue, up to this many items per resident workgroup (2 .. 24: the large shapes are indifferent; profiles/r06_ab/)
 #endif
