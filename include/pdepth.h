@@ -65,7 +65,8 @@ extern "C" {
                                 *    pdepth_warp_feature_backward_f32, pdepth_warp_feature_backward_det_f32 and its _det_workspace_bytes;
                                 *    pdepth_ssim_f32, pdepth_ssim_backward_f32;
                                 *    pdepth_loss_photo_workspace_bytes, pdepth_loss_photo_f32, pdepth_loss_photo_backward_f32;
-                                *    pdepth_ternary_f32, pdepth_ternary_backward_f32 */
+                                *    pdepth_ternary_f32, pdepth_ternary_backward_f32;
+                                *    pdepth_range_map_workspace_bytes, pdepth_range_map_f32, pdepth_depth_range_map_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -807,6 +808,40 @@ int pdepth_loss_photo_backward_f32(const float *src_rgb, const float *tgt_rgb, c
 int pdepth_ternary_f32(const float *x, const float *y, int32_t B, int32_t H, int32_t W, int32_t md, float *out, void *stream);
 int pdepth_ternary_backward_f32(const float *x, const float *y, const float *g_out, int32_t B, int32_t H, int32_t W, int32_t md,
                                 float *g_x, float *g_y, void *stream);
+
+/*
+ * Range map of a forward splat and the occlusion mask behind it (csrc/occlusion.hip): get_corresponding_map (utils/warp_utils.py:
+ * 25-79) and 1 - get_occu_mask_backward (:102-108), the third operand of the photometric composition of losses/flow_loss.py:72-78.
+ *
+ *     range[b,y,x] = sum over the source pixels p of the bilinear weight with which p's position lands on (x, y)
+ *     visible      = (min(max(range, 0), 1) < th) ? 0 : 1                                  (1 = some source pixel sees it)
+ * Only in-bounds taps count; a NaN or infinite position adds nothing.  Two forms of the position:
+ *   pdepth_range_map_f32        coords [B,2,H,W]: un-normalised (x, y) per source pixel.  With w = x - floor(x), e = 1 - w and n, s
+ *                               likewise from y, the taps (floor x, floor y) ... (+1, +1) receive s e, s w, n e, n w: fp32, one
+ *                               rounding per operation.
+ *   pdepth_depth_range_map_f32  depth [B,H,W] of the source view, src_mask [B,H,W] or NULL (a pixel whose mask is 0 adds nothing),
+ *                               Kinv [B,3,3], proj [B,3,4]: the position is the one pdepth_inverse_warp_f32 samples pixel (x, y) at
+ *                               with these matrices and this depth, bit for bit -- its align_corners=False un-normalisation of
+ *                               cam2pixel's 2 X / (W - 1) - 1 included, so the mask describes the warp the opposite term performs.
+ * range and visible are [B,1,H,W]; either may be NULL (not written), not both.
+ *
+ * The sum is an order-independent integer sum (pdepth_det_scale_exponent(1, H W): every weight lies in [0, 1] and a destination
+ * receives at most one tap per source pixel, so no maximum pass is needed): the same bits from call to call and on any stream, and
+ * an item's result does not depend on its neighbours in the batch.  A destination's error is below (1 + its contributions) 2^-22
+ * against the float64 sum over the same fp32 positions.  There is no float-atomics variant: a mass within an ulp of th would flip a
+ * mask bit with the order of arrival.
+ *
+ * Workspace: roundup256(8 B H W) bytes, 256-byte aligned, cleared by the call; the query returns 0 for sizes out of range; missing,
+ * too small or misaligned: PDEPTH_E_WORKSPACE.  H * W <= 2^24, B <= 65535, H, W >= 1 (the depth form: >= 2); a null input, no
+ * output, a non-positive size or th NaN: PDEPTH_E_ARG, before any launch.  A memset and two launches on `stream`; nothing is
+ * allocated, nothing waits for the host.
+ */
+size_t pdepth_range_map_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_range_map_f32(const float *coords, int32_t B, int32_t H, int32_t W, float th, float *range, float *visible,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int pdepth_depth_range_map_f32(const float *depth, const float *src_mask, const float *Kinv, const float *proj, int32_t B, int32_t H,
+                               int32_t W, float th, float *range, float *visible, void *workspace, size_t workspace_bytes,
+                               void *stream);
 
 #ifdef __cplusplus
 }

@@ -105,14 +105,18 @@ _SIGNATURES = {
     "pdepth_loss_photo_backward_f32": (c_int, [_P] * 7 + [_I] * 3 + [c_double, _I] + [_P] * 2),
     "pdepth_ternary_f32": (c_int, [_P] * 2 + [_I] * 4 + [_P] * 2),
     "pdepth_ternary_backward_f32": (c_int, [_P] * 3 + [_I] * 4 + [_P] * 3),
+    "pdepth_range_map_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_range_map_f32": (c_int, [_P] + [_I] * 3 + [_F] + [_P] * 3 + [_Z, _P]),
+    "pdepth_depth_range_map_f32": (c_int, [_P] * 4 + [_I] * 3 + [_F] + [_P] * 3 + [_Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM and census entries live in objects of their own: part of an entry's name -> the source file.  The
+# The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM, census and range-map entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
 _SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
                     "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip", "_ternary_": "csrc/ternary.hip",
+                    "_range_map_": "csrc/occlusion.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -1430,6 +1434,75 @@ def ternary_backward(x, y, g_out, md=1, want_x=True, want_y=True):
                                                         _stream(x.device))
     _check(rc, lib)
     return g_x, g_y
+
+
+# ---- range map and occlusion mask (ops.range_map, ops.occlusion_mask, ops.depth_occlusion) -----------------------------------------
+def _range_call(who, entry, head, B, H, W, th, want_range, want_visible, dev):
+    """Outputs and workspace of a range-map entry, the call on the current stream: (range | None, visible | None), each [B,1,H,W]."""
+    th = float(th)
+    if th != th:
+        raise RuntimeError(f"{who}: th is NaN")
+    if not (want_range or want_visible):
+        raise RuntimeError(f"{who}: no output requested")
+    lib = load()
+    rng = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if want_range else None
+    vis = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if want_visible else None
+    ws_bytes = _entry(lib, "pdepth_range_map_workspace_bytes")(B, H, W)
+    if ws_bytes == 0:
+        raise RuntimeError(f"{who}: B={B}, H={H}, W={W}: H*W must be at most 2^24 and B at most 65535")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, entry)(*head, B, H, W, th, _ptr(rng), _ptr(vis), ws.data_ptr(), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return rng, vis
+
+
+def _fp32_maps(who, **named):
+    """Contiguous device tensors of a range-map entry, which must be fp32 already (a position in half precision is another position)."""
+    out = []
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name}: expected float32, got {t.dtype}")
+    for name, t in named.items():
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+        out.append(t.contiguous())
+    return out
+
+
+def range_map(coords, th=0.2, want_range=True, want_visible=False):
+    """coords [B,2,H,W] un-normalised (x, y) -> (range [B,1,H,W] | None, visible [B,1,H,W] | None): pdepth_range_map_f32 on the
+    current stream, no host synchronisation."""
+    who = "range_map"
+    _no_autograd(who, coords)
+    if not isinstance(coords, torch.Tensor):
+        raise TypeError(f"{who}: coords: expected a torch.Tensor")
+    if coords.dim() != 4 or coords.shape[1] != 2 or min(coords.shape) < 1:
+        raise RuntimeError(f"{who}: coords must be [B,2,H,W] with B, H, W >= 1, got {list(coords.shape)}")
+    B, _, H, W = coords.shape
+    (coords,) = _fp32_maps(who, coords=coords)
+    return _range_call(who, "pdepth_range_map_f32", (coords.data_ptr(),), B, H, W, th, want_range, want_visible, coords.device)
+
+
+def depth_range_map(depth, Kinv, proj, src_mask=None, th=0.2, want_range=True, want_visible=False):
+    """depth [B,H,W] of the source view (+ src_mask [B,H,W]), Kinv [B,3,3], proj [B,3,4] -> (range | None, visible | None), each
+    [B,1,H,W]: pdepth_depth_range_map_f32 on the current stream, no host synchronisation."""
+    who = "depth_range_map"
+    _no_autograd(who, depth, src_mask, Kinv, proj)
+    if not isinstance(depth, torch.Tensor):
+        raise TypeError(f"{who}: depth: expected a torch.Tensor")
+    B, H, W = _map_dims(who, depth, "depth")
+    _shape(Kinv, (B, 3, 3), "Kinv", who)
+    _shape(proj, (B, 3, 4), "proj", who)
+    named = {"depth": depth, "Kinv": Kinv, "proj": proj}
+    if src_mask is not None:
+        _shape(src_mask, (B, H, W), "src_mask", who)
+        named["src_mask"] = src_mask
+    t = _fp32_maps(who, **named)
+    head = (t[0].data_ptr(), _ptr(t[3] if src_mask is not None else None), t[1].data_ptr(), t[2].data_ptr())
+    return _range_call(who, "pdepth_depth_range_map_f32", head, B, H, W, th, want_range, want_visible, t[0].device)
 
 
 # ---- evaluation metrics (ops.depth_metrics) -----------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // Order-independent sums of fp32 contributions: exact integer accumulation.  Users: sweep_bwd_det.hip (exponent from a bound, its
 // own policies in sweep_bwd_body.hpp); scatter_det.hip and warp_bwd.hip (exponent from the exact maximum: the sinks,
-// max_exponent_pass and max_exponent_scatter below); extras.hip and loss_terms.hip take FloatAtomics for the same scatter bodies.
+// max_exponent_pass and max_exponent_scatter below); occlusion.hip (exponent known before the launch: fixed_exponent_scatter);
+// extras.hip and loss_terms.hip take FloatAtomics for the same scatter bodies.
 //
 // Float addition is not associative, integer addition is.  A contribution q (fp32) is scaled by 2^S (exact: the product is
 // formed in double, whose exponent range holds every fp32 times every 2^S chosen below), rounded to the nearest integer, ties to
@@ -171,6 +172,27 @@ inline hipError_t max_exponent_scatter(void* workspace, int B, size_t per_item, 
     launch(std::integral_constant<int, 0>{}, hdr, acc);
     launch(std::integral_constant<int, 1>{}, hdr, acc);
     return det_convert(workspace, B, per_item, MaxExponent{n}, out, stream);
+}
+
+// ---- a scatter whose exponent is known before the launch (occlusion.hip: every contribution lies in [0, 1]) --------------------
+// No header, no pass 0: the workspace is the accumulator alone (WORDS == 0), and S = det_scale_exponent(bound, n) is computed by the
+// caller on the host, once, for every item.
+struct FixedExponent {
+    static constexpr int WORDS = 0;
+    int S;
+    __host__ __device__ int operator()(const uint32_t*) const { return S; }
+};
+
+// The host side of a fixed-exponent scatter: clear the accumulator, one pass.  launch(sink) launches the kernel, whose lanes hand
+// their contributions to sink.add; the convert pass is the caller's (det_convert with FixedExponent{S}, or a kernel of its own
+// that reads det_accumulator(workspace, B, FixedExponent::WORDS) with det_to_float(., S)).  The caller has checked the workspace
+// (det_workspace_bytes(B, FixedExponent::WORDS, per_item)) and that S is an exponent.
+template <class Launch>
+inline hipError_t fixed_exponent_scatter(void* workspace, int B, size_t per_item, int S, hipStream_t stream, Launch launch) {
+    hipError_t e = hipMemsetAsync(workspace, 0, det_workspace_bytes(B, FixedExponent::WORDS, per_item), stream);
+    if (e != hipSuccess) return e;
+    launch(IntegerSum{det_accumulator(workspace, B, FixedExponent::WORDS), S});
+    return hipGetLastError();
 }
 
 }  // namespace fixed

@@ -7,7 +7,7 @@
 // Behind the position: the in-bounds taps (TapMask), the masked load of a channel's four texels, their bilinear value and its two
 // derivatives with respect to the position, the gradient of the projected point, and the scatter of an upstream gradient to the
 // taps through a sink (fixed_accum.hpp: FloatAtomics, MaxOfAbs, IntegerSum) -- each once, for the forward and backward kernels of
-// extras.hip, the rsc term of loss_terms.hip and the integer sums of scatter_det.hip.
+// extras.hip, the rsc term of loss_terms.hip, the integer sums of scatter_det.hip and the range map of occlusion.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,26 @@ struct WarpSample {
     bool finite, xi0, xi1, yi0, yi1;
     float xn, yn;
 };
+
+// the bilinear footprint of the un-normalised position (q.ix, q.iy): fractions, weights, the top-left tap and which taps lie inside
+__device__ __forceinline__ void place_taps(WarpSample& q, int H, int W) {
+    const float xf = floorf(q.ix), yf = floorf(q.iy);
+    q.w = q.ix - xf; q.e = 1.0f - q.w; q.n = q.iy - yf; q.s = 1.0f - q.n;
+    q.nw = q.s * q.e; q.ne = q.s * q.w; q.sw = q.n * q.e; q.se = q.n * q.w;
+    q.finite = (q.ix == q.ix) && (q.iy == q.iy);
+    q.x0 = (int)fminf(fmaxf(xf, -2.0f), (float)(W + 1)); q.y0 = (int)fminf(fmaxf(yf, -2.0f), (float)(H + 1));
+    q.xi0 = q.x0 >= 0 && q.x0 < W; q.xi1 = q.x0 + 1 >= 0 && q.x0 + 1 < W;
+    q.yi0 = q.y0 >= 0 && q.y0 < H; q.yi1 = q.y0 + 1 >= 0 && q.y0 + 1 < H;
+}
+
+// a sample at a given un-normalised position (the range map of occlusion.hip, whose positions arrive as data): the footprint
+// alone, the projected point left at 0
+__device__ __forceinline__ WarpSample sample_at(float ix, float iy, int H, int W) {
+    WarpSample q{};
+    q.ix = ix; q.iy = iy;
+    place_taps(q, H, W);
+    return q;
+}
 
 __device__ __forceinline__ WarpSample warp_sample(const float* __restrict__ ki, const float* __restrict__ pr, int x, int y,
                                                    float d, int H, int W) {
@@ -43,13 +63,7 @@ __device__ __forceinline__ WarpSample warp_sample(const float* __restrict__ ki, 
     q.yn = 2.0f * (pc[1] / q.Z) / (float)(H - 1) - 1.0f;
     q.ix = __builtin_fmaf(q.xn + 1.0f, (float)W / 2.0f, -0.5f);
     q.iy = __builtin_fmaf(q.yn + 1.0f, (float)H / 2.0f, -0.5f);
-    const float xf = floorf(q.ix), yf = floorf(q.iy);
-    q.w = q.ix - xf; q.e = 1.0f - q.w; q.n = q.iy - yf; q.s = 1.0f - q.n;
-    q.nw = q.s * q.e; q.ne = q.s * q.w; q.sw = q.n * q.e; q.se = q.n * q.w;
-    q.finite = (q.ix == q.ix) && (q.iy == q.iy);
-    q.x0 = (int)fminf(fmaxf(xf, -2.0f), (float)(W + 1)); q.y0 = (int)fminf(fmaxf(yf, -2.0f), (float)(H + 1));
-    q.xi0 = q.x0 >= 0 && q.x0 < W; q.xi1 = q.x0 + 1 >= 0 && q.x0 + 1 < W;
-    q.yi0 = q.y0 >= 0 && q.y0 < H; q.yi1 = q.y0 + 1 >= 0 && q.y0 + 1 < H;
+    place_taps(q, H, W);
     return q;
 }
 

@@ -32,6 +32,15 @@ def _lower_two_thirds(shape, device):
     return keep
 
 
+def _visibility(occlusion, shape):
+    """An occlusion= argument, [B,1,H,W] | [B,H,W], as the fp32 [B,1,H,W] factor of a term's mask of that shape."""
+    vis = occlusion.float()
+    vis = vis.unsqueeze(1) if vis.dim() == 3 else vis
+    if tuple(vis.shape) != tuple(shape):
+        raise RuntimeError(f"occlusion must be {list(shape)} or {[shape[0]] + list(shape[2:])}, got {list(occlusion.shape)}")
+    return vis
+
+
 def _inv3(m):
     """Inverse of [B,3,3] matrices by the adjugate: elementwise, on the device the matrices live on."""
     a, b, c, d, e, f, g, h, i = m.reshape(-1, 9).unbind(1)
@@ -97,7 +106,7 @@ def TernaryLoss(im, im_warp, max_distance=1):
 
 
 def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, pose_target2src, intr, viz=False, per_item=False,
-                                ternary_weight=0.0, ternary_md=1, ssim_weight=0.0, ssim_md=1, fused=False):
+                                occlusion=None, ternary_weight=0.0, ternary_md=1, ssim_weight=0.0, ssim_md=1, fused=False):
     """Photometric error between the target image and the source image warped into it with the target's depth map, over the
     pixels that land inside the source and lie below the top third (loss_blocks.py:114-145).  rgb [B,3,H,W], depth [B,H,W],
     pose [1,4,4] | [B,4,4], intr [B,3,3].  viz is accepted and ignored (the reference opens a window).
@@ -114,7 +123,15 @@ def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, p
     ternary_weight = wt != 0 mixes in the third piece of that flow loss, the census distance, the same way: with ws = ssim_weight,
         (1 - ws - wt) L1 + ws mean(SSIM) / mean(m) + wt mean(TernaryLoss(warped m, tgt m, ternary_md)) / mean(m),
     a piece whose weight is 0 not evaluated.  With wt == 0 the op is not called and the path, and so the bits, are those above.
-    The single-pass op has no census term: fused=True with wt != 0 is a RuntimeError."""
+    The single-pass op has no census term: fused=True with wt != 0 is a RuntimeError.
+
+    occlusion: a visibility map of the target view, [B,1,H,W] | [B,H,W], 1 where some source pixel sees the target pixel
+    (ops.depth_occlusion of the source's depth map; the occu_mask of losses/flow_loss.py:72-78).  It multiplies the mask m before
+    anything is averaged, so the band beside a depth edge that the source camera cannot see is left out of every piece.  With None
+    not one operation changes.  The single-pass op has no mask input: fused=True with an occlusion map is a RuntimeError."""
+    if fused and occlusion is not None:
+        raise RuntimeError("rgb_stereo_consistency_loss: fused=True is the single-pass op (csrc/photo.hip), which has no mask input; "
+                           "an occlusion map needs fused=False")
     if fused and ternary_weight != 0:
         raise RuntimeError("rgb_stereo_consistency_loss: fused=True is the single-pass op (csrc/photo.hip), which has no census term; "
                            f"ternary_weight={ternary_weight} needs fused=False")
@@ -130,6 +147,8 @@ def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, p
         return value if per_item else value[0]
     warped, valid = _warp(src_rgb_img, target_depth_map, pose_target2src, intr, "bilinear")
     mask = (valid & _lower_two_thirds(valid.shape, src_rgb_img.device)).float().unsqueeze(1)
+    if occlusion is not None:
+        mask = mask * _visibility(occlusion, mask.shape)
     diff = (target_rgb_img * mask - warped * mask).abs()
     photo = mean_on_mask(diff, mask, per_item)
     if ssim_weight == 0 and ternary_weight == 0:
@@ -149,12 +168,13 @@ def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, p
 
 
 def depth_stereo_consistency_loss(src_depth_img, target_depth_img, src_depth_mask, target_depth_mask, pose_target2src, intr,
-                                  pose_src2target=None, per_item=False):
+                                  pose_src2target=None, per_item=False, occlusion=None):
     """Relative difference between the target depth map and the source depth map brought into the target view: the source
     depths are re-expressed in the target camera (transform_dmap with the inverse pose), masked, and fetched with a nearest
     warp along the target's own depth (loss_blocks.py:147-171).  depth maps [B,1,H,W], masks [B,1,H,W] | [B,H,W], pose
     [1,4,4] | [B,4,4], intr [B,3,3].  pose_src2target: the inverse of the pose where the caller already has it (else it is
-    inverted here); target_depth_mask is unused, as in the reference."""
+    inverted here); target_depth_mask is unused, as in the reference.  occlusion: a visibility map of the target view as
+    rgb_stereo_consistency_loss takes it; it multiplies the term's mask before the average.  With None not one operation changes."""
     B, _, H, W = src_depth_img.shape
     back = pose_src2target if pose_src2target is not None else _inv4(pose_target2src)
     moved = iv.transform_dmap(src_depth_img[:, 0], back, intr)
@@ -162,6 +182,8 @@ def depth_stereo_consistency_loss(src_depth_img, target_depth_img, src_depth_mas
     warped, valid = _warp(moved, target_depth_img[:, 0], pose_target2src, intr, "nearest")
     mask = (valid & _lower_two_thirds(valid.shape, src_depth_img.device)).unsqueeze(1) & (warped > 0.)
     mask = mask.float()
+    if occlusion is not None:
+        mask = mask * _visibility(occlusion, mask.shape)
     tgt = (target_depth_img * mask).clamp(min=1e-3)
     got = (warped * mask).clamp(min=1e-3)
     diff = ((tgt - got).abs() / (tgt + got).abs()).clamp(0, 1)

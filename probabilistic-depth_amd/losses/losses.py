@@ -32,6 +32,14 @@ over patches of half-width cfg.loss.rsc_ternary_md (absent: 1): (1 - w - wt) L1 
 per item.  The fused passes have no census term, so with wt != 0 both terms are the composition of
 loss_blocks.rgb_stereo_consistency_loss around the HIP warp and the HIP ops, whatever fused_terms and fused_photo say; the other
 fused terms stay fused.  With the key absent or 0 no path changes.
+
+cfg.loss.occ != 0 (absent: 0) leaves the pixels that the other camera cannot see out of the rsc, rsc_low and dsc terms.  Per call
+four visibility masks are computed, two sides at two resolutions, by splatting the other side's depth map into the view
+(ops.depth_occlusion, csrc/occlusion.hip; threshold cfg.loss.occ_th, absent: 0.2) with the camera pair of the term of the opposite
+direction, which the call caches anyway: the mask describes the warp that term performs.  The masks are constants (no gradient
+reaches a depth map through them) and order-independent sums: the same bits from call to call.  The fused passes have no mask
+input, so with occ != 0 those three terms are the compositions of loss_blocks (occlusion=...), whatever fused_terms and
+fused_photo say; the other fused terms stay fused.  With the key absent or 0 no path changes.
 """
 import torch
 import torch.nn as nn
@@ -120,13 +128,29 @@ class BaseLoss(nn.Module):
             dc_loss = (depth_consistency_loss(large["l"], small["l"], per_item=True).sum() +
                        depth_consistency_loss(large["r"], small["r"], per_item=True).sum())
 
+        # visibility of each view from the other one, per resolution: {} with cfg.loss.occ absent or 0
+        occ = getattr(mul, "occ", 0) != 0
+        occ_th = getattr(mul, "occ_th", 0.2)
+        seen = {}
+
+        def visible(hi):
+            """{"l", "r"} -> {"occlusion": visible [B,1,h,w]} of the view that is the term's target, once per resolution."""
+            if not occ:
+                return {"l": {}, "r": {}}
+            if hi not in seen:
+                dm = large if hi else small
+                ik = "intrinsics_up" if hi else "intrinsics"
+                seen[hi] = {"l": {"occlusion": ops.depth_occlusion(dm["r"], *camera(tgt_r[ik], pose_r2l), th=occ_th)},
+                            "r": {"occlusion": ops.depth_occlusion(dm["l"], *camera(tgt_l[ik], pose_l2r), th=occ_th)}}
+            return seen[hi]
+
         dsc_loss = 0
         if mul.dsc_mul != 0:
             for hi in (True, False):
                 dm = large if hi else small
                 mk = "masks_imgsizes" if hi else "masks"
                 ik = "intrinsics_up" if hi else "intrinsics"
-                if fused:   # right into left, then left into right
+                if fused and not occ:   # right into left, then left into right
                     Kinv, proj = camera(tgt_l[ik], pose_l2r)
                     dsc_loss = dsc_loss + ops.depth_stereo_consistency(dm["r"], dm["l"], tgt_r[mk], Kinv, proj, pose_r2l[:, 2],
                                                                        tgt_l[ik].float())[0].sum()
@@ -136,10 +160,11 @@ class BaseLoss(nn.Module):
                     continue
                 dl, dr = dm["l"].unsqueeze(1), dm["r"].unsqueeze(1)
                 # right into left, then left into right
+                vis = visible(hi)
                 dsc_loss = dsc_loss + depth_stereo_consistency_loss(dr, dl, tgt_r[mk], tgt_l[mk], pose_l2r, tgt_l[ik],
-                                                                    pose_src2target=pose_r2l, per_item=True).sum()
+                                                                    pose_src2target=pose_r2l, per_item=True, **vis["l"]).sum()
                 dsc_loss = dsc_loss + depth_stereo_consistency_loss(dl, dr, tgt_l[mk], tgt_r[mk], pose_r2l, tgt_r[ik],
-                                                                    pose_src2target=pose_l2r, per_item=True).sum()
+                                                                    pose_src2target=pose_l2r, per_item=True, **vis["r"]).sum()
 
         rgb_l, rgb_r = tgt_l["rgb"][:, -1], tgt_r["rgb"][:, -1]
         ssim_w, ssim_md = getattr(mul, "rsc_ssim", 0.0), getattr(mul, "rsc_ssim_md", 1)
@@ -147,7 +172,7 @@ class BaseLoss(nn.Module):
         census_w = getattr(mul, "rsc_ternary", 0.0)
         if census_w != 0:
             photo.update(ternary_weight=census_w, ternary_md=getattr(mul, "rsc_ternary_md", 1))
-        one_pass = self.fused_photo and ssim_w != 0 and census_w == 0
+        one_pass = self.fused_photo and ssim_w != 0 and census_w == 0 and not occ
 
         def photometric(src, tgt, depth, intr, pose):
             return ops.rgb_stereo_consistency(src, tgt, depth, *camera(intr, pose), **photo)[0].sum()
@@ -156,12 +181,15 @@ class BaseLoss(nn.Module):
         if mul.rsc_mul != 0 and one_pass:
             rsc_loss = (photometric(rgb_r, rgb_l, large["l"], tgt_l["intrinsics_up"], pose_l2r) +
                         photometric(rgb_l, rgb_r, large["r"], tgt_r["intrinsics_up"], pose_r2l))
-        elif mul.rsc_mul != 0 and fused and ssim_w == 0 and census_w == 0:
+        elif mul.rsc_mul != 0 and fused and ssim_w == 0 and census_w == 0 and not occ:
             rsc_loss = (ops.rgb_stereo_consistency(rgb_r, rgb_l, large["l"], *camera(tgt_l["intrinsics_up"], pose_l2r))[0].sum() +
                         ops.rgb_stereo_consistency(rgb_l, rgb_r, large["r"], *camera(tgt_r["intrinsics_up"], pose_r2l))[0].sum())
         elif mul.rsc_mul != 0:
-            rsc_loss = (rgb_stereo_consistency_loss(rgb_r, rgb_l, large["l"], pose_l2r, tgt_l["intrinsics_up"], per_item=True, **photo).sum() +
-                        rgb_stereo_consistency_loss(rgb_l, rgb_r, large["r"], pose_r2l, tgt_r["intrinsics_up"], per_item=True, **photo).sum())
+            vis = visible(True)
+            rsc_loss = (rgb_stereo_consistency_loss(rgb_r, rgb_l, large["l"], pose_l2r, tgt_l["intrinsics_up"], per_item=True, **photo,
+                                                    **vis["l"]).sum() +
+                        rgb_stereo_consistency_loss(rgb_l, rgb_r, large["r"], pose_r2l, tgt_r["intrinsics_up"], per_item=True, **photo,
+                                                    **vis["r"]).sum())
 
         rsc_low_loss = 0
         if mul.rsc_low_mul != 0:
@@ -171,8 +199,11 @@ class BaseLoss(nn.Module):
             rsc_low_loss = (photometric(low_r, low_l, small["l"], tgt_l["intrinsics"], pose_l2r) +
                             photometric(low_l, low_r, small["r"], tgt_r["intrinsics"], pose_r2l))
         elif mul.rsc_low_mul != 0:
-            rsc_low_loss = (rgb_stereo_consistency_loss(low_r, low_l, small["l"], pose_l2r, tgt_l["intrinsics"], per_item=True, **photo).sum() +
-                            rgb_stereo_consistency_loss(low_l, low_r, small["r"], pose_r2l, tgt_r["intrinsics"], per_item=True, **photo).sum())
+            vis = visible(False)
+            rsc_low_loss = (rgb_stereo_consistency_loss(low_r, low_l, small["l"], pose_l2r, tgt_l["intrinsics"], per_item=True, **photo,
+                                                        **vis["l"]).sum() +
+                            rgb_stereo_consistency_loss(low_l, low_r, small["r"], pose_r2l, tgt_r["intrinsics"], per_item=True, **photo,
+                                                        **vis["r"]).sum())
 
         smooth_loss = 0
         if mul.smooth_mul != 0 and fused:

@@ -336,6 +336,42 @@ def ternary(x, y, md=1):
     return _native.ternary(x, y, md)
 
 
+def range_map(coords):
+    """Range map of a forward splat (utils/warp_utils.py:25-79, get_corresponding_map), a memset and two HIP passes: coords
+    [B,2,H,W], un-normalised (x, y) positions of the source pixels, fp32 -> [B,1,H,W], the bilinear mass every pixel receives.  Only
+    in-bounds taps count; a NaN or infinite position adds nothing.  The sum is an order-independent integer sum (csrc/occlusion.hip):
+    the same bits from call to call.  Not differentiable: coords that require grad are refused."""
+    _refuse_grad("range_map", coords=coords)
+    return _native.range_map(coords)[0]
+
+
+def occlusion_mask(coords, th=0.2, want_range=False):
+    """visible [B,1,H,W]: 0 where the range map of coords, clamped to [0, 1], is below th -- where no source pixel lands -- and 1
+    elsewhere: 1 - get_occu_mask_backward's mask (utils/warp_utils.py:102-108) for coords = base grid + flow.  want_range: (visible,
+    range), both from one convert pass.  coords as ops.range_map takes them; a constant, without a graph."""
+    _refuse_grad("occlusion_mask", coords=coords)
+    rng, vis = _native.range_map(coords, th=th, want_range=bool(want_range), want_visible=True)
+    return (vis, rng) if want_range else vis
+
+
+def depth_occlusion(src_depth, Kinv, proj, th=0.2, src_mask=None, want_range=False):
+    """The visibility mask of the view a source depth map is splatted into: src_depth [B,H,W] | [B,1,H,W], src_mask likewise or
+    None (a pixel whose mask is 0 adds nothing), Kinv [B,3,3] and proj [B,3,4] as utils.inverse_warp.warp_with_matrices takes them
+    for the warp whose target is the source view.  A source pixel lands where that warp samples it -- the same chain, bit for bit --
+    so the mask describes the warp the consistency term of the opposite direction performs.  -> visible [B,1,H,W] (1 = seen), or
+    (visible, range) with want_range.  The mask is a constant: the inputs are detached (src_depth may require grad) and the result
+    carries no graph."""
+    who = "depth_occlusion"
+    for name, t in (("src_depth", src_depth), ("Kinv", Kinv), ("proj", proj)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+    src_depth, src_mask = (_squeeze_map(t) for t in (src_depth, src_mask))
+    detached = [t.detach() if isinstance(t, torch.Tensor) else t for t in (src_depth, Kinv, proj, src_mask)]
+    rng, vis = _native.depth_range_map(detached[0], detached[1], detached[2], src_mask=detached[3], th=th, want_range=bool(want_range),
+                                       want_visible=True)
+    return (vis, rng) if want_range else vis
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
