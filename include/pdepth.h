@@ -66,7 +66,9 @@ extern "C" {
                                 *    pdepth_ssim_f32, pdepth_ssim_backward_f32;
                                 *    pdepth_loss_photo_workspace_bytes, pdepth_loss_photo_f32, pdepth_loss_photo_backward_f32;
                                 *    pdepth_ternary_f32, pdepth_ternary_backward_f32;
-                                *    pdepth_range_map_workspace_bytes, pdepth_range_map_f32, pdepth_depth_range_map_f32 */
+                                *    pdepth_range_map_workspace_bytes, pdepth_range_map_f32, pdepth_depth_range_map_f32;
+                                *    pdepth_flow_warp_f32, pdepth_flow_warp_backward_f32, pdepth_flow_warp_backward_det_f32 and its
+                                *    _det_workspace_bytes, pdepth_flow_fb_check_f32; pdepth_loss_smooth1_f32 and its _backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -654,6 +656,8 @@ int pdepth_loss_smooth_backward_f32(const float *depth, const float *rgb, const 
  *           M_b = |gscale| max|grad_cost[b]| E_b, gscale = 2 / sigma (L2), 1 / sigma (L1), E_b = max|src[b]| + max|ref[b]| (L2), 1 (L1),
  *           the maxima from a pre-pass over the item's inputs;
  *   dsc, inverse_warp:  N = 4 H W (pixels x taps); M_b = the exact maximum of |q_i|, from a first run of the per-pixel chain.
+ *   warp_feature (the fourth case, further below):  N = H W, M_b likewise;
+ *   flow_warp (the fifth: grad_x of pdepth_flow_warp_backward_f32, declared with the flow entries below):  N = 4 H W, M_b likewise.
  * M_b == 0: the item's gradient is exactly 0.
  * Non-finite: if M_b is NaN or infinite -- a NaN or an infinity among the inputs that enter it --, or overflows (the sweep: M_b or
  * one of its factors |gscale| max|grad_cost[b]|, E_b at or above 2^127, where the fp32 chain may leave the finite range), EVERY
@@ -668,7 +672,8 @@ int pdepth_loss_smooth_backward_f32(const float *depth, const float *rgb, const 
  * Workspace (256-byte aligned; needed when the scattered gradient is requested; cleared by the call):
  *   sweep         roundup256(16 B) + roundup256(8 B V C H W) bytes: B = 4, V = 1, C = 67: 17.6 MB at 64 x 128, 281 MB at 256 x 512;
  *   dsc           roundup256(4 B)  + roundup256(8 B H W);
- *   inverse_warp  roundup256(4 B)  + roundup256(8 B C H W).
+ *   inverse_warp  roundup256(4 B)  + roundup256(8 B C H W);
+ *   flow_warp     roundup256(4 B)  + roundup256(8 B C H W).
  * The queries return 0 for sizes out of range.  A workspace that is missing, too small or misaligned is PDEPTH_E_WORKSPACE.
  *
  * pdepth_det_scale_exponent(bound, n): the exponent rule itself, a host function (the kernels call the same inline code): S for
@@ -842,6 +847,68 @@ int pdepth_range_map_f32(const float *coords, int32_t B, int32_t H, int32_t W, f
 int pdepth_depth_range_map_f32(const float *depth, const float *src_mask, const float *Kinv, const float *proj, int32_t B, int32_t H,
                                int32_t W, float th, float *range, float *visible, void *workspace, size_t workspace_bytes,
                                void *stream);
+
+/*
+ * flow_warp and the forward-backward check of the unsupervised flow loss (csrc/flow_warp.hip): utils/warp_utils.py:82-99 over
+ * F.grid_sample, bilinear, align_corners=False; the operands of losses/flow_loss.py:66-78.
+ *
+ * x [B,C,H,W] is sampled at base grid + flow [B,2,H,W] (channel 0 along x); pad: 0 = border, 1 = zeros.  The chain of pixel
+ * (row y, column x) (csrc/flow_warp_sample.hpp, run by every kernel of these entries): the position is formed in double from the
+ * fp32 flow, and only its fractions are rounded to fp32 --
+ *     vx = double(x) + double(flow[b,0,y,x])   (exact)        ix = vx (double(W) / double(W - 1)) - 0.5
+ * and likewise iy: the reference's mixed normalisation, 2 v / (W - 1) - 1 un-normalised by ((g + 1) W - 1) / 2, as the number it
+ * defines (the reference's own fp32 chain rounds the normalised coordinate near 1 and is about W / 2 eps32 from that number
+ * everywhere in the image: 2.5e-5 px at W = 832; the double operations are per pixel, not per channel).  Border: ix is clamped to
+ * [0, W - 1], iy to [0, H - 1].  x0 = floor(ix), x1 = x0 + 1; w = ix - x0, e = x1 - ix, n = iy - y0, s = y1 - iy, each rounded to
+ * fp32 once; from there fp32, one rounding per operation and no fma: the taps (x0, y0), (x1, y0), (x0, y1), (x1, y1) weigh e s,
+ * w s, e n, w n; each tap is tested for bounds on its own and an out-of-bounds tap contributes 0 (border at ix = W - 1: the x1
+ * column is outside, with weight 0).  out = ((v_nw nw + v_ne ne) + v_sw sw) + v_se se.
+ * A position that is not finite before the clamp has no tap and gives 0 in BOTH paddings, value and gradients -- a stated
+ * departure: ATen's clamp of a NaN is unspecified, and it clamps an infinite position to the border.
+ *
+ *   pdepth_flow_warp_f32               out [B,C,H,W].  One launch.
+ *   pdepth_flow_warp_backward_f32      grad_x [B,C,H,W] and grad_flow [B,2,H,W]; either may be NULL, not both.
+ *       grad_flow is written per owner, one thread summing d out / d (ix, iy) grad_out over the channels of its pixel in channel
+ *       order: no atomics, the same bits from call to call.  d ix / d flow_x = (W / 2) (2 / (W - 1)); with border padding the factor
+ *       is 0 where the position was clamped from strictly outside [0, W - 1] and 1 at exactly 0 or W - 1 (likewise y).
+ *       grad_x is a scatter of g w_tap: an in-bounds tap receives g w even when w == 0, an out-of-bounds tap nothing (the rules
+ *       of pdepth_warp_feature_backward_f32); float atomics into grad_x, zeroed by the call on the stream.
+ *   pdepth_flow_warp_backward_det_f32  grad_x as the order-independent sum of "Deterministic backward" above: its fifth case,
+ *       q_i = g w_tap, N = 4 H W, M_b the exact maximum of |q_i| over item b (a first run of the chain); M_b == 0, NaN and overflow
+ *       as the other _det entries.  grad_flow has the bits of the atomic entry.  Workspace: roundup256(4 B) + roundup256(8 B C H W)
+ *       bytes, 256-byte aligned, needed when grad_x is requested, cleared by the call; the query returns 0 for sizes out of range;
+ *       missing, too small or misaligned: PDEPTH_E_WORKSPACE.
+ *   pdepth_flow_fb_check_f32           occ [B,1,H,W] = 1.0 where |flow12 + w|^2 > scale (|flow12|^2 + |w|^2) + bias, else 0.0, with
+ *       w the two channels of flow21 sampled at base + flow12 with zeros padding by the chain above; |a|^2 = a_x a_x + a_y a_y,
+ *       the right side (|flow12|^2 + |w|^2) scale + bias, fp32.  One launch; a mask has no gradient.
+ * B <= 65535, H, W >= 2 (the reference divides by H - 1 and W - 1), H * W <= 2^30; a null pointer, a non-positive size, H or W
+ * below 2, an unknown pad, no gradient requested, a NaN scale or bias: PDEPTH_E_ARG, before any launch.  Nothing is allocated,
+ * nothing waits for the host.
+ */
+int pdepth_flow_warp_f32(const float *x, const float *flow, int32_t B, int32_t C, int32_t H, int32_t W, int32_t pad, float *out,
+                         void *stream);
+int pdepth_flow_warp_backward_f32(const float *x, const float *flow, const float *grad_out, int32_t B, int32_t C, int32_t H,
+                                  int32_t W, int32_t pad, float *grad_x, float *grad_flow, void *stream);
+size_t pdepth_flow_warp_backward_det_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int pdepth_flow_warp_backward_det_f32(const float *x, const float *flow, const float *grad_out, int32_t B, int32_t C, int32_t H,
+                                      int32_t W, int32_t pad, float *grad_x, float *grad_flow, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+int pdepth_flow_fb_check_f32(const float *flow12, const float *flow21, int32_t B, int32_t H, int32_t W, float scale, float bias,
+                             float *occ, void *stream);
+
+/*
+ * First-order smoothness of a flow (csrc/loss_smooth1.hip): smooth_grad_1st of losses/loss_blocks.py:210-220, the smoothness term
+ * of losses/flow_loss.py:29-32.  flo [B,Cf,H,W], image [B,Ci,H,W], one value for the batch:
+ *     wx = exp(-alpha mean_c |image[..., x+1] - image[..., x]|),   value = mean(wx |dx flo|) / 4 + mean(wy |dy flo|) / 4
+ * the means over [B,Cf,H,W-1] and [B,Cf,H-1,W].  fp32 per pair (the channel sum in channel order), a workgroup's 256 pixels summed
+ * in a fixed tree, the workgroups' sums added in a fixed order in double: the same bits from call to call.  value is ONE float.
+ * Workspace: pdepth_loss_terms_workspace_bytes(B, H, W).  Backward: g_value [1] -> g_flo [B,Cf,H,W], every flow value gathering
+ * its left / right and up / down differences, sign(0) = 0; no atomics.  image is data.  H, W >= 2, H * W <= 2^24, B <= 65535.
+ */
+int pdepth_loss_smooth1_f32(const float *flo, const float *image, int32_t B, int32_t Cf, int32_t Ci, int32_t H, int32_t W,
+                            float alpha, float *value, void *workspace, size_t workspace_bytes, void *stream);
+int pdepth_loss_smooth1_backward_f32(const float *flo, const float *image, const float *g_value, int32_t B, int32_t Cf, int32_t Ci,
+                                     int32_t H, int32_t W, float alpha, float *g_flo, void *stream);
 
 #ifdef __cplusplus
 }

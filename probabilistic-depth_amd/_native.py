@@ -108,15 +108,22 @@ _SIGNATURES = {
     "pdepth_range_map_workspace_bytes": (_Z, [_I] * 3),
     "pdepth_range_map_f32": (c_int, [_P] + [_I] * 3 + [_F] + [_P] * 3 + [_Z, _P]),
     "pdepth_depth_range_map_f32": (c_int, [_P] * 4 + [_I] * 3 + [_F] + [_P] * 3 + [_Z, _P]),
+    "pdepth_flow_warp_f32": (c_int, [_P] * 2 + [_I] * 5 + [_P] * 2),
+    "pdepth_flow_warp_backward_f32": (c_int, [_P] * 3 + [_I] * 5 + [_P] * 3),
+    "pdepth_flow_warp_backward_det_workspace_bytes": (_Z, [_I] * 4),
+    "pdepth_flow_warp_backward_det_f32": (c_int, [_P] * 3 + [_I] * 5 + [_P] * 3 + [_Z, _P]),
+    "pdepth_flow_fb_check_f32": (c_int, [_P] * 2 + [_I] * 3 + [_F] * 2 + [_P] * 2),
+    "pdepth_loss_smooth1_f32": (c_int, [_P] * 2 + [_I] * 5 + [_F] + [_P] * 2 + [_Z, _P]),
+    "pdepth_loss_smooth1_backward_f32": (c_int, [_P] * 3 + [_I] * 5 + [_F] + [_P] * 2),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM, census and range-map entries live in objects of their own: part of an entry's name -> the source file.  The
 # product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
 # loads, and a call of such an entry on it raises (_entry)
-_SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
+_SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_loss_smooth1_": "csrc/loss_smooth1.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
                     "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip", "_ternary_": "csrc/ternary.hip",
-                    "_range_map_": "csrc/occlusion.hip",
+                    "_range_map_": "csrc/occlusion.hip", "_flow_": "csrc/flow_warp.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -1503,6 +1510,128 @@ def depth_range_map(depth, Kinv, proj, src_mask=None, th=0.2, want_range=True, w
     t = _fp32_maps(who, **named)
     head = (t[0].data_ptr(), _ptr(t[3] if src_mask is not None else None), t[1].data_ptr(), t[2].data_ptr())
     return _range_call(who, "pdepth_depth_range_map_f32", head, B, H, W, th, want_range, want_visible, t[0].device)
+
+
+# ---- flow_warp, the forward-backward check and the flow's smoothness (ops.flow_warp, ops.flow_fb_check, ops.smooth_grad_1st) -----
+FLOW_PADS = {"border": 0, "zeros": 1}
+
+
+def _flow_args(who, x, flow, pad, xname="x", fname="flow"):
+    """((B, C, H, W), x, flow, pad code) of a flow_warp call: x [B,C,H,W] and flow [B,2,H,W], contiguous fp32 device tensors.  The
+    shapes are judged first, where the tensors live; the device last."""
+    if pad not in FLOW_PADS:
+        raise RuntimeError(f"{who}: pad must be 'border' or 'zeros', got {pad!r}")
+    for name, t in ((xname, x), (fname, flow)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise RuntimeError(f"{who}: {xname} must be [B,C,H,W] with B, C >= 1, got {list(x.shape)}")
+    B, C, H, W = x.shape
+    if H < 2 or W < 2:
+        raise RuntimeError(f"{who}: H={H}, W={W}: the grid is normalised by H - 1 and W - 1, both must be at least 2")
+    _shape(flow, (B, 2, H, W), fname, who)
+    x, flow = _fp32_maps(who, **{xname: x, fname: flow})
+    return (B, C, H, W), x, flow, FLOW_PADS[pad]
+
+
+def flow_warp(x, flow, pad="border"):
+    """x [B,C,H,W] sampled at base grid + flow [B,2,H,W] -> [B,C,H,W]: pdepth_flow_warp_f32 on the current stream."""
+    who = "flow_warp"
+    _no_autograd(who, x, flow)
+    (B, C, H, W), x, flow, code = _flow_args(who, x, flow, pad)
+    lib = load()
+    out = torch.empty_like(x)
+    with _on_device(x.device):
+        rc = _entry(lib, "pdepth_flow_warp_f32")(x.data_ptr(), flow.data_ptr(), B, C, H, W, code, out.data_ptr(), _stream(x.device))
+    _check(rc, lib)
+    return out
+
+
+def flow_warp_backward(x, flow, grad_out, pad="border", want_x=True, want_flow=True, deterministic=False):
+    """-> (grad_x [B,C,H,W] | None, grad_flow [B,2,H,W] | None): pdepth_flow_warp_backward_f32; deterministic:
+    pdepth_flow_warp_backward_det_f32 (grad_x as an order-independent sum; grad_flow has the same bits either way)."""
+    who = "flow_warp_backward"
+    (B, C, H, W), x, flow, code = _flow_args(who, x, flow, pad)
+    _shape(grad_out, (B, C, H, W), "grad_out", who)
+    (grad_out,) = _fp32_maps(who, grad_out=grad_out)
+    if not (want_x or want_flow):
+        raise RuntimeError(f"{who}: no gradient requested")
+    lib = load()
+    dev = x.device
+    g_x = torch.empty_like(x) if want_x else None
+    g_f = torch.empty_like(flow) if want_flow else None
+    args = (x.data_ptr(), flow.data_ptr(), grad_out.data_ptr(), B, C, H, W, code, _ptr(g_x), _ptr(g_f))
+    with _on_device(dev):
+        if deterministic:
+            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_flow_warp_backward_det_workspace_bytes")(B, C, H, W) if want_x else 0, dev)
+            rc = _entry(lib, "pdepth_flow_warp_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
+        else:
+            rc = _entry(lib, "pdepth_flow_warp_backward_f32")(*args, _stream(dev))
+    _check(rc, lib)
+    return g_x, g_f
+
+
+def flow_fb_check(flow12, flow21, scale=0.01, bias=0.5):
+    """flow12, flow21 [B,2,H,W] -> occ [B,1,H,W] (1 = the forward-backward check fails): pdepth_flow_fb_check_f32."""
+    who = "flow_fb_check"
+    _no_autograd(who, flow12, flow21)
+    if isinstance(flow12, torch.Tensor) and (flow12.dim() != 4 or flow12.shape[1] != 2):
+        raise RuntimeError(f"{who}: flow12 must be [B,2,H,W], got {list(flow12.shape)}")
+    (B, _, H, W), flow12, flow21, _ = _flow_args(who, flow12, flow21, "zeros", xname="flow12", fname="flow21")
+    lib = load()
+    occ = torch.empty((B, 1, H, W), dtype=torch.float32, device=flow12.device)
+    with _on_device(flow12.device):
+        rc = _entry(lib, "pdepth_flow_fb_check_f32")(flow12.data_ptr(), flow21.data_ptr(), B, H, W, float(scale), float(bias),
+                                                     occ.data_ptr(), _stream(flow12.device))
+    _check(rc, lib)
+    return occ
+
+
+def _smooth1_args(who, flo, image):
+    for name, t in (("flo", flo), ("image", image)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+    if flo.dim() != 4 or image.dim() != 4 or min(flo.shape) < 1 or min(image.shape) < 1 or \
+            (flo.shape[0],) + tuple(flo.shape[2:]) != (image.shape[0],) + tuple(image.shape[2:]):
+        raise RuntimeError(f"{who}: flo [B,Cf,H,W] and image [B,Ci,H,W] must share B, H and W, got {list(flo.shape)} and {list(image.shape)}")
+    B, Cf, H, W = flo.shape
+    if H < 2 or W < 2:
+        raise RuntimeError(f"{who}: H={H}, W={W}: both must be at least 2")
+    flo, image = _fp32_maps(who, flo=flo, image=image)
+    return (B, Cf, image.shape[1], H, W), flo, image
+
+
+def loss_smooth1(flo, image, alpha):
+    """-> value (a 0-dim tensor): pdepth_loss_smooth1_f32."""
+    who = "loss_smooth1"
+    _no_autograd(who, flo)
+    (B, Cf, Ci, H, W), flo, image = _smooth1_args(who, flo, image)
+    lib = load()
+    dev = flo.device
+    ws_bytes = _entry(lib, "pdepth_loss_terms_workspace_bytes")(B, H, W)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    out = torch.empty((1,), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_loss_smooth1_f32")(flo.data_ptr(), image.data_ptr(), B, Cf, Ci, H, W, float(alpha), out.data_ptr(),
+                                                    ws.data_ptr(), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return out[0]
+
+
+def loss_smooth1_backward(flo, image, alpha, g_value):
+    """g_value (one element) -> g_flo [B,Cf,H,W]: pdepth_loss_smooth1_backward_f32."""
+    who = "loss_smooth1_backward"
+    (B, Cf, Ci, H, W), flo, image = _smooth1_args(who, flo, image)
+    if g_value.numel() != 1:
+        raise RuntimeError(f"{who}: g_value must have one element, got {list(g_value.shape)}")
+    (g_value,) = _maps(who, g_value=g_value.reshape(1))
+    lib = load()
+    g = torch.empty_like(flo)
+    with _on_device(flo.device):
+        rc = _entry(lib, "pdepth_loss_smooth1_backward_f32")(flo.data_ptr(), image.data_ptr(), g_value.data_ptr(), B, Cf, Ci, H, W,
+                                                             float(alpha), g.data_ptr(), _stream(flo.device))
+    _check(rc, lib)
+    return g
 
 
 # ---- evaluation metrics (ops.depth_metrics) -----------------------------------------------------------------------------------

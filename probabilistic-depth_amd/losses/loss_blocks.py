@@ -105,6 +105,19 @@ def TernaryLoss(im, im_warp, max_distance=1):
     return ops.ternary(im, im_warp, max_distance)
 
 
+def gradient(data):
+    """Forward differences (D_dx [..., W-1], D_dy [..., H-1, :]) of a [B,C,H,W] tensor (loss_blocks.py:204-207); plain slicing."""
+    D_dy = data[:, :, 1:] - data[:, :, :-1]
+    D_dx = data[:, :, :, 1:] - data[:, :, :, :-1]
+    return D_dx, D_dy
+
+
+def smooth_grad_1st(flo, image, alpha):
+    """Edge-aware first-order smoothness of a flow [B,Cf,H,W] under an image [B,Ci,H,W] of the same size (loss_blocks.py:210-220):
+    one HIP pass forward, one backward with respect to flo (ops.smooth_grad_1st); a 0-dim tensor."""
+    return ops.smooth_grad_1st(flo, image, alpha)
+
+
 def rgb_stereo_consistency_loss(src_rgb_img, target_rgb_img, target_depth_map, pose_target2src, intr, viz=False, per_item=False,
                                 occlusion=None, ternary_weight=0.0, ternary_md=1, ssim_weight=0.0, ssim_md=1, fused=False):
     """Photometric error between the target image and the source image warped into it with the target's depth map, over the

@@ -372,6 +372,36 @@ def depth_occlusion(src_depth, Kinv, proj, th=0.2, src_mask=None, want_range=Fal
     return (vis, rng) if want_range else vis
 
 
+def flow_warp(x, flow, pad="border", deterministic=None):
+    """flow_warp of the flow loss and the flow network (utils/warp_utils.py:82-89), one HIP pass: x [B,C,H,W] sampled bilinearly at
+    base grid + flow [B,2,H,W] (channel 0 along x), pad 'border' or 'zeros', with the reference's normalisation (2 v / (W - 1) - 1
+    into grid_sample's align_corners=False).  fp32 device tensors.  A non-finite position gives 0 in both paddings.  Differentiable
+    with respect to x and / or flow (csrc/flow_warp.hip): grad_flow is a per-owner sum, the same bits from call to call; grad_x is a
+    scatter -- float atomics, or with deterministic=True an order-independent integer sum (None follows
+    torch.are_deterministic_algorithms_enabled() at the call)."""
+    if _wants_grad(x, flow):
+        return _FlowWarpFn.apply(x, flow, pad, _deterministic(deterministic))
+    return _native.flow_warp(x, flow, pad)
+
+
+def flow_fb_check(flow12, flow21, scale=0.01, bias=0.5):
+    """Forward-backward check (utils/warp_utils.py:92-99, get_occu_mask_bidirection), one HIP pass: occ [B,1,H,W], 1 where
+    |flow12 + w|^2 > scale (|flow12|^2 + |w|^2) + bias with w = flow21 sampled at base + flow12 (zeros padding).  A mask has no
+    gradient: the flows are detached and the result carries no graph, as the reference's .float() of a comparison."""
+    detached = [t.detach() if isinstance(t, torch.Tensor) else t for t in (flow12, flow21)]
+    return _native.flow_fb_check(detached[0], detached[1], scale, bias)
+
+
+def smooth_grad_1st(flo, image, alpha):
+    """smooth_grad_1st (losses/loss_blocks.py:210-220), one HIP pass and a fixed-order sum: flo [B,Cf,H,W], image [B,Ci,H,W] ->
+    mean(wx |dx flo|) / 4 + mean(wy |dy flo|) / 4, wx = exp(-alpha mean_c |dx image|); a 0-dim tensor, the same bits from call to
+    call.  Differentiable with respect to flo only (a per-owner gather); image is data."""
+    if _wants_grad(flo, image):
+        _refuse_data_grad("smooth_grad_1st", image=image)
+        return _Smooth1Fn.apply(flo, image, float(alpha))
+    return _native.loss_smooth1(flo, image, alpha)
+
+
 def dpv_moments(dpv, d_candi, BV_log=True):
     """(mean, variance) [B,H,W] of the depth distribution of a (log-)DPV (trainer/default_trainer.py:333-336)."""
     return _native.dpv_moments(dpv, d_candi_tensor(d_candi, dpv.device), BV_log)
@@ -713,6 +743,48 @@ class _SmoothFn(torch.autograd.Function):
         if g_value is None or not ctx.needs_input_grad[0]:
             return None, None
         return _native.loss_smooth_backward(*ctx.saved_tensors, g_value), None
+
+
+class _Smooth1Fn(torch.autograd.Function):
+    """smooth_grad_1st under autograd."""
+
+    @staticmethod
+    def forward(ctx, flo, image, alpha):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(flo, image)
+        ctx.alpha = alpha
+        return _native.loss_smooth1(flo, image, alpha)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value):
+        if g_value is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        flo, image = ctx.saved_tensors
+        return _native.loss_smooth1_backward(flo, image, ctx.alpha, g_value), None, None
+
+
+class _FlowWarpFn(torch.autograd.Function):
+    """flow_warp under autograd: the forward is the no-grad kernel call; the backward asks the kernels only for the gradients that
+    are needed."""
+
+    @staticmethod
+    def forward(ctx, x, flow, pad, deterministic):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, flow)
+        ctx.cfg = (pad, deterministic)
+        return _native.flow_warp(x, flow, pad)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        want_x, want_flow = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_out is None or not (want_x or want_flow):
+            return None, None, None, None
+        x, flow = ctx.saved_tensors
+        pad, deterministic = ctx.cfg
+        g_x, g_f = _native.flow_warp_backward(x, flow, g_out, pad, want_x=want_x, want_flow=want_flow, deterministic=deterministic)
+        return g_x, g_f, None, None
 
 
 class _SsimFn(torch.autograd.Function):

@@ -2,8 +2,10 @@
 imports unchanged.
 
 get_corresponding_map and get_occu_mask_backward are the HIP range map of csrc/occlusion.hip (ops.range_map, ops.occlusion_mask):
-an order-independent integer sum, the same bits from call to call.  flow_warp and get_occu_mask_bidirection are plain torch
-compositions around F.grid_sample, as in the reference; they have no HIP kernel here and run wherever their tensors live.
+an order-independent integer sum, the same bits from call to call.  flow_warp and get_occu_mask_bidirection on fp32 device tensors
+(mode='bilinear') are the HIP kernels of csrc/flow_warp.hip (ops.flow_warp with both gradients, ops.flow_fb_check); everything else
+-- CPU tensors, other dtypes, mode='nearest' -- is the plain torch composition around F.grid_sample, as in the reference, and runs
+wherever its tensors live.
 """
 import torch
 import torch.nn.functional as F
@@ -30,9 +32,17 @@ def get_corresponding_map(data):
     return ops.range_map(data)
 
 
+def _on_hip(*tensors):
+    """True where the HIP ops take the call: every tensor fp32 and on a device."""
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
 def flow_warp(x, flow12, pad='border', mode='bilinear'):
-    """x [B,C,H,W] sampled at base grid + flow12 (warp_utils.py:82-89).  A plain torch composition around F.grid_sample with the
-    reference's call (align_corners=False, torch's default, which the reference leaves unsaid): no HIP here."""
+    """x [B,C,H,W] sampled at base grid + flow12 (warp_utils.py:82-89).  fp32 device tensors with mode='bilinear': ops.flow_warp,
+    HIP, differentiable in x and flow12.  Otherwise a plain torch composition around F.grid_sample with the reference's call
+    (align_corners=False, torch's default, which the reference leaves unsaid)."""
+    if mode == 'bilinear' and _on_hip(x, flow12):
+        return ops.flow_warp(x, flow12, pad=pad)
     B, _, H, W = x.shape
     base = mesh_grid(B, H, W).to(device=x.device, dtype=x.dtype)
     return F.grid_sample(x, norm_grid(base + flow12), mode=mode, padding_mode=pad, align_corners=False)
@@ -40,7 +50,9 @@ def flow_warp(x, flow12, pad='border', mode='bilinear'):
 
 def get_occu_mask_bidirection(flow12, flow21, scale=0.01, bias=0.5):
     """Forward-backward check (warp_utils.py:92-99): 1 where |flow12 + warp(flow21)|^2 exceeds scale (|flow12|^2 + |warp(flow21)|^2)
-    + bias.  A plain torch composition over flow_warp: no HIP here."""
+    + bias.  fp32 device tensors: ops.flow_fb_check, one HIP pass; otherwise a plain torch composition over flow_warp."""
+    if _on_hip(flow12, flow21):
+        return ops.flow_fb_check(flow12, flow21, scale=scale, bias=bias)
     back = flow_warp(flow21, flow12, pad='zeros')
     both = flow12 + back
     mag = (flow12 * flow12).sum(1, keepdim=True) + (back * back).sum(1, keepdim=True)
