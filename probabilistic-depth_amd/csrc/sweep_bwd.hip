@@ -12,17 +12,17 @@
 // One workgroup owns a 16 x 16 tile of reference pixels of one batch item and BCC channels (grid z), every view and every
 // plane.  The two outputs are two instantiations, launched one after the other when both are requested
 // (one kernel for both did not fit the scalar register file):
-//   * g_ref is a per-pixel gather kept in registers and written by the thread that owns the pixel (view after view, read back
+//   * g_ref is a per-pixel gather kept in registers (summed in double over the planes of a view) and written by the thread that owns the pixel (view after view, read back
 //     and added in view order): no atomics, bitwise reproducible from call to call;
 //   * g_src is a scatter.  Per view the workgroup first reduces, plane by plane, the bounding box of the in-bounds taps of its
 //     tile (LDS).  Consecutive planes are grouped while the union of their boxes fits BOX_CAP texels; a group's taps are summed
-//     in an LDS image of the box (ds_add_f32), which is then added to g_src with global_atomic_add_f32, row-contiguous (the
+//     in an LDS image of the box, kept in double (ds_add_f64), which is then rounded once and added to g_src with global_atomic_add_f32, row-contiguous (the
 //     lanes of a wave cover consecutive texels of a box row).  A plane whose box alone does not fit (degenerate geometry,
 //     near planes of wide baselines) adds its taps to g_src directly: correct, slower.  The launcher zeroes g_src on the
 //     stream first.  The sums of g_src depend on the order in which the adds arrive: results may differ in the last bits
 //     from call to call.
 // The body of the kernel is sweep_bwd_body.hpp, shared with sweep_bwd_det.hip; here it runs with the policies NoScatter (g_ref) and
-// FloatAtomics (g_src: cells of float, atomicAdd, 8 channels per pass).
+// FloatAtomics (g_src: a double box image, float atomicAdd into g_src, 4 channels per pass).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>

@@ -4,8 +4,9 @@
 // nowhere else, so the contributions of the two g_src paths are the same bit for bit by construction.
 //
 // A policy says what happens to a contribution:
-//   Cell     element of the LDS box image and of the destination in global memory (the image is flushed with atomicAdd(Cell*, Cell));
-//   BCC      channels per pass (grid z): BCC * BOX_CAP cells of LDS;
+//   Cell     element of the destination in global memory;
+//   Stage    element of the LDS box image (the image is flushed with atomicAdd(Cell*, flush(Stage)));
+//   BCC      channels per pass (grid z): BCC * BOX_CAP stage cells of LDS;
 //   SCATTER  whether anything is scattered at all (false: no boxes, no groups, no LDS -- the g_ref gather);
 //   add      one contribution to a cell, of the box image (LDS) or of the destination (global memory).
 #pragma once
@@ -26,28 +27,39 @@ constexpr int BOX_CAP = 2048;     // texels of the LDS box image
 
 struct NoScatter {   // g_ref alone
     using Cell = float;
+    using Stage = float;
     static constexpr int BCC = 8;
     static constexpr bool SCATTER = false;
     __device__ __forceinline__ void add(float*, float) const {}
+    static __device__ __forceinline__ float flush(float v) { return v; }
 };
-struct FloatAtomics {   // ds_add_f32 / global_atomic_add_f32: 8 * 2048 * 4 B = 64 KB
+// The box image of the float path is double: a texel of the image takes every contribution of the group's planes, hundreds of
+// terms at D = 128 and more, and their sum in float32 in the order of arrival was several times further from float64 than the
+// reference's cascade sum.  In double the image is exact to 2^-53 per add; one rounding at the flush, then the
+// few float adds of the groups and tiles that share a texel.
+struct FloatAtomics {   // ds_add_f64 / global_atomic_add_f32: 4 * 2048 * 8 B = 64 KB
     using Cell = float;
-    static constexpr int BCC = 8;
+    using Stage = double;
+    static constexpr int BCC = 4;
     static constexpr bool SCATTER = true;
-    __device__ __forceinline__ void add(float* q, float c) const { atomicAdd(q, c); }
+    __device__ __forceinline__ void add(double* q, float c) const { atomicAdd(q, (double)c); }   // the box image
+    __device__ __forceinline__ void add(float* q, float c) const { atomicAdd(q, c); }            // a direct add
+    static __device__ __forceinline__ float flush(double v) { return (float)v; }
 };
 struct IntegerSum {   // rn(2^S c) with ds_add_u64 / global_atomic_add_x2 (fixed_accum.hpp): 4 * 2048 * 8 B = 64 KB
     using Cell = unsigned long long;
+    using Stage = unsigned long long;
     static constexpr int BCC = 4;   // (8: a 128 KB image, one workgroup per CU -- measured slower)
     static constexpr bool SCATTER = true;
     int S;   // the exponent of the workgroup's batch item
     __device__ __forceinline__ void add(unsigned long long* q, float c) const { fixed::det_add(q, c, S); }
+    static __device__ __forceinline__ unsigned long long flush(unsigned long long v) { return v; }
 };
 
 // dynamic LDS of a launch: [4 waves][D][4] ints of boxes, then the box image
 template <class Policy>
 inline size_t lds_bytes(int D) {
-    return Policy::SCATTER ? (size_t)16 * D * sizeof(int) + (size_t)Policy::BCC * BOX_CAP * sizeof(typename Policy::Cell) : 0;
+    return Policy::SCATTER ? (size_t)16 * D * sizeof(int) + (size_t)Policy::BCC * BOX_CAP * sizeof(typename Policy::Stage) : 0;
 }
 template <class Policy>
 inline dim3 grid(const SweepArgs& a) {
@@ -72,11 +84,12 @@ template <int METRIC, bool GREF, class Policy>
 __device__ __forceinline__ void sweep_bwd_body(const SweepArgs& a, const float* __restrict__ gcost, float* __restrict__ gref,
                                                typename Policy::Cell* __restrict__ dst, const Policy pol) {
     using Cell = typename Policy::Cell;
+    using Stage = typename Policy::Stage;
     constexpr int BCC = Policy::BCC;
     constexpr bool SCATTER = Policy::SCATTER;
     extern __shared__ unsigned long long sweep_bwd_lds[];
     int* box = reinterpret_cast<int*>(sweep_bwd_lds);         // [4 waves][D][4]: x min, x max, y min, y max of the wave's in-bounds taps of plane k
-    Cell* img = reinterpret_cast<Cell*>(sweep_bwd_lds + 8 * a.D);   // [BCC][box area]
+    Stage* img = reinterpret_cast<Stage*>(sweep_bwd_lds + 8 * a.D);   // [BCC][box area]
     const int tid = threadIdx.x;
     const int HW = a.H * a.W;
     const int b = blockIdx.y;
@@ -140,11 +153,12 @@ __device__ __forceinline__ void sweep_bwd_body(const SweepArgs& a, const float* 
 
         {   // this workgroup's BCC channels
             const int c0 = blockIdx.z * BCC;
-            float rf[BCC], gr[BCC];
+            float rf[BCC];
+            double gr[BCC];   // V D terms per pixel, one after another: in double (the float32 sum was noisier than the reference's cascade)
 #pragma unroll
             for (int cc = 0; cc < BCC; ++cc) {
                 rf[cc] = refp[min(c0 + cc, a.C - 1) * hw_v];
-                gr[cc] = 0.0f;
+                gr[cc] = 0.0;
             }
             int k = 0;
             while (k < a.D) {   // groups of planes (workgroup-uniform)
@@ -171,7 +185,7 @@ __device__ __forceinline__ void sweep_bwd_body(const SweepArgs& a, const float* 
                         staged = true;
                         bx0 = ux0; by0 = uy0; bw = ux1 - ux0 + 1; area = bw * (uy1 - uy0 + 1);
                         #pragma unroll 1
-                        for (int i = tid; i < BCC * area; i += BTHREADS) img[i] = Cell(0);
+                        for (int i = tid; i < BCC * area; i += BTHREADS) img[i] = Stage(0);
                         __syncthreads();
                     } else if (!GREF) {
                         k = k1;   // a run of planes without an in-bounds tap: nothing to add (the g_ref gather needs every plane)
@@ -203,12 +217,12 @@ __device__ __forceinline__ void sweep_bwd_body(const SweepArgs& a, const float* 
                         const float e = val - rf[cc];
                         const float r = METRIC == 0 ? coef * e : (e > 0.0f ? coef : (e < 0.0f ? -coef : 0.0f));
                         rr[cc] = c0 + cc < a.C ? r : 0.0f;
-                        gr[cc] = gr[cc] - rr[cc];
+                        gr[cc] = gr[cc] - (double)rr[cc];
                     }
                     if (!SCATTER || !m) continue;   // (no in-bounds tap: nothing to add)
                     // (expect: the direct adds are laid out behind the plane loop, not in the middle of it -- 1 % of the integer scatter)
                     if (__builtin_expect(staged, 1)) {   // (rows of the image past the last channel are never flushed)
-                        Cell* q = img + lo;
+                        Stage* q = img + lo;
 #pragma unroll
                         for (int cc = 0; cc < BCC; ++cc) {
                             if (m & 1u) pol.add(q, f.nw * rr[cc]);
@@ -236,8 +250,8 @@ __device__ __forceinline__ void sweep_bwd_body(const SweepArgs& a, const float* 
                     for (int i = tid; i < nc * area; i += BTHREADS) {
                         const int cc = i / area, rr = i - cc * area;
                         const int ry = rr / bw, rx = rr - ry * bw;
-                        const Cell val = img[i];
-                        if (val != Cell(0)) atomicAdd(dstv + (size_t)(c0 + cc) * HW + (by0 + ry) * a.W + (bx0 + rx), val);
+                        const Stage val = img[i];
+                        if (val != Stage(0)) atomicAdd(dstv + (size_t)(c0 + cc) * HW + (by0 + ry) * a.W + (bx0 + rx), Policy::flush(val));
                     }
                     __syncthreads();   // (the next group zeroes the image)
                 }
@@ -248,7 +262,7 @@ __device__ __forceinline__ void sweep_bwd_body(const SweepArgs& a, const float* 
                 for (int cc = 0; cc < BCC; ++cc) {
                     if (c0 + cc < a.C) {
                         float* o = grefp + (c0 + cc) * hw_v;
-                        *o = v == 0 ? gr[cc] : *o + gr[cc];   // views in order: reproducible
+                        *o = v == 0 ? (float)gr[cc] : *o + (float)gr[cc];   // views in order: reproducible
                     }
                 }
             }

@@ -19,10 +19,11 @@ from pdepth_amd.losses import loss_blocks as lb
 from pdepth_amd.utils import inverse_warp as iv
 import test_loss_terms_gpu as TL
 import test_sweep_backward_groups as G
+import test_sweep_backward_pin_gpu as P
 import test_warps_gpu as TW
 import util_loss_terms as LT
 import util_warps as UW
-from util_sweep_backward import l1_allowance, oracle_grads, rel_err, to_dev
+from util_sweep_backward import l1_allowance, oracle_grads, pin_check, rel_err, to_dev
 
 pytestmark = pytest.mark.gpu
 SIGMA = G.SIGMA
@@ -73,6 +74,14 @@ def _assert_src(tag, gs, gs_atomic, s64, allow):
         assert touched <= 1e-2, touched
 
 
+def _assert_pinned(tag, x, gr, gs, gs_atomic):
+    """The same gradients under the per-element bound of tests/util_sweep_backward.py (float64 at the kernel's own positions; the
+    integer sum with its quantisation term), on the same input: x is the reference of tests/test_sweep_backward_pin_gpu.py."""
+    pin_check(gr, x, "ref", tag + " g_ref")
+    pin_check(gs_atomic, x, "src", tag + " g_src atomic")
+    pin_check(gs, x, "src", tag + " g_src deterministic", det=True)
+
+
 @pytest.mark.parametrize("metric", METRICS)
 @pytest.mark.parametrize("name", NAMES)
 def test_sweep_group_cases_against_float64(dev, name, metric):
@@ -81,6 +90,7 @@ def test_sweep_group_cases_against_float64(dev, name, metric):
     gr, gs = _det(dev, name, metric)
     assert torch.equal(gr, r["gr"])   # g_ref is the gather pass either way
     _assert_src("%s %s" % (name, metric), gs, r["gs"], r["s64"], r["as_"])
+    _assert_pinned("%s %s" % (name, metric), P.reference(name, metric), gr, gs, r["gs"])
 
 
 @pytest.mark.parametrize("metric,V,C,D,pose", [("L2", 2, 67, 64, "stereo"), ("L1", 4, 80, 128, "wide")])
@@ -94,6 +104,7 @@ def test_sweep_ordinary_cases_against_float64(dev, metric, V, C, D, pose):
     gr, gs = det_grads(d, gup, SIGMA, metric)
     assert torch.equal(gr, gr_a) and rel_err(gr, r64, ar) <= TOL
     _assert_src("%s V=%d C=%d D=%d %s" % (metric, V, C, D, pose), gs, gs_a, s64, as_)
+    _assert_pinned("%s V=%d C=%d D=%d %s" % (metric, V, C, D, pose), P.reference("ordinary-%d-%d-%d-%s-0.0" % (V, C, D, pose), metric), gr, gs, gs_a)
 
 
 # ---- sweep: the same bits ----------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """What the compiler made of the backward kernels (no GPU needed: hipcc cross-compiles): csrc/sweep_bwd.hip and
 csrc/dpv_bwd.hip.  Every kernel: no spilled register of either kind, no scratch, no compare-and-swap loop; the float adds of
-the scatter are global_atomic_add_f32 (global memory) and ds_add_f32 (the LDS box image)."""
+the scatter are global_atomic_add_f32 (global memory) and ds_add_f64 (the LDS box image, kept in double: DESIGN.md 6.1.4)."""
 import os
 import re
 import shutil
@@ -50,7 +50,8 @@ def test_scatter_adds_are_float_atomics():
     gather = {n: ops for n, (md, ops) in ks.items() if "ELb1ELb0E" in n}
     assert len(scatter) == 2 and len(gather) == 2, sorted(ks)
     for name, ops in scatter.items():
-        assert "global_atomic_add_f32" in ops and "ds_add_f32" in ops, name
+        assert "global_atomic_add_f32" in ops and "ds_add_f64" in ops, name
+        assert not [o for o in ops if o.startswith("ds_add") and o != "ds_add_f64"], name   # (no returning add, no float32 image)
         assert not [o for o in ops if "atomic" in o and o not in ("global_atomic_add_f32",)], name
     for name, ops in gather.items():   # g_ref: a gather, no atomics at all
         assert not [o for o in ops if "atomic" in o or o.startswith("ds_add")], name

@@ -1,7 +1,32 @@
 """Shared by the suites of the sweep backward (csrc/sweep_bwd.hip): autograd of the oracle's formula in float64 / fp32, the
 HIP gradients, the error measure and its L1 allowance; and a host restatement of how the g_src pass of the kernel groups the
 planes of a (tile, view) pair -- staged through the LDS box image, added directly, or empty -- with the inputs that reach the
-paths the ordinary poses never take (tests/test_sweep_backward_groups.py)."""
+paths the ordinary poses never take (tests/test_sweep_backward_groups.py).
+
+The per-element criterion (tests/test_sweep_backward_host.py, tests/test_sweep_backward_pin_gpu.py).  The reference is
+exact64_grads: float64 arithmetic at the float32 sample positions of oracle.ref_cpu.sample_coords, which the kernel, the
+reference's float32 grid_sample and this module all have bit for bit -- so no tolerance pays for positions an ulp apart, as
+the float64 grid_sample of oracle_cost makes it do.  Per sample (item, view, plane, pixel, channel): g the upstream gradient,
+c = (2 | 1) / |sigma|, w_t the in-bounds taps' weights, s_t their texels, r the reference feature, S = sum_t w_t |s_t|,
+e = sum_t w_t s_t - r.  The contributions are q_t = g c w_t e to g_src at tap t and -g c e to g_ref (L1: sign(e) for e).
+With u = 2^-24, counted on csrc/sweep_bwd_body.hpp and geometry.hpp::make_footprint, first order in u:
+  weights  w = ix - floor(ix) is exact (floor(ix) <= ix < floor(ix) + 1, both on ix's grid or a finer one); 1 - w is one
+           rounding; a weight is the product of two such factors: one rounding more, so a weight carries at most 3 u;
+  value    val = vnw nw, then three fmas: 4 roundings on partial sums bounded by S, so |d val| <= 3 u S + 4 u S = 7 u S;
+           e = val - r is one more rounding: |d e| <= 7 u S + u |e|;
+  factors  gscale = (2 | 1) / sigma, coef = g gscale, r = coef e, q = w r: 4 roundings, the weight's 3 u and the u |e| of the
+           subtraction: 8 u relative to the contribution (g_ref: 5 u; L1, where r = +-coef: 6 u and 2 u) -- 8 u bounds all;
+  sum      n terms added in any order in float32: at most n u sum |q|.  (The kernel does better: g_ref sums a view's planes in
+           double, the float path's box image is double and is rounded once per flush, the integer sum is exact with at most two
+           roundings of the conversion; float32 adds remain between views, groups and tiles, and in torch's own sum.)
+Summed over the samples that reach an element, A0 = sum |g| c w_t |e| (L1: |e| -> 1), A1 = sum |g| c w_t S (L2 only; for g_ref
+w_t = 1 and n = V D), the worst case is u (7 A1 + (8 + n) A0).  The bound is twice that, eps32 (7 A1 + (8 + n) A0), which also
+covers the second-order terms; it is exactly 0 where nothing contributes, and there the gradient must be exactly 0.  No constant
+is fitted.  The integer sum adds its documented quantisation, n N M_b 2^-59 (fixed_accum.hpp, sweep_bwd_det.hip: N = D H W,
+M_b = |gscale| max|g_cost[b]| (max|src[b]| + max|ref[b]|), L1: |gscale| max|g_cost[b]|).
+L1: sign(e) is decided by val, which is off by at most 7 u S (the subtraction val - r never changes a sign).  A sample with
+S > 0 and |e64| <= 7 eps32 S -- twice that -- is ambiguous: it may move g_ref by 2 |g| / |sigma| and g_src by 2 |g| w_t / |sigma| at
+its taps, and the bound adds exactly that.  At most 1 % of the elements of a case may carry such an allowance."""
 import os
 import re
 
@@ -11,6 +36,9 @@ import torch.nn.functional as F
 
 from pdepth_amd import ops, synth
 from oracle import ref_cpu as O
+import util_warps as UW
+
+EPS32 = UW.EPS32
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL = os.path.join(REPO, "probabilistic-depth_amd", "csrc", "sweep_bwd_body.hpp")   # the one body of both g_src paths
@@ -97,6 +125,181 @@ def l1_allowance(b, gup, sigma, dev, tau=1e-5):
             total = total + (w * warped).sum()                              # d/dsrc = the taps' weights times w
     total.backward()
     return allow_ref, src.grad
+
+
+# ---- float64 at the kernel's positions, and the bound an fp32 evaluation is held to, element by element ----------------------
+def case_positions(b):
+    """(ix, iy) float32 [B,V,D,H*W] of oracle.ref_cpu.sample_coords: the positions every fp32 implementation has bit for bit."""
+    B, V, C, H, W = b["src"].shape
+    ix, iy = [], []
+    for i in range(B):
+        K = b["K"][i].cpu()
+        cx, cy = K.numpy()[0, 2], K.numpy()[1, 2]
+        for v in range(V):
+            x, y = O.sample_coords(K, b["R"][i, v].cpu(), b["t"][i, v].cpu(), b["rays"][i].cpu(), b["d_candi"], cx, cy, H, W)
+            ix.append(x)
+            iy.append(y)
+    D = ix[0].shape[0]
+    return torch.stack(ix).reshape(B, V, D, H * W), torch.stack(iy).reshape(B, V, D, H * W)
+
+
+def oracle_positions64(b):
+    """(ix, iy) float64 [B,V,D,H*W]: where a float64 grid_sample puts the samples of oracle_cost -- the float32 grid of
+    oracle.ref_cpu.plane_coords un-normalised in float64, ((g + 1) size - 1) / 2."""
+    B, V, C, H, W = b["src"].shape
+    d32 = torch.from_numpy(np.asarray(b["d_candi"]).astype(np.float32))
+    ix, iy = [], []
+    for i in range(B):
+        K = b["K"][i].cpu()
+        cx, cy = K.numpy()[0, 2], K.numpy()[1, 2]
+        for v in range(V):
+            g = O.plane_coords(K, b["R"][i, v].cpu(), b["t"][i, v].cpu(), b["rays"][i].cpu(), d32, cx, cy).double()
+            ix.append(((g[..., 0] + 1) * W - 1) / 2)
+            iy.append(((g[..., 1] + 1) * H - 1) / 2)
+    return torch.stack(ix).reshape(B, V, -1, H * W), torch.stack(iy).reshape(B, V, -1, H * W)
+
+
+def _tap_list(ix, iy, H, W):
+    """Positions [d,HW] (float32: floor and fraction are taken in float32, where the subtraction is exact; float64: taken as they
+    are) -> the four taps as (inside bool, flat texel index int64, weight float64), each [d,HW].  A tap outside the image or of
+    a position that is not finite is not inside; the weights (1-w)(1-n), w(1-n), (1-w)n, wn are float64 products."""
+    if ix.dtype == torch.float32:
+        fin, x0, y0, w, n = UW._taps(ix, iy, H, W)
+    else:
+        fin = torch.isfinite(ix) & torch.isfinite(iy)
+        x, y = torch.where(fin, ix, torch.zeros_like(ix)), torch.where(fin, iy, torch.zeros_like(iy))
+        xf, yf = torch.floor(x), torch.floor(y)
+        w, n, x0, y0 = x - xf, y - yf, xf.clamp(-2, W + 1).long(), yf.clamp(-2, H + 1).long()
+    out = []
+    for dx, dy, wt in ((0, 0, (1 - w) * (1 - n)), (1, 0, w * (1 - n)), (0, 1, (1 - w) * n), (1, 1, w * n)):
+        xx, yy = x0 + dx, y0 + dy
+        inside = fin & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+        out.append((inside, yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1), wt))
+    return out
+
+
+def _gather64(s2, taps):
+    """s2 [C,HW] float64, taps of _tap_list -> [C,d,HW]: the zeros-padded bilinear value (util_warps.bilinear64's sum), differentiable in s2."""
+    C = s2.shape[0]
+    out = 0
+    for inside, idx, wt in taps:
+        val = s2[:, idx.reshape(-1)].reshape(C, *idx.shape)
+        out = out + torch.where(inside.unsqueeze(0), val * wt.unsqueeze(0), torch.zeros((), dtype=s2.dtype, device=s2.device))
+    return out
+
+
+def exact64_grads(b, gup, sigma, metric, dev="cpu", positions=None, block=1 << 25):
+    """The float64 reference of the sweep backward AT THE float32 SAMPLE POSITIONS (case_positions; `positions` replaces them, float32
+    or float64 [B,V,D,HW]), and per element the quantities of the bound of this module's criterion (pin_bound).
+
+    ref and src are float64 leaves; each view is gathered with the sum of util_warps.bilinear64 (taps outside the image and
+    positions that are not finite count as zero), the cost is the reference's sum_v dist / sigma, and (cost * gup).sum() is
+    differentiated by autograd.  The work goes view by view and, where a view's [C,D,HW] block exceeds `block` elements, by runs
+    of planes.  Per sample (item, view, plane, pixel, channel): c = (2 | 1) / |sigma|, w_t the in-bounds taps' weights,
+    S = sum_t w_t |s_t|, e = sum_t w_t s_t - r.  Summed over the samples that reach an element (autograd of the gather with these
+    as upstream gradients for src, plain sums with w_t = 1 for ref):
+        A0 = sum |g| c w_t |e|   (L1: |e| -> 1),      A1 = sum |g| c w_t S   (L2 only),      n = the in-bounds contributions
+    (ref: n = V D), and for L1 the allowance: a sample with S > 0 and |e| <= 7 eps32 S may take another branch of sign() in fp32
+    and moves g_ref by up to 2 |g| / |sigma| and g_src by 2 |g| w_t / |sigma| at its taps.
+    -> dict of float64 tensors on `dev`: g_ref, g_src; A0_ref, A1_ref, n_ref, allow_ref [B,C,H,W]; A0_src, A1_src, allow_src
+    [B,V,C,H,W], n_src [B,V,1,H,W]; Mb [B] (the bound M_b of csrc/sweep_bwd_det.hip on a contribution) and N = D H W."""
+    dt = torch.float64
+    L2 = metric == "L2"
+    ref = b["ref"].to(dev, dt).detach().clone().requires_grad_(True)
+    src = b["src"].to(dev, dt).detach().clone().requires_grad_(True)
+    B, V, C, H, W = src.shape
+    HW = H * W
+    ix, iy = case_positions(b) if positions is None else positions
+    ix, iy = ix.to(dev), iy.to(dev)
+    D = ix.shape[2]
+    g = gup.to(dev, dt).reshape(B, D, HW)
+    c = (2.0 if L2 else 1.0) / abs(float(sigma))
+    q = {k: torch.zeros(B, C, HW, dtype=dt, device=dev) for k in ("A0_ref", "A1_ref", "allow_ref")}
+    q.update({k: torch.zeros_like(src) for k in ("A0_src", "A1_src", "allow_src")})
+    q["n_src"] = torch.zeros(B, V, 1, HW, dtype=dt, device=dev)
+    step = max(1, min(D, block // (C * HW)))
+    for i in range(B):
+        rf = ref[i].reshape(C, 1, HW)
+        for v in range(V):
+            for k0 in range(0, D, step):
+                taps = _tap_list(ix[i, v, k0:k0 + step], iy[i, v, k0:k0 + step], H, W)
+                for inside, idx, _ in taps:
+                    q["n_src"][i, v, 0].index_add_(0, idx.reshape(-1), inside.reshape(-1).to(dt))
+                val = _gather64(src[i, v].reshape(C, HW), taps)                       # [C,d,HW]
+                gk = g[i, k0:k0 + step]
+                with torch.no_grad():
+                    S = _gather64(src[i, v].detach().abs().reshape(C, HW), taps)
+                    e = val.detach() - rf.detach()
+                    ga = (gk.abs() * c).unsqueeze(0)                                       # |g| c  [1,d,HW]
+                    ups = {"A0": ga * e.abs() if L2 else ga.expand_as(e)}
+                    if L2:
+                        ups["A1"] = ga * S
+                    else:
+                        ups["allow"] = ((S > 0) & (e.abs() <= 7 * EPS32 * S)).to(dt) * (2 * ga)
+                    for k, up in ups.items():
+                        q[k + "_ref"][i] += up.sum(1)
+                for k, up in ups.items():
+                    q[k + "_src"] += torch.autograd.grad(val, src, up.contiguous(), retain_graph=True)[0]
+                diff = val - rf
+                dist = (diff ** 2).sum(0) if L2 else diff.abs().sum(0)
+                ((dist / sigma) * gk).sum().backward()
+    out = {k: (t if t.shape == src.shape else t.reshape(t.shape[:-1] + (H, W))) for k, t in q.items()}
+    out.update(g_ref=ref.grad, g_src=src.grad, n_ref=torch.full_like(out["A0_ref"], float(V * D)), N=D * HW)
+    gscale = abs(float(np.float32(2.0 if L2 else 1.0) / np.float32(sigma)))
+    E = b["src"].abs().amax(dim=(1, 2, 3, 4)).double() + b["ref"].abs().amax(dim=(1, 2, 3)).double() if L2 else torch.ones(B, dtype=dt)
+    out["Mb"] = (gscale * gup.abs().reshape(B, -1).amax(1).double().cpu() * E.cpu()).to(dev)
+    return out
+
+
+def pin_bound(x, which, det=False):
+    """The bound of |g32 - g64| per element of g_ref / g_src (`which` = 'ref' | 'src') from the dict of exact64_grads:
+    eps32 (7 A1 + (8 + n) A0) + the L1 allowance; det: + the quantisation term of the integer sum, n N M_b 2^-59 (g_src only).
+    Exactly 0 where nothing contributes (A0 == A1 == 0 and no allowance)."""
+    A0, A1, n, allow = (x[k + "_" + which] for k in ("A0", "A1", "n", "allow"))
+    bound = EPS32 * (7 * A1 + (8 + n) * A0) + allow
+    if det:
+        assert which == "src"
+        quant = n * (x["N"] * 2.0 ** -59) * x["Mb"].reshape(-1, 1, 1, 1, 1)
+        bound = torch.where(bound > 0, bound + quant, bound)   # (no contribution, or only zeros: the integer sum is exactly 0 too)
+    return bound
+
+
+def pin_check(got, x, which, what, det=False, bound=None, want=None):
+    """Every element of `got` within the bound of the float64 reference, exactly 0 where the bound is 0 (a texel no tap reaches
+    among them).  Prints and returns the worst error / bound."""
+    want = x["g_" + which] if want is None else want
+    bound = pin_bound(x, which, det) if bound is None else bound
+    got = got.detach().to(want.device, torch.float64)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    assert bool(torch.isfinite(got).all()), what
+    zero = bound == 0
+    assert bool((got[zero] == 0).all()), "%s: an element nothing contributes to is not exactly 0" % what
+    err = (got - want).abs()
+    ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
+    note = ""
+    if bool((x["allow_" + which] > 0).any()):   # L1: an element with an allowance may sit at a whole sign flip; the others for the record
+        plain = ~zero & (x["allow_" + which] == 0)
+        note = " (%.4f over the elements without an L1 allowance)" % float((err[plain] / bound[plain]).max())
+    print("%s: worst error / bound = %.4f%s; max error %.3e of max |g64| %.3e; %d of %d elements exactly 0"
+          % (what, ratio, note, float(err.max()), float(want.abs().max()), int(zero.sum()), zero.numel()))
+    bad = err > bound
+    if bool(bad.any()):
+        at = torch.nonzero(bad)[0].tolist()
+        raise AssertionError("%s: %d elements outside the bound, worst error / bound = %.4f, first at %s" % (what, int(bad.sum()), ratio, at))
+    return ratio
+
+
+def allowance_share(x):
+    """(share of g_ref's, of g_src's elements that carry a non-zero L1 allowance)."""
+    return tuple(float((x["allow_" + w] > 0).double().mean()) for w in ("ref", "src"))
+
+
+def max_err(g, x, which):
+    """max over the elements of (|g - g64| - the L1 allowance)+ : the figure of the project's max-norm rule
+    max|g - g64| <= 2 E_ref + eps32 max|g64|, E_ref the same figure of the CPU fp32 autograd of oracle_cost."""
+    want = x["g_" + which]
+    d = (g.detach().to(want.device, torch.float64) - want).abs() - x["allow_" + which]
+    return float(d.clamp_min(0).max())
 
 
 # ---- the plane groups of the g_src pass, restated on the host ------------------------------------------------------------
@@ -211,7 +414,7 @@ def describe(groups):
     return ", ".join(one(g) for g in groups)
 
 
-def group_stats(tg, C, channels_per_pass=8):
+def group_stats(tg, C, channels_per_pass=4):
     """The counts that the coverage test holds the cases to."""
     kinds = {key: [g[0] for g in gs] for key, gs in tg.items()}
     follows = sum(1 for ks in kinds.values() for a, b_ in zip(ks, ks[1:]) if a == "empty" and b_ in ("direct", "staged"))
