@@ -68,7 +68,8 @@ extern "C" {
                                 *    pdepth_ternary_f32, pdepth_ternary_backward_f32;
                                 *    pdepth_range_map_workspace_bytes, pdepth_range_map_f32, pdepth_depth_range_map_f32;
                                 *    pdepth_flow_warp_f32, pdepth_flow_warp_backward_f32, pdepth_flow_warp_backward_det_f32 and its
-                                *    _det_workspace_bytes, pdepth_flow_fb_check_f32; pdepth_loss_smooth1_f32 and its _backward_f32 */
+                                *    _det_workspace_bytes, pdepth_flow_fb_check_f32; pdepth_loss_smooth1_f32 and its _backward_f32;
+                                *    pdepth_flow_cost_volume_f32, its _backward_f32 and _backward_det_f32 and their workspace queries */
 
 enum {
     PDEPTH_OK = 0,
@@ -909,6 +910,49 @@ int pdepth_loss_smooth1_f32(const float *flo, const float *image, int32_t B, int
                             float alpha, float *value, void *workspace, size_t workspace_bytes, void *stream);
 int pdepth_loss_smooth1_backward_f32(const float *flo, const float *image, const float *g_value, int32_t B, int32_t Cf, int32_t Ci,
                                      int32_t H, int32_t W, float alpha, float *g_flo, void *stream);
+
+/*
+ * The per-level cost volume of the flow network (csrc/cost_volume.hip; models/pwclite.py: flow_warp, the correlation, LeakyReLU)
+ * in one pass:
+ *     out = leaky_relu(correlation(x1, flow_warp(x2, flow, pad)), negative_slope)          [B, (2 md + 1)^2, H, W],  md = max_displacement
+ * x1, x2 [B,C,H,W], flow [B,2,H,W] or NULL (no warp: the network's coarsest level; still one launch), fp32.  The correlation is the
+ * configuration the reference instantiates: kernel 1, both strides 1, pad_size = max_displacement,
+ *     out[b, (tj + md)(2 md + 1) + (ti + md), y, x] = (1 / C) sum_c x1[b,c,y,x] w[b,c,y+tj,x+ti]     (tj the row displacement)
+ * with w the warped x2 and zeros outside the image.  A warped texel is the chain of the flow entries above
+ * (csrc/flow_warp_sample.hpp: the position formed in double; a non-finite position gives 0 in both paddings).  The sum runs over c
+ * in ascending order in fp32 (blocks of 8 channels: a block's sum by one fma per channel, the blocks' sums added in turn), then
+ * times 1 / C, then x > 0 ? x : x negative_slope.  The zeros of the correlation's
+ * padding are multiplied, not skipped: 0 x inf gives NaN, as in pdepth_correlation_forward_f32.  Neither the warped image nor the
+ * pre-activation volume reaches global memory.
+ *
+ *   pdepth_flow_cost_volume_f32               out.  One launch.
+ *   pdepth_flow_cost_volume_backward_f32      grad_x1 [B,C,H,W], grad_x2 [B,C,H,W], grad_flow [B,2,H,W]; any may be NULL, not all three
+ *       (grad_flow must be NULL without a flow).  `out` is the forward's saved result: the activation's factor is
+ *       out > 0 ? 1 : negative_slope (0, -0 and NaN take the slope); no pre-activation is kept.  Launch 1 gathers, without atomics,
+ *       grad_x1 and the gradient of the warped image into the workspace; launch 2 is pdepth_flow_warp_backward_f32's own work on that
+ *       gradient: grad_x2 by float atomics (zeroed by the call on the stream), grad_flow per owner.  Without a flow the gradient of
+ *       the "warped" image is grad_x2 itself: one launch, no workspace.
+ *   pdepth_flow_cost_volume_backward_det_f32  grad_x2 by the order-independent sum of pdepth_flow_warp_backward_det_f32 (the fifth
+ *       case of "Deterministic backward" above); everything else has the bits of the entry without _det.
+ * Workspace with a flow (256-byte aligned; needed when grad_x2 or grad_flow is requested): roundup256(4 B C H W) bytes; _det, when
+ * grad_x2 is requested: that plus the bytes of pdepth_flow_warp_backward_det_workspace_bytes(B, C, H, W).  The queries take
+ * with_flow (0: no flow, no workspace) and return 0 for sizes out of range.  Missing, too small or misaligned: PDEPTH_E_WORKSPACE.
+ * max_displacement in 1..4; H, W >= 2 with a flow (>= 1 without); H * W <= 2^30, H <= 16 * 65535, B * ceil(C / 8) <= 65535; pad as
+ * the flow entries; a NaN or negative negative_slope, a null pointer, no gradient requested: PDEPTH_E_ARG, before any launch.
+ * Nothing is allocated, nothing waits for the host.
+ */
+int pdepth_flow_cost_volume_f32(const float *x1, const float *x2, const float *flow, int32_t B, int32_t C, int32_t H, int32_t W,
+                                int32_t max_displacement, float negative_slope, int32_t pad, float *out, void *stream);
+size_t pdepth_flow_cost_volume_backward_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t with_flow);
+int pdepth_flow_cost_volume_backward_f32(const float *x1, const float *x2, const float *flow, const float *out, const float *grad_out,
+                                         int32_t B, int32_t C, int32_t H, int32_t W, int32_t max_displacement, float negative_slope,
+                                         int32_t pad, float *grad_x1, float *grad_x2, float *grad_flow, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+size_t pdepth_flow_cost_volume_backward_det_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t with_flow);
+int pdepth_flow_cost_volume_backward_det_f32(const float *x1, const float *x2, const float *flow, const float *out,
+                                             const float *grad_out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t max_displacement,
+                                             float negative_slope, int32_t pad, float *grad_x1, float *grad_x2, float *grad_flow,
+                                             void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,11 @@ _SIGNATURES = {
     "pdepth_flow_fb_check_f32": (c_int, [_P] * 2 + [_I] * 3 + [_F] * 2 + [_P] * 2),
     "pdepth_loss_smooth1_f32": (c_int, [_P] * 2 + [_I] * 5 + [_F] + [_P] * 2 + [_Z, _P]),
     "pdepth_loss_smooth1_backward_f32": (c_int, [_P] * 3 + [_I] * 5 + [_F] + [_P] * 2),
+    "pdepth_flow_cost_volume_f32": (c_int, [_P] * 3 + [_I] * 5 + [_F, _I] + [_P] * 2),
+    "pdepth_flow_cost_volume_backward_workspace_bytes": (_Z, [_I] * 5),
+    "pdepth_flow_cost_volume_backward_f32": (c_int, [_P] * 5 + [_I] * 5 + [_F, _I] + [_P] * 4 + [_Z, _P]),
+    "pdepth_flow_cost_volume_backward_det_workspace_bytes": (_Z, [_I] * 5),
+    "pdepth_flow_cost_volume_backward_det_f32": (c_int, [_P] * 5 + [_I] * 5 + [_F, _I] + [_P] * 4 + [_Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM, census and range-map entries live in objects of their own: part of an entry's name -> the source file.  The
@@ -123,7 +128,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_loss_smooth1_": "csrc/loss_smooth1.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
                     "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip", "_ternary_": "csrc/ternary.hip",
-                    "_range_map_": "csrc/occlusion.hip", "_flow_": "csrc/flow_warp.hip",
+                    "_range_map_": "csrc/occlusion.hip", "_flow_cost_volume_": "csrc/cost_volume.hip", "_flow_": "csrc/flow_warp.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -1585,6 +1590,76 @@ def flow_fb_check(flow12, flow21, scale=0.01, bias=0.5):
                                                      occ.data_ptr(), _stream(flow12.device))
     _check(rc, lib)
     return occ
+
+
+def _cost_volume_args(who, x1, x2, flow, max_displacement, negative_slope, pad):
+    """((B, C, H, W), x1, x2, flow | None, md, slope, pad code) of a cost-volume call: x1, x2 [B,C,H,W] and flow [B,2,H,W] or None,
+    contiguous fp32 device tensors.  Shapes and scalars are judged first, where the tensors live; the device last."""
+    if pad not in FLOW_PADS:
+        raise RuntimeError(f"{who}: pad must be 'border' or 'zeros', got {pad!r}")
+    md, slope = int(max_displacement), float(negative_slope)
+    if md != max_displacement or not 1 <= md <= 4:
+        raise RuntimeError(f"{who}: max_displacement must be 1..4, got {max_displacement!r}")
+    if not slope >= 0.0:
+        raise RuntimeError(f"{who}: negative_slope is NaN or negative ({negative_slope!r})")
+    named = {"x1": x1, "x2": x2} if flow is None else {"x1": x1, "x2": x2, "flow": flow}
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+    if x1.dim() != 4 or min(x1.shape) < 1:
+        raise RuntimeError(f"{who}: x1 must be [B,C,H,W] with every size >= 1, got {list(x1.shape)}")
+    B, C, H, W = x1.shape
+    _shape(x2, (B, C, H, W), "x2", who)
+    if flow is not None:
+        if H < 2 or W < 2:
+            raise RuntimeError(f"{who}: H={H}, W={W}: the grid is normalised by H - 1 and W - 1, both must be at least 2 with a flow")
+        _shape(flow, (B, 2, H, W), "flow", who)
+    t = _fp32_maps(who, **named)
+    return (B, C, H, W), t[0], t[1], (t[2] if flow is not None else None), md, slope, FLOW_PADS[pad]
+
+
+def flow_cost_volume(x1, x2, flow=None, max_displacement=4, negative_slope=0.1, pad="border"):
+    """leaky_relu(correlation(x1, flow_warp(x2, flow, pad))) -> [B, (2 md + 1)^2, H, W]: pdepth_flow_cost_volume_f32 on the current
+    stream, one launch; flow None: no warp."""
+    who = "flow_cost_volume"
+    _no_autograd(who, x1, x2, flow)
+    (B, C, H, W), x1, x2, flow, md, slope, code = _cost_volume_args(who, x1, x2, flow, max_displacement, negative_slope, pad)
+    lib = load()
+    out = torch.empty((B, (2 * md + 1) ** 2, H, W), dtype=torch.float32, device=x1.device)
+    with _on_device(x1.device):
+        rc = _entry(lib, "pdepth_flow_cost_volume_f32")(x1.data_ptr(), x2.data_ptr(), _ptr(flow), B, C, H, W, md, slope, code,
+                                                        out.data_ptr(), _stream(x1.device))
+    _check(rc, lib)
+    return out
+
+
+def flow_cost_volume_backward(x1, x2, flow, out, grad_out, max_displacement=4, negative_slope=0.1, pad="border", want_x1=True,
+                              want_x2=True, want_flow=True, deterministic=False):
+    """-> (grad_x1 | None, grad_x2 | None, grad_flow | None): pdepth_flow_cost_volume_backward_f32; deterministic:
+    pdepth_flow_cost_volume_backward_det_f32 (grad_x2 as an order-independent sum; the others have the same bits either way).
+    `out` is the forward's result.  The workspace (the gradient of the warped image, and the integer accumulator) is allocated here."""
+    who = "flow_cost_volume_backward"
+    (B, C, H, W), x1, x2, flow, md, slope, code = _cost_volume_args(who, x1, x2, flow, max_displacement, negative_slope, pad)
+    nd2 = (2 * md + 1) ** 2
+    _shape(out, (B, nd2, H, W), "out", who)
+    _shape(grad_out, (B, nd2, H, W), "grad_out", who)
+    out, grad_out = _fp32_maps(who, out=out, grad_out=grad_out)
+    want_flow = bool(want_flow) and flow is not None
+    if not (want_x1 or want_x2 or want_flow):
+        raise RuntimeError(f"{who}: no gradient requested")
+    lib = load()
+    dev = x1.device
+    g1 = torch.empty_like(x1) if want_x1 else None
+    g2 = torch.empty_like(x2) if want_x2 else None
+    gf = torch.empty_like(flow) if want_flow else None
+    name = "pdepth_flow_cost_volume_backward_det" if deterministic else "pdepth_flow_cost_volume_backward"
+    with _on_device(dev):
+        need = flow is not None and (want_x2 or want_flow)
+        ws, ws_bytes = _det_workspace(_entry(lib, name + "_workspace_bytes")(B, C, H, W, 1) if need else 0, dev)
+        rc = _entry(lib, name + "_f32")(x1.data_ptr(), x2.data_ptr(), _ptr(flow), out.data_ptr(), grad_out.data_ptr(), B, C, H, W, md, slope,
+                                        code, _ptr(g1), _ptr(g2), _ptr(gf), _ptr(ws), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return g1, g2, gf
 
 
 def _smooth1_args(who, flo, image):

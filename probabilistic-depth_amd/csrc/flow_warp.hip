@@ -21,6 +21,7 @@
 
 #include "capi_util.hpp"
 #include "fixed_accum.hpp"
+#include "flow_warp_launch.hpp"
 #include "flow_warp_sample.hpp"
 
 namespace pdepth {
@@ -147,7 +148,15 @@ __global__ __launch_bounds__(256) void flow_fb_check_kernel(const float* __restr
     occ[(size_t)b * HW + pix] = (sx * sx + sy * sy) > scale * mag + bias ? 1.0f : 0.0f;
 }
 
-// what the warp entries ask of their sizes and of `pad` alike
+void launch_grad_flow(const float* x, const float* flo, const float* gout, int B, int C, int H, int W, int pad, float* gflow, hipStream_t s) {
+    hipLaunchKernelGGL(flow_warp_grad_flow_kernel, grid_of(B, H, W, 1), dim3(256), 0, s, x, flo, gout, C, flow::geometry(H, W), pad, gflow);
+}
+
+}  // namespace
+
+// ---- the host side of the backward (flow_warp_launch.hpp): the entries below and those of cost_volume.hip ---------------------------
+namespace flow {
+
 int check_flow_warp(const char* who, int32_t B, int32_t C, int32_t H, int32_t W, int32_t pad) {
     if (int rc = capi::check_dims(who, B, C, H, W)) return rc;
     if (H < 2 || W < 2) return capi::fail(PDEPTH_E_ARG, "%s: H and W must be at least 2 (the grid is normalised by H - 1 and W - 1)", who);
@@ -155,17 +164,42 @@ int check_flow_warp(const char* who, int32_t B, int32_t C, int32_t H, int32_t W,
     return capi::check_launch_limits(who, B, H, W);
 }
 
-void launch_grad_flow(const float* x, const float* flo, const float* gout, int B, int C, int H, int W, int pad, float* gflow, hipStream_t s) {
-    hipLaunchKernelGGL(flow_warp_grad_flow_kernel, grid_of(B, H, W, 1), dim3(256), 0, s, x, flo, gout, C, flow::geometry(H, W), pad, gflow);
+hipError_t launch_warp_backward(const float* x, const float* flo, const float* gout, int B, int C, int H, int W, int pad, float* gx,
+                                float* gflow, hipStream_t s) {
+    if (gflow) launch_grad_flow(x, flo, gout, B, C, H, W, pad, gflow, s);
+    if (gx) {
+        if (hipError_t e = hipMemsetAsync(gx, 0, (size_t)B * C * H * W * sizeof(float), s)) return e;
+        hipLaunchKernelGGL(flow_warp_bwd_kernel, grid_of(B, H, W, channel_chunks(B, C, H, W)), dim3(256), 0, s, flo, gout, C,
+                           flow::geometry(H, W), pad, gx);
+    }
+    return hipGetLastError();
 }
 
-}  // namespace
+size_t warp_backward_det_workspace_bytes(int B, int C, int H, int W) { return workspace_bytes(B, (size_t)C * H * W); }
+
+hipError_t launch_warp_backward_det(const float* x, const float* flo, const float* gout, int B, int C, int H, int W, int pad, float* gx,
+                                    float* gflow, void* workspace, hipStream_t s) {
+    if (gflow) {   // written per owner: the kernel of the atomic entry, nothing scattered
+        launch_grad_flow(x, flo, gout, B, C, H, W, pad, gflow, s);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (!gx) return hipSuccess;
+    const dim3 grid = grid_of(B, H, W, channel_chunks(B, C, H, W));
+    auto launch = [&](auto pass, uint32_t* hdr, unsigned long long* acc) {
+        hipLaunchKernelGGL(flow_warp_bwd_det_kernel<decltype(pass)::value>, grid, dim3(256), 0, s, flo, gout, C, flow::geometry(H, W), pad,
+                           hdr, acc);
+    };
+    return max_exponent_scatter(workspace, B, (size_t)C * H * W, max_contributions(H, W), gx, s, launch);
+}
+
+}  // namespace flow
 
 }  // namespace pdepth
 
 // ---- C ABI (include/pdepth.h), beside the kernels like the entries of occlusion.hip -------------------------------------------------
 using namespace pdepth;
 using namespace pdepth::capi;
+using pdepth::flow::check_flow_warp;
 
 extern "C" {
 
@@ -185,14 +219,7 @@ int pdepth_flow_warp_backward_f32(const float* x, const float* flow, const float
     if (!x || !flow || !grad_out) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     if (!grad_x && !grad_flow) return fail(PDEPTH_E_ARG, "%s: no gradient requested", who);
     if (int rc = check_flow_warp(who, B, C, H, W, pad)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (grad_flow) launch_grad_flow(x, flow, grad_out, B, C, H, W, pad, grad_flow, s);
-    if (grad_x) {
-        if (int rc = launched(hipMemsetAsync(grad_x, 0, (size_t)B * C * H * W * sizeof(float), s), who)) return rc;
-        hipLaunchKernelGGL(flow_warp_bwd_kernel, grid_of(B, H, W, channel_chunks(B, C, H, W)), dim3(256), 0, s, flow, grad_out, C,
-                           flow::geometry(H, W), pad, grad_x);
-    }
-    return launched(hipGetLastError(), who);
+    return launched(flow::launch_warp_backward(x, flow, grad_out, B, C, H, W, pad, grad_x, grad_flow, (hipStream_t)stream), who);
 }
 
 size_t pdepth_flow_warp_backward_det_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
@@ -206,24 +233,12 @@ int pdepth_flow_warp_backward_det_f32(const float* x, const float* flow, const f
     if (!x || !flow || !grad_out) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     if (!grad_x && !grad_flow) return fail(PDEPTH_E_ARG, "%s: no gradient requested", who);
     if (int rc = check_flow_warp(who, B, C, H, W, pad)) return rc;
-    const size_t per_item = (size_t)C * H * W;
     if (grad_x) {
-        if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, per_item),
+        if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, (size_t)C * H * W),
                                      "; query pdepth_flow_warp_backward_det_workspace_bytes()"))
             return rc;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (grad_flow) {   // written per owner: the kernel of the atomic entry, nothing scattered
-        launch_grad_flow(x, flow, grad_out, B, C, H, W, pad, grad_flow, s);
-        if (int rc = launched(hipGetLastError(), who)) return rc;
-    }
-    if (!grad_x) return PDEPTH_OK;
-    const dim3 grid = grid_of(B, H, W, channel_chunks(B, C, H, W));
-    auto launch = [&](auto pass, uint32_t* hdr, unsigned long long* acc) {
-        hipLaunchKernelGGL(flow_warp_bwd_det_kernel<decltype(pass)::value>, grid, dim3(256), 0, s, flow, grad_out, C, flow::geometry(H, W), pad,
-                           hdr, acc);
-    };
-    return launched(max_exponent_scatter(workspace, B, per_item, max_contributions(H, W), grad_x, s, launch), who);
+    return launched(flow::launch_warp_backward_det(x, flow, grad_out, B, C, H, W, pad, grad_x, grad_flow, workspace, (hipStream_t)stream), who);
 }
 
 int pdepth_flow_fb_check_f32(const float* flow12, const float* flow21, int32_t B, int32_t H, int32_t W, float scale, float bias,

@@ -384,6 +384,19 @@ def flow_warp(x, flow, pad="border", deterministic=None):
     return _native.flow_warp(x, flow, pad)
 
 
+def flow_cost_volume(x1, x2, flow=None, max_displacement=4, negative_slope=0.1, pad="border", deterministic=None):
+    """The flow network's per-level cost volume (models/pwclite.py), one HIP pass: leaky_relu(correlation(x1, flow_warp(x2, flow,
+    pad)), negative_slope) -> [B, (2 md + 1)^2, H, W], the correlation with kernel 1, strides 1 and pad_size = max_displacement
+    (1..4); flow None: no warp (the coarsest level).  fp32 device tensors, the dtype policy of flow_warp.  Neither the warped image
+    nor the pre-activation volume is written (csrc/cost_volume.hip).  Differentiable with respect to x1, x2 and the flow: a gather
+    for grad_x1 and the gradient of the warped image, then flow_warp's own backward -- grad_x2 a scatter (float atomics, or with
+    deterministic=True the order-independent integer sum; None follows torch.are_deterministic_algorithms_enabled() at the call),
+    grad_flow a per-owner sum."""
+    if _wants_grad(x1, x2, flow):
+        return _FlowCostVolumeFn.apply(x1, x2, flow, max_displacement, negative_slope, pad, _deterministic(deterministic))
+    return _native.flow_cost_volume(x1, x2, flow, max_displacement, negative_slope, pad)
+
+
 def flow_fb_check(flow12, flow21, scale=0.01, bias=0.5):
     """Forward-backward check (utils/warp_utils.py:92-99, get_occu_mask_bidirection), one HIP pass: occ [B,1,H,W], 1 where
     |flow12 + w|^2 > scale (|flow12|^2 + |w|^2) + bias with w = flow21 sampled at base + flow12 (zeros padding).  A mask has no
@@ -785,6 +798,33 @@ class _FlowWarpFn(torch.autograd.Function):
         pad, deterministic = ctx.cfg
         g_x, g_f = _native.flow_warp_backward(x, flow, g_out, pad, want_x=want_x, want_flow=want_flow, deterministic=deterministic)
         return g_x, g_f, None, None
+
+
+class _FlowCostVolumeFn(torch.autograd.Function):
+    """flow_cost_volume under autograd: the forward is the no-grad kernel call and saves its own result (the activation's factor is
+    read from it); the backward asks the kernels only for the gradients that are needed."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, flow, max_displacement, negative_slope, pad, deterministic):
+        ctx.set_materialize_grads(False)
+        out = _native.flow_cost_volume(x1, x2, flow, max_displacement, negative_slope, pad)
+        ctx.has_flow = flow is not None
+        ctx.save_for_backward(*((x1, x2, flow, out) if ctx.has_flow else (x1, x2, out)))
+        ctx.cfg = (max_displacement, negative_slope, pad, deterministic)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        want1, want2, wantf = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_flow and ctx.needs_input_grad[2]
+        if g_out is None or not (want1 or want2 or wantf):
+            return (None,) * 7
+        saved = ctx.saved_tensors
+        x1, x2, flow, out = saved if ctx.has_flow else (saved[0], saved[1], None, saved[2])
+        md, slope, pad, deterministic = ctx.cfg
+        g1, g2, gf = _native.flow_cost_volume_backward(x1, x2, flow, out, g_out, md, slope, pad, want_x1=want1, want_x2=want2,
+                                                       want_flow=wantf, deterministic=deterministic)
+        return g1, g2, gf, None, None, None, None
 
 
 class _SsimFn(torch.autograd.Function):
