@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
             // hoists every lane-derived invariant of the phases to the top of the kernel)
             const int tid = opaque_v((int)threadIdx.x), lane = tid & 63;   // (shadow the kernel's: re-derived per trip)
             const int n = lane & 15, kq = lane >> 4, tq = wave * 4 + kq;
-            const int a32 = (lane ^ 32) << 2;   // (bperm_f: the lane of pixel n two K slices on)
+            const int a32 = DIST_LANE_XCHG == 0 ? (lane ^ 32) << 2 : 0;   // (quad_sum / quad_max by the LDS pipe: the lane of pixel n two K slices on)
             const int HW = H * W;
             int p;
             bool xlive;
@@ -628,8 +628,9 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             }
                         }
                         pr = 0.25f * pr;
-                        pr = pr + xor16_f(pr); pr = pr + bperm_f(a32, pr);
-                        pz = pz + xor16_f(pz); pz = pz + bperm_f(a32, pz);
+                        // (over the pixel's four K-slice lanes: wave_util.hpp)
+                        pr = quad_sum<DIST_LANE_XCHG>(pr, a32);
+                        pz = quad_sum<DIST_LANE_XCHG>(pz, a32);
                         if (kq == 0) *reinterpret_cast<v2f*>(&L.rp[(wave * 16 + n) * 2]) = v2f{pr, pz};
                     }
                     // ---- row table: the texels this thread's planes touch ---------------------------------------------------------
@@ -658,7 +659,35 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                             ylo = min(ylo, vj ? yj : 32767);
                             yhi = max(yhi, yj);
                         }
-                        if (open) {
+                        if (DIST_ROWTAB_FOLD) {
+                            // The last run (the only one on a rectified pair).  Where the eight lanes of half a DPP row -- a pixel
+                            // row's share of an 8 x 2 block, half of a 16 x 1 block's -- end on ONE row, their runs are folded with
+                            // DPP first and the group's first lane issues the two atomics for all eight: the same table (min and
+                            // max of integers, in any order), an eighth of the same-address lanes for the LDS pipe to serve one by
+                            // one.  A group whose lanes end on different rows (or not all on one) issues lane by lane, as before.
+                            int gy = ry, glo = rmin, ghi = rmax;
+                            asm volatile("s_nop 1\n\t"
+                                         "v_min_i32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_min_i32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_max_i32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_min_i32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_min_i32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_max_i32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_min_i32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_min_i32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+                                         "v_max_i32_dpp %2, %2, %2 row_half_mirror row_mask:0xf bank_mask:0xf"
+                                         : "+v"(gy), "+v"(glo), "+v"(ghi));   // (a chain's steps stand two instructions apart: the wait states a DPP read needs)
+                            // (the least row of the group is every lane's own: one row; a lane without a run has row -32768)
+                            unsigned long long u = ~__builtin_amdgcn_ballot_w64(gy == ry);
+                            u |= u >> 4; u |= u >> 2; u |= u >> 1;
+                            u &= 0x0101010101010101ull;                          // bit 0 of a group: a lane of it is elsewhere
+                            const unsigned long long apart = (u << 8) - u;       // the lanes of such groups
+                            const bool own = __builtin_amdgcn_inverse_ballot_w64(apart);
+                            if (open && __builtin_amdgcn_inverse_ballot_w64(apart | 0x0101010101010101ull)) {
+                                atomicMin(&L.ctab[par][(ry & 63) * 2], own ? rmin : glo);
+                                atomicMax(&L.ctab[par][(ry & 63) * 2 + 1], own ? rmax : ghi);
+                            }
+                        } else if (open) {
                             atomicMin(&L.ctab[par][(ry & 63) * 2], rmin);
                             atomicMax(&L.ctab[par][(ry & 63) * 2 + 1], rmax);
                         }
@@ -1019,8 +1048,7 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
 #pragma unroll
                     for (int j = 0; j < NC; ++j)
                         mx = max_raw(mx, 64 * (j >> 2) + tq4 + (j & 3) < D ? cost[j] : -INFINITY);
-                    mx = max_raw(mx, xor16_f(mx));
-                    mx = max_raw(mx, bperm_f(a32, mx));
+                    mx = quad_max<DIST_LANE_XCHG>(mx, a32);
                     float ssum = 0.0f, esum = 0.0f;
 #pragma unroll
                     for (int j = 0; j < NC; ++j) {
@@ -1029,8 +1057,8 @@ __global__ __launch_bounds__(256, NH == 1 ? DIST_OCC1 : DIST_OCC2) void sweep_di
                         ssum = ssum + ek;
                         esum = __builtin_fmaf(L.dcl[k], ek, esum);
                     }
-                    ssum = ssum + xor16_f(ssum); ssum = ssum + bperm_f(a32, ssum);
-                    esum = esum + xor16_f(esum); esum = esum + bperm_f(a32, esum);
+                    ssum = quad_sum<DIST_LANE_XCHG>(ssum, a32);
+                    esum = quad_sum<DIST_LANE_XCHG>(esum, a32);
                     if (kq == 0) *reinterpret_cast<v4f*>(&L.red[(wave * 16 + n) * 4]) = v4f{mx, ssum, esum, 0.0f};
                 }
                 DSTAMP(10)   // cost stores, partial softmax

@@ -35,6 +35,12 @@
 #ifndef DIST_REV_BATCH
 #define DIST_REV_BATCH 1      // 1: on the NCHW entry the queues hand out the batch items last to first -- the pack kernel wrote the last one last (bit-identical; headline -2.1 %, the sweep kernel 277 -> 272 us: profiles/r14_l2_warm/); 0: first to last
 #endif
+#ifndef DIST_LANE_XCHG
+#define DIST_LANE_XCHG 0      // how the centring's and the partial softmax's sums and maxima cross the four K-slice lanes of a pixel (wave_util.hpp: quad_sum, quad_max): 0 = ds_swizzle + ds_bpermute (LDS pipe, an lgkmcnt wait behind each); 1 = v_permlane16_swap / v_permlane32_swap (vector pipe; bit-identical; headline +0.4 us alone, +1.7 us beside DIST_ROWTAB_FOLD: profiles/r15_lane_exchange/)
+#endif
+#ifndef DIST_ROWTAB_FOLD
+#define DIST_ROWTAB_FOLD 1    // 1: the row table's last update of a thread is folded over groups of eight lanes with DPP where they end on one row, one lane issuing the two LDS atomics (bit-identical; headline -1.3 %, --pose stereo -7.1 %, config 5 -2.1 %: profiles/r15_lane_exchange/); 0: every lane issues its own
+#endif
 #ifndef DIST_ONE_EACH_X
 #define DIST_ONE_EACH_X 6  // a workgroup per item, no queue, up to this many items per resident workgroup (2 .. 24: the large shapes are indifferent; profiles/r06_ab/)
 #endif

@@ -109,6 +109,43 @@ __device__ __forceinline__ float max_raw(float a, float b) {
     return r;
 }
 
+// All-reduce over the four K-slice lanes of a pixel (lanes l, l ^ 16, l ^ 32, l ^ 48): the sum / max_raw of the four values in
+// every one of them -- x combined with lane ^ 16's first, the result with lane ^ 32's, this lane's value the first operand both
+// times -- by either transport:
+//   XCHG == 0  the LDS pipe: ds_swizzle + ds_bpermute (a32 = (lane ^ 32) << 2), an lgkmcnt wait behind each;
+//   XCHG == 1  the vector pipe: v_permlane16_swap_b32 exchanges the odd rows of 16 of its first operand with the even rows of
+//              its second, v_permlane32_swap_b32 the upper half of the first with the lower half of the second.  On two copies
+//              of x one of the two results is, in every lane, its partner's value: the second result in the even rows / the
+//              lower half, the first in the others -- picked with a constant lane mask (one v_cndmask, no compare).  No LDS
+//              queue, no lgkmcnt; the swaps read copies the compiler makes, and it pads the hazard "vector write -> swap
+//              reads it" itself.
+// The same bits, NaNs included, as long as the operand order is kept: a + b and b + a differ where both are NaNs of different
+// signs (an input NaN beside the -NaN that inf - inf makes; a first form that added the swaps' two results as they came failed
+// tools/mb_lane_exchange.hip on exactly that).  That program compares the two transports bit for bit, beside
+// v_mfma_f32_16x16x32_f16 and LDS atomics in the other waves of the SIMD as well (the packed-fp32 finding above is why a new
+// cross-lane instruction gets that look), and times a step of either: 68 against 32 cycles in a dependent chain.
+// sweep_dist.hip uses the LDS pipe all the same (DIST_LANE_XCHG): in that kernel the swaps' copies, picks and pads cost the
+// vector pipe what the LDS round trips cost in waiting (profiles/r15_lane_exchange/).
+template <int XCHG, bool MAX>
+__device__ __forceinline__ float quad_reduce(float x, int a32) {
+    auto comb = [](float a, float b) { return MAX ? max_raw(a, b) : a + b; };
+    auto f = [](unsigned u) { return __builtin_bit_cast(float, u); };
+    static_assert(XCHG == 0 || XCHG == 1, "the transport: 0 = LDS pipe, 1 = lane swaps");
+    if (XCHG == 1) {
+        const unsigned u = __builtin_bit_cast(unsigned, x);
+        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+        x = comb(x, __builtin_amdgcn_inverse_ballot_w64(0xffff0000ffff0000ull) ? f(r[0]) : f(r[1]));
+        const unsigned v = __builtin_bit_cast(unsigned, x);
+        const auto s = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+        return comb(x, __builtin_amdgcn_inverse_ballot_w64(0xffffffff00000000ull) ? f(s[0]) : f(s[1]));
+    } else {
+        x = comb(x, xor16_f(x));
+        return comb(x, bperm_f(a32, x));
+    }
+}
+template <int XCHG> __device__ __forceinline__ float quad_sum(float x, int a32) { return quad_reduce<XCHG, false>(x, a32); }
+template <int XCHG> __device__ __forceinline__ float quad_max(float x, int a32) { return quad_reduce<XCHG, true>(x, a32); }
+
 template <typename T>
 __device__ __forceinline__ T kernarg_at(size_t offset) {
     typedef const char __attribute__((address_space(4))) * kptr;
