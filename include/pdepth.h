@@ -69,7 +69,8 @@ extern "C" {
                                 *    pdepth_range_map_workspace_bytes, pdepth_range_map_f32, pdepth_depth_range_map_f32;
                                 *    pdepth_flow_warp_f32, pdepth_flow_warp_backward_f32, pdepth_flow_warp_backward_det_f32 and its
                                 *    _det_workspace_bytes, pdepth_flow_fb_check_f32; pdepth_loss_smooth1_f32 and its _backward_f32;
-                                *    pdepth_flow_cost_volume_f32, its _backward_f32 and _backward_det_f32 and their workspace queries */
+                                *    pdepth_flow_cost_volume_f32, its _backward_f32 and _backward_det_f32 and their workspace queries;
+                                *    pdepth_flow_photo_workspace_bytes, pdepth_flow_photo_f32, pdepth_flow_photo_backward_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -953,6 +954,44 @@ int pdepth_flow_cost_volume_backward_det_f32(const float *x1, const float *x2, c
                                              const float *grad_out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t max_displacement,
                                              float negative_slope, int32_t pad, float *grad_x1, float *grad_x2, float *grad_flow,
                                              void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * One direction of the photometric term of the unsupervised flow loss in one pass each way (csrc/flow_photo.hip):
+ * losses/flow_loss.py:13-27, loss_photomatric at its fixed max_distance = 1, with the warp of :66-78 inside.  im, other [B,3,H,W],
+ * flow [B,2,H,W], mask [B,1,H,W] (any float; in practice 0 / 1), pad as the flow entries.  With R = flow_warp(other, flow, pad) by the
+ * chain of pdepth_flow_warp_f32 (the same bits), x = R mask, y = im mask and N = B H W:
+ *     value = ( w_l1 sum |im - R| mask / (3 N)  +  w_ssim sum_windows dist(x, y) / (3 B (H - 2)(W - 2))  +  w_ternary sum T(x, y) / N )
+ *             / (sum(mask) / N)
+ *     count = sum(mask)
+ * dist the clamped 3 x 3 window distance of pdepth_ssim_f32 (md = 1), T the census distance of pdepth_ternary_f32 (md = 1; 0 in the
+ * border ring; its zero padding sees the masked images).  value and count are ONE float each.  A weight that is not > 0 -- zero,
+ * negative, NaN: the reference's `if w > 0` -- removes its term entirely: nothing of it is evaluated, a NaN it would have produced
+ * does not reach the value; with all three off the value is 0 / (sum(mask) / N).  The products with the mask stay products: a NaN
+ * behind a zero mask makes the value NaN; sum(mask) == 0 gives 0 / 0 = NaN; a non-finite flow has no tap and R = 0 there.
+ *
+ *   pdepth_flow_photo_f32           two launches: a workgroup per 64 x 8 tile and item evaluates the warp chain for the tile and a
+ *       halo of 1 and writes four partial sums (fp32, a fixed tree) to the workspace; one workgroup adds them in a fixed order in
+ *       double.  No atomics: the same bits from call to call.  Nothing per-pixel is written.
+ *   pdepth_flow_photo_backward_f32  count [1] (the forward's), g_value [1] -> g_flow [B,2,H,W], one launch; the images and the mask
+ *       are data.  The chain is recomputed with a halo of 2.  Per pixel and channel the gradient of R is the sum of
+ *       -g w_l1 / (3 N) sign(im - R) mask (sign(0) = 0), mask times the gather of pdepth_ssim_backward_f32 over the up to nine windows
+ *       that contain the pixel (in its order, with the forward's clamp decision, inclusive rule), and mask 255 (0.2989, 0.5870,
+ *       0.1140)_c times the census gather of pdepth_ternary_backward_f32, with g = g_value / (count / N); g_flow is formed from it as
+ *       pdepth_flow_warp_backward_f32 forms grad_flow (channel order, the clamp factors).  A gather in a fixed order: no atomics, the
+ *       same bits from call to call.
+ * Workspace: pdepth_flow_photo_workspace_bytes(B, H, W) = roundup256(16 ceil(W / 64) ceil(H / 8) B) bytes, 256-byte aligned; the
+ * query returns 0 for sizes out of range; missing, too small or misaligned: PDEPTH_E_WORKSPACE.
+ * The sizes and pads pdepth_flow_warp_f32 refuses are refused; B * H * W <= 2^24 (a pixel count is exact in fp32); H and W of at least
+ * 3 when w_ssim or w_ternary is on (the message names "H=.., W=.."); a null pointer, g_flow aliasing flow: PDEPTH_E_ARG, before any
+ * launch.  Nothing is allocated, nothing waits for the host.
+ */
+size_t pdepth_flow_photo_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_flow_photo_f32(const float *im, const float *other, const float *flow, const float *mask, int32_t B, int32_t H, int32_t W,
+                          int32_t pad, double w_l1, double w_ssim, double w_ternary, float *value, float *count, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int pdepth_flow_photo_backward_f32(const float *im, const float *other, const float *flow, const float *mask, const float *count,
+                                   const float *g_value, int32_t B, int32_t H, int32_t W, int32_t pad, double w_l1, double w_ssim,
+                                   double w_ternary, float *g_flow, void *stream);
 
 #ifdef __cplusplus
 }

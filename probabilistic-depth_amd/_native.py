@@ -120,6 +120,9 @@ _SIGNATURES = {
     "pdepth_flow_cost_volume_backward_f32": (c_int, [_P] * 5 + [_I] * 5 + [_F, _I] + [_P] * 4 + [_Z, _P]),
     "pdepth_flow_cost_volume_backward_det_workspace_bytes": (_Z, [_I] * 5),
     "pdepth_flow_cost_volume_backward_det_f32": (c_int, [_P] * 5 + [_I] * 5 + [_F, _I] + [_P] * 4 + [_Z, _P]),
+    "pdepth_flow_photo_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_flow_photo_f32": (c_int, [_P] * 4 + [_I] * 4 + [c_double] * 3 + [_P] * 3 + [_Z, _P]),
+    "pdepth_flow_photo_backward_f32": (c_int, [_P] * 6 + [_I] * 4 + [c_double] * 3 + [_P] * 2),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM, census and range-map entries live in objects of their own: part of an entry's name -> the source file.  The
@@ -128,7 +131,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_loss_smooth1_": "csrc/loss_smooth1.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
                     "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip", "_ternary_": "csrc/ternary.hip",
-                    "_range_map_": "csrc/occlusion.hip", "_flow_cost_volume_": "csrc/cost_volume.hip", "_flow_": "csrc/flow_warp.hip",
+                    "_range_map_": "csrc/occlusion.hip", "_flow_cost_volume_": "csrc/cost_volume.hip", "_flow_photo_": "csrc/flow_photo.hip",
+                    "_flow_": "csrc/flow_warp.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -1660,6 +1664,65 @@ def flow_cost_volume_backward(x1, x2, flow, out, grad_out, max_displacement=4, n
                                         code, _ptr(g1), _ptr(g2), _ptr(gf), _ptr(ws), ws_bytes, _stream(dev))
     _check(rc, lib)
     return g1, g2, gf
+
+
+def _flow_photo_args(who, im, other, flow, mask, w_l1, w_ssim, w_ternary, pad):
+    """((B, H, W), (im, other, flow, mask), weights, pad code) of a flow_photo call: im, other [B,3,H,W], flow [B,2,H,W], mask
+    [B,1,H,W], contiguous fp32 device tensors.  Shapes and scalars are judged first, where the tensors live; the device last."""
+    if pad not in FLOW_PADS:
+        raise RuntimeError(f"{who}: pad must be 'border' or 'zeros', got {pad!r}")
+    named = {"im": im, "other": other, "flow": flow, "mask": mask}
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+    if im.dim() != 4 or im.shape[0] < 1 or im.shape[1] != 3:
+        raise RuntimeError(f"{who}: im must be [B,3,H,W] with B >= 1, got {list(im.shape)}")
+    B, _, H, W = im.shape
+    weights = (float(w_l1), float(w_ssim), float(w_ternary))
+    if H < 2 or W < 2:
+        raise RuntimeError(f"{who}: H={H}, W={W}: the grid is normalised by H - 1 and W - 1, both must be at least 2")
+    if (weights[1] > 0 or weights[2] > 0) and (H < 3 or W < 3):
+        raise RuntimeError(f"{who}: H={H}, W={W}: the SSIM and census terms need H and W of at least 3")
+    _shape(other, (B, 3, H, W), "other", who)
+    _shape(flow, (B, 2, H, W), "flow", who)
+    _shape(mask, (B, 1, H, W), "mask", who)
+    return (B, H, W), tuple(_fp32_maps(who, **named)), weights, FLOW_PADS[pad]
+
+
+def flow_photo(im, other, flow, mask, w_l1, w_ssim, w_ternary, pad="border"):
+    """-> (value, count), 0-dim tensors: pdepth_flow_photo_f32, the warp of `other` along the flow, the masked L1, the SSIM and the
+    census distance against `im` in one pass, over the mean of the mask (count = its sum)."""
+    who = "flow_photo"
+    _no_autograd(who, im, other, flow, mask)
+    (B, H, W), t, weights, code = _flow_photo_args(who, im, other, flow, mask, w_l1, w_ssim, w_ternary, pad)
+    lib = load()
+    dev = t[0].device
+    ws_bytes = _entry(lib, "pdepth_flow_photo_workspace_bytes")(B, H, W)
+    out = torch.empty((2,), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_flow_photo_f32")(*(x.data_ptr() for x in t), B, H, W, code, *weights, out[0].data_ptr(), out[1].data_ptr(),
+                                                  ws.data_ptr(), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return out[0], out[1]
+
+
+def flow_photo_backward(im, other, flow, mask, count, g_value, w_l1, w_ssim, w_ternary, pad="border"):
+    """count, g_value (one element each) -> g_flow [B,2,H,W]: pdepth_flow_photo_backward_f32."""
+    who = "flow_photo_backward"
+    (B, H, W), t, weights, code = _flow_photo_args(who, im, other, flow, mask, w_l1, w_ssim, w_ternary, pad)
+    for name, v in (("count", count), ("g_value", g_value)):
+        if v.numel() != 1:
+            raise RuntimeError(f"{who}: {name} must have one element, got {list(v.shape)}")
+    count, g_value = _maps(who, count=count.reshape(1), g_value=g_value.reshape(1))
+    lib = load()
+    dev = t[0].device
+    g = torch.empty_like(t[2])
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_flow_photo_backward_f32")(*(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W, code,
+                                                           *weights, g.data_ptr(), _stream(dev))
+    _check(rc, lib)
+    return g
 
 
 def _smooth1_args(who, flo, image):

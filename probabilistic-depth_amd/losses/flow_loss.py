@@ -12,6 +12,10 @@ What a scale composes, in the order of the reference's loss_photomatric (:13-27)
 The 'area' resizes of the images stay F.interpolate.  Device fp32 tensors only: the ops have no CPU path.  Nothing is printed and
 nothing is read back to the host.
 
+unFlowLoss(cfg, fused_photo=True): the warp and the photometric pieces of a scale and direction are one ops.flow_photometric call
+(csrc/flow_photo.hip: three launches for forward and backward together); the masks, the resizes and the smoothness are the ones
+above.  Off by default; off, every output bit is the composition's.
+
 cfg attributes: w_l1, w_ssim, w_ternary, alpha, warp_pad, occ_from_back, with_bk, w_scales, w_sm_scales, w_smooth.
 """
 import torch.nn as nn
@@ -21,7 +25,19 @@ from .. import ops
 from ..utils.warp_utils import get_occu_mask_backward
 
 
-class unFlowLoss(nn.Module):
+class _Switches(type):
+    """unFlowLoss(cfg, fused_photo=False): the switch is taken at the call of the class, so that __init__ keeps the reference's
+    signature -- cfg alone -- for code that subclasses or inspects it."""
+
+    def __call__(cls, cfg, fused_photo=False):
+        loss = super().__call__(cfg)
+        loss.fused_photo = bool(fused_photo)
+        return loss
+
+
+class unFlowLoss(nn.Module, metaclass=_Switches):
+    fused_photo = False
+
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
@@ -38,6 +54,13 @@ class unFlowLoss(nn.Module):
         if cfg.w_ternary > 0:
             total = total + (cfg.w_ternary * ops.ternary(recons, seen)).mean()
         return total / occu_mask1.mean()
+
+    def _photometric(self, im, other, flow, mask):
+        """The photometric term of one direction: `other` warped along `flow` against `im` under `mask`."""
+        cfg = self.cfg
+        if self.fused_photo:
+            return ops.flow_photometric(im, other, flow, mask, cfg.w_l1, cfg.w_ssim, cfg.w_ternary, pad=cfg.warp_pad)[0]
+        return self.loss_photomatric(im, ops.flow_warp(other, flow, pad=cfg.warp_pad), mask)
 
     def loss_smooth(self, flow, im1_scaled):
         return ops.smooth_grad_1st(flow, im1_scaled, self.cfg.alpha)
@@ -65,7 +88,6 @@ class unFlowLoss(nn.Module):
             h, w = flow.shape[2:]
             fwd, bwd = flow[:, :2], flow[:, 2:]
             im1, im2 = (F.interpolate(im, (h, w), mode='area') for im in images)
-            recons1 = ops.flow_warp(im2, fwd, pad=cfg.warp_pad)
             if i == 0:
                 mask1, mask2 = self._first_masks(fwd, bwd)
                 s = min(h, w)
@@ -75,11 +97,10 @@ class unFlowLoss(nn.Module):
             self.pyramid_occu_mask1.append(mask1)
             self.pyramid_occu_mask2.append(mask2)
 
-            warp = self.loss_photomatric(im1, recons1, mask1)
+            warp = self._photometric(im1, im2, fwd, mask1)
             smooth = self.loss_smooth(fwd / s, im1)
             if cfg.with_bk:
-                recons2 = ops.flow_warp(im1, bwd, pad=cfg.warp_pad)
-                warp = (warp + self.loss_photomatric(im2, recons2, mask2)) / 2.
+                warp = (warp + self._photometric(im2, im1, bwd, mask2)) / 2.
                 smooth = (smooth + self.loss_smooth(bwd / s, im2)) / 2.
             warp_terms.append(warp * cfg.w_scales[i])
             smooth_terms.append(smooth * cfg.w_sm_scales[i])

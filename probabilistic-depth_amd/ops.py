@@ -397,6 +397,26 @@ def flow_cost_volume(x1, x2, flow=None, max_displacement=4, negative_slope=0.1, 
     return _native.flow_cost_volume(x1, x2, flow, max_displacement, negative_slope, pad)
 
 
+def flow_photometric(im, other, flow, mask, w_l1, w_ssim, w_ternary, pad="border"):
+    """One direction of the flow loss's photometric term (losses/flow_loss.py:13-27 with the warp of :66-78 inside), one HIP pass
+    each way (csrc/flow_photo.hip): -> (value, count), 0-dim fp32 tensors.  im, other [B,3,H,W], flow [B,2,H,W], mask [B,1,H,W],
+    fp32 device tensors.  With R = flow_warp(other, flow, pad), x = R mask, y = im mask:
+        value = (w_l1 mean(|im - R| mask) + w_ssim mean(ssim(x, y)) + w_ternary mean(ternary(x, y))) / mean(mask),  count = sum(mask)
+    what unFlowLoss.loss_photomatric composes from ops.flow_warp, ops.ssim and ops.ternary (md = 1).  A weight that is not > 0
+    removes its term entirely; H or W below 3 with the SSIM or census term on: a RuntimeError that names the sizes.  A NaN behind
+    a zero mask makes the value NaN, an empty mask gives 0 / 0 = NaN, a non-finite flow samples 0.  Differentiable with respect to
+    the flow only (a gather in a fixed order: the same bits from call to call, no deterministic switch needed); im, other and mask
+    are data and are refused when they require grad."""
+    who = "flow_photometric"
+    if _wants_grad(im, other, flow, mask):
+        for name, x in (("im", im), ("other", other), ("mask", mask)):
+            if isinstance(x, torch.Tensor) and x.requires_grad:
+                raise RuntimeError(f"{who}: {name} requires grad, but the HIP backward differentiates the flow only (images and "
+                                   f"masks are data); detach {name}")
+        return _FlowPhotoFn.apply(im, other, flow, mask, float(w_l1), float(w_ssim), float(w_ternary), pad)
+    return _native.flow_photo(im, other, flow, mask, w_l1, w_ssim, w_ternary, pad)
+
+
 def flow_fb_check(flow12, flow21, scale=0.01, bias=0.5):
     """Forward-backward check (utils/warp_utils.py:92-99, get_occu_mask_bidirection), one HIP pass: occ [B,1,H,W], 1 where
     |flow12 + w|^2 > scale (|flow12|^2 + |w|^2) + bias with w = flow21 sampled at base + flow12 (zeros padding).  A mask has no
@@ -798,6 +818,26 @@ class _FlowWarpFn(torch.autograd.Function):
         pad, deterministic = ctx.cfg
         g_x, g_f = _native.flow_warp_backward(x, flow, g_out, pad, want_x=want_x, want_flow=want_flow, deterministic=deterministic)
         return g_x, g_f, None, None
+
+
+class _FlowPhotoFn(torch.autograd.Function):
+    """flow_photometric under autograd: (value, count); the backward recomputes from the inputs."""
+
+    @staticmethod
+    def forward(ctx, im, other, flow, mask, w_l1, w_ssim, w_ternary, pad):
+        ctx.set_materialize_grads(False)
+        ctx.cfg = (w_l1, w_ssim, w_ternary, pad)
+        value, count = _native.flow_photo(im, other, flow, mask, *ctx.cfg)
+        ctx.save_for_backward(im, other, flow, mask, count)
+        ctx.mark_non_differentiable(count)
+        return value, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_value, _g_count):
+        if g_value is None or not ctx.needs_input_grad[2]:
+            return (None,) * 8
+        return None, None, _native.flow_photo_backward(*ctx.saved_tensors, g_value, *ctx.cfg), None, None, None, None, None
 
 
 class _FlowCostVolumeFn(torch.autograd.Function):
