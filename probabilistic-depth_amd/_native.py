@@ -1227,13 +1227,20 @@ def loss_rsc_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count, g_value):
     return g
 
 
-def _photo_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, md):
-    """_rsc_args, and the window of the SSIM: md one of SSIM_MD, H and W of at least 2 md + 1."""
+def _check_md(who, md, noun=None, H=None, W=None):
+    """The refusals a half-width shares among the SSIM, the census and the photometric term: md is one the kernels are built for,
+    and, given H and W, they hold one `noun` ("window", "patch") of (2 md + 1)^2.  Two calls where the shapes are judged between."""
     if md not in SSIM_MD:
         raise NotImplementedError(f"{who}: md={md}: the HIP kernels are built for md = 1, 2 and 3")
+    if noun is not None and (H < 2 * md + 1 or W < 2 * md + 1):
+        raise RuntimeError(f"{who}: H={H}, W={W}: a {noun} of md={md} needs H and W of at least {2 * md + 1}")
+
+
+def _photo_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, md):
+    """_rsc_args, and the window of the SSIM: md one of SSIM_MD, H and W of at least 2 md + 1."""
+    _check_md(who, md)
     _, H, W = _map_dims(who, tgt_depth, "tgt_depth")
-    if H < 2 * md + 1 or W < 2 * md + 1:
-        raise RuntimeError(f"{who}: H={H}, W={W}: a window of md={md} needs H and W of at least {2 * md + 1}")
+    _check_md(who, md, "window", H, W)
     return _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
 
 
@@ -1354,16 +1361,14 @@ SSIM_MD = (1, 2, 3)   # the window half-widths the kernels are built for
 
 def _ssim_args(who, x, y, md):
     """((B, C, H, W), x, y) of an SSIM call: two [B,C,H,W] device tensors of one shape, as contiguous fp32."""
-    if md not in SSIM_MD:
-        raise NotImplementedError(f"{who}: md={md}: the HIP kernels are built for md = 1, 2 and 3")
+    _check_md(who, md)
     x, y = _maps(who, x=x, y=y)
     if x.dim() != 4 or x.shape != y.shape:
         raise RuntimeError(f"{who}: x and y must be two [B,C,H,W] tensors of one shape, got {list(x.shape)} and {list(y.shape)}")
     B, C, H, W = x.shape
     if B < 1 or C < 1:
         raise RuntimeError(f"{who}: x and y must be [B,C,H,W] with B, C >= 1, got {list(x.shape)}")
-    if H < 2 * md + 1 or W < 2 * md + 1:
-        raise RuntimeError(f"{who}: H={H}, W={W}: a window of md={md} needs H and W of at least {2 * md + 1}")
+    _check_md(who, md, "window", H, W)
     return (B, C, H, W), x, y
 
 
@@ -1405,8 +1410,7 @@ TERNARY_MD = (1, 2, 3)   # the patch half-widths the kernels are built for
 def _ternary_args(who, x, y, md):
     """((B, H, W), x, y) of a census call: two [B,3,H,W] device tensors of one shape, as contiguous fp32.  The shapes are judged
     first, where the tensors live; the device last."""
-    if md not in TERNARY_MD:
-        raise NotImplementedError(f"{who}: md={md}: the HIP kernels are built for md = 1, 2 and 3")
+    _check_md(who, md)
     for name, t in (("x", x), ("y", y)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{who}: {name}: expected a torch.Tensor")
@@ -1415,8 +1419,7 @@ def _ternary_args(who, x, y, md):
     B, C, H, W = x.shape
     if B < 1 or C != 3:
         raise RuntimeError(f"{who}: x and y must be [B,3,H,W] RGB images with B >= 1, got {list(x.shape)} and {list(y.shape)}")
-    if H < 2 * md + 1 or W < 2 * md + 1:
-        raise RuntimeError(f"{who}: H={H}, W={W}: a patch of md={md} needs H and W of at least {2 * md + 1}")
+    _check_md(who, md, "patch", H, W)
     x, y = _maps(who, x=x, y=y)
     return (B, H, W), x, y
 

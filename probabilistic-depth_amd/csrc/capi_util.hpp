@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/pdepth.h"
 #include "kernels.hpp"
@@ -60,6 +61,22 @@ inline int check_map(const char* who, int32_t B, int32_t H, int32_t W, int least
     if (H < least || W < least) return fail(PDEPTH_E_ARG, "%s: H and W must be at least %d", who, least);
     if ((long long)H * W > (1ll << 24) || B > 65535) return fail(PDEPTH_E_ARG, "%s: H*W must be at most 2^24 and B at most 65535", who);
     return PDEPTH_OK;
+}
+
+// the half-width of a window or patch (`noun`: the word the message uses) of (2 md + 1)^2: md in 1..3, and H and W hold one
+inline int check_window(const char* who, const char* noun, int32_t H, int32_t W, int32_t md) {
+    if (md < 1 || md > 3) return fail(PDEPTH_E_ARG, "%s: md=%d: the %s is (2 md + 1)^2 with md = 1, 2 or 3", who, md, noun);
+    if (H < 2 * md + 1 || W < 2 * md + 1)
+        return fail(PDEPTH_E_ARG, "%s: H=%d, W=%d: md=%d needs H and W of at least %d", who, H, W, md, 2 * md + 1);
+    return PDEPTH_OK;
+}
+
+// md (one that check_window passes) as a compile-time constant: f(std::integral_constant<int, 1 | 2 | 3>)
+template <typename F>
+inline void for_md(int md, F&& f) {
+    if (md == 1) f(std::integral_constant<int, 1>{});
+    else if (md == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
 }
 
 // ---- the sweep descriptor (the entries of capi.hip and sweep_bwd_det.hip) ----

@@ -20,8 +20,11 @@
 // Every piece of arithmetic is a shared header's: position, taps, value, d_ix / d_iy and the clamp masks (flow_warp_sample.hpp: R
 // has the bits of pdepth_flow_warp_f32, and the flow's gradient is formed from g_R exactly as flow_warp.hip's grad_flow pass
 // forms it), the window sums, the window chain and its coefficients (ssim_math.hpp: the backward's clamp decision is the
-// forward's), the gray value and the pair chain (ternary_math.hpp).  The products with the mask stay products: a NaN behind a zero
-// mask makes the value NaN; an empty mask is 0 / 0 = NaN; a non-finite flow has no tap, R = 0 there.
+// forward's), the gray value and the pair chain (ternary_math.hpp); and so is every walk over the tile: the window of a pixel, the
+// coefficient planes and their gather, the census sum and gather (window_tile.hpp: the bodies ssim.hip and ternary.hip run, here
+// with md = 1), the sums (loss_terms_sum.hpp).  What is this file's own: the staging, the L1 term, the channel order.  The
+// products with the mask stay products: a NaN behind a zero mask makes the value NaN; an empty mask is 0 / 0 = NaN; a non-finite
+// flow has no tap, R = 0 there.
 //
 // Tile.  A workgroup of 256 threads owns 64 x 8 pixels of one item (blockIdx.z), lanes along W; a thread owns 2 pixels of one
 // column.  The height is ternary.hip's, for its reason: with the census on, a pixel costs 8 chains of two square roots and three
@@ -38,9 +41,9 @@
 //   backward  recomputes the chain with a halo of 2 (the windows that contain a pixel read their own 3 x 3 pixels; the census
 //             needs 1) and stages the same six planes and two gray planes (26 KiB).  A thread first takes the census gather of its
 //             pixels, g_I(p) = -sum_o (G(p) + G(p+o)) D(p, p+o) with G = g w_ter / (9 N) at the pixels the forward counts and 0
-//             elsewhere (ternary.hip's order).  Then one channel at a time: G P, G Q, G R of the 66 x 10 windows that touch the tile
+//             elsewhere (census_tile_gather).  Then one channel at a time: G P, G Q, G R of the 66 x 10 windows that touch the tile
 //             (8 KiB; zeros for windows that do not exist), a gather per pixel over the up to nine windows that contain it (rows
-//             top to bottom, left to right, as ssim_bwd_kernel), and
+//             top to bottom, left to right: ssim_tile_coef, ssim_tile_gather), and
 //                 g_R,c = -g w_l1 / (3 N) sign0(im_c - R_c) m  +  m sum_windows (G P + G Q x_p + G R y_p) / 9
 //                         +  m 255 (0.2989, 0.5870, 0.1140)_c g_I
 //             times d_ix(c), d_iy(c) of the pixel's own taps, summed over c in channel order; g = g_value / (count / N).
@@ -55,17 +58,16 @@
 #include "flow_warp_sample.hpp"
 #include "kernels.hpp"
 #include "loss_terms_math.hpp"
-#include "ssim_math.hpp"
-#include "ternary_math.hpp"
+#include "loss_terms_sum.hpp"
+#include "window_tile.hpp"
 
 namespace pdepth {
 
 namespace {
 
-constexpr int FP_TW = 64;   // tile width: one wave row
-constexpr int FP_TH = 8;    // tile height
-constexpr int FP_R = 2;     // rows of the tile per thread (256 threads = 64 columns x 4 strips)
-static_assert(FP_TW * FP_TH == 256 * FP_R, "a thread per column and strip");
+constexpr int FP_TH = 8;   // tile height
+using FpTile = WindowTile<1, FP_TH>;
+constexpr int FP_R = FpTile::R;
 
 struct FpArgs {
     const float* im;      // [B,3,H,W] the image of this side
@@ -150,27 +152,23 @@ __device__ __forceinline__ void fp_stage(const FpArgs& a, int b, int gy0, int gx
 __device__ __forceinline__ bool fp_inner(int px, int py, int H, int W) { return px >= 1 && px < W - 1 && py >= 1 && py < H - 1; }
 
 __global__ __launch_bounds__(256) void flow_photo_fwd_kernel(FpArgs a, int on_ssim, int on_ter, float* __restrict__ part) {
-    constexpr int LW = FP_TW + 2, LH = FP_TH + 2, LN = LH * LW;
+    constexpr int LW = FpTile::LW, LH = FpTile::LH, LN = LH * LW;
     __shared__ float sx[3 * LN];
     __shared__ float sy[3 * LN];
     __shared__ float sa[LN];
     __shared__ float sb[LN];
-    __shared__ float s0[4];
-    __shared__ float s1[4];
-    __shared__ float s2[4];
-    __shared__ float s3[4];
     const int H = a.g.H, W = a.g.W;
     const int b = blockIdx.z;
-    const int x0 = blockIdx.x * FP_TW, y0 = blockIdx.y * FP_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * FP_TH;
     float num = 0.0f, den = 0.0f, dist = 0.0f, tern = 0.0f;
     fp_stage<true>(a, b, y0 - 1, x0 - 1, LH, LW, sx, sy, sa, sb, [&](const FpPixel& p, int r, int c) {
-        if (r >= 1 && r <= FP_TH && c >= 1 && c <= FP_TW) {   // a pixel of the tile itself
+        if (r >= 1 && r <= FP_TH && c >= 1 && c <= TILE_W) {   // a pixel of the tile itself
             num += (fabsf(p.d[0]) * p.m + fabsf(p.d[1]) * p.m) + fabsf(p.d[2]) * p.m;
             den += p.m;
         }
     });
     __syncthreads();
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int px = x0 + tx;
 #pragma unroll
     for (int k = 0; k < FP_R; ++k) {
@@ -179,76 +177,31 @@ __global__ __launch_bounds__(256) void flow_photo_fwd_kernel(FpArgs a, int on_ss
         if (!fp_inner(px, py, H, W)) continue;
         if (on_ssim) {   // the window centred on the pixel: its first pixel is (ly, tx) of the stage
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float* wx = sx + ch * LN + ly * LW + tx;
-                const float* wy = sy + ch * LN + ly * LW + tx;
-                dist += ssim_clamp01(ssim_window(ssim_sums<3>(wx, wy, LW), 9.0f).d);
-            }
+            for (int ch = 0; ch < 3; ++ch) dist += ssim_tile_dist<1>(sx + ch * LN, sy + ch * LN, ly, tx);
         }
-        if (on_ter) {   // ternary_fwd_kernel's sum: rows top to bottom, left to right, without the centre
-            const float c = sa[(ly + 1) * LW + tx + 1], cp = sb[(ly + 1) * LW + tx + 1];
-            float sum = 0.0f;
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    if (dy == 1 && dx == 1) continue;
-                    const int q = (ly + dy) * LW + tx + dx;
-                    sum += ternary_h(sa[q] - c, sb[q] - cp);
-                }
-            }
-            tern += sum / 9.0f;
-        }
+        if (on_ter) tern += census_tile_sum<1>(sa, sb, LW, ly, tx) / 9.0f;   // the patch centred on the pixel
     }
-    wg_sum_put(num, s0);
-    wg_sum_put(den, s1);
-    wg_sum_put(dist, s2);
-    wg_sum_put(tern, s3);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const size_t nblk = (size_t)gridDim.x * gridDim.y * gridDim.z;
-        const size_t slot = ((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        part[slot] = wg_sum_get(s0);
-        part[nblk + slot] = wg_sum_get(s1);
-        part[2 * nblk + slot] = wg_sum_get(s2);
-        part[3 * nblk + slot] = wg_sum_get(s3);
-    }
+    block_partial({num, den, dist, tern}, part);
 }
 
 // the four partial sums of the batch in a fixed order, in double; a term that is off is not read into the value
 __global__ __launch_bounds__(256) void flow_photo_final_kernel(const float* __restrict__ part, int nblk, FpTerms t,
                                                                float* __restrict__ value, float* __restrict__ count) {
-    __shared__ double sa[4];
-    __shared__ double sb[4];
-    __shared__ double sc[4];
-    __shared__ double sd[4];
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-        a0 += (double)part[i];
-        a1 += (double)part[(size_t)nblk + i];
-        a2 += (double)part[(size_t)2 * nblk + i];
-        a3 += (double)part[(size_t)3 * nblk + i];
-    }
-    wg_sum_put(a0, sa);
-    wg_sum_put(a1, sb);
-    wg_sum_put(a2, sc);
-    wg_sum_put(a3, sd);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t0 = (float)wg_sum_get(sa), t1 = (float)wg_sum_get(sb), t2 = (float)wg_sum_get(sc), t3 = (float)wg_sum_get(sd);
-        float total = 0.0f;
-        if (t.on_l1) total = total + t.w_l1 * (t0 / t.n3);
-        if (t.on_ssim) total = total + t.w_ssim * (t2 / t.n_w);
-        if (t.on_ter) total = total + t.w_ter * (t3 / t.n);
-        value[0] = total / (t1 / t.n);
-        count[0] = t1;
-    }
+    float s[4];
+    partial_sums(part, (size_t)nblk, 0, nblk, s);
+    if (threadIdx.x != 0) return;
+    float total = 0.0f;
+    if (t.on_l1) total = total + t.w_l1 * (s[0] / t.n3);
+    if (t.on_ssim) total = total + t.w_ssim * (s[2] / t.n_w);
+    if (t.on_ter) total = total + t.w_ter * (s[3] / t.n);
+    value[0] = total / (s[1] / t.n);
+    count[0] = s[1];
 }
 
 __global__ __launch_bounds__(256) void flow_photo_bwd_kernel(FpArgs a, FpTerms t, const float* __restrict__ count,
                                                              const float* __restrict__ g_value, float* __restrict__ g_flow) {
-    constexpr int CW = FP_TW + 2, CH = FP_TH + 2;               // the windows that touch the tile
-    constexpr int IW = FP_TW + 4, IH = FP_TH + 4, IN = IH * IW;   // the pixels those windows read
+    constexpr int CW = FpTile::LW, CH = FpTile::LH;               // the windows that touch the tile
+    constexpr int IW = FpTile::IW, IH = FpTile::IH, IN = IH * IW;   // the pixels those windows read
     __shared__ float sx[3 * IN];
     __shared__ float sy[3 * IN];
     __shared__ float sa[IN];
@@ -259,7 +212,7 @@ __global__ __launch_bounds__(256) void flow_photo_bwd_kernel(FpArgs a, FpTerms t
     const int H = a.g.H, W = a.g.W, HW = H * W;
     const int OH = H - 2, OW = W - 2;
     const int b = blockIdx.z;
-    const int x0 = blockIdx.x * FP_TW, y0 = blockIdx.y * FP_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * FP_TH;
     const float gq = g_value[0] / (count[0] / t.n);   // d L / d (the sum of the three means)
     const float g_l1 = (gq * t.w_l1) / t.n3;          // d L / d |d_c| m of every pixel
     const float g_dist = (gq * t.w_ssim) / t.n_w;     // d L / d dist of every window
@@ -267,7 +220,7 @@ __global__ __launch_bounds__(256) void flow_photo_bwd_kernel(FpArgs a, FpTerms t
     if (t.on_ter) fp_stage<true>(a, b, y0 - 2, x0 - 2, IH, IW, sx, sy, sa, sb, [](const FpPixel&, int, int) {});
     else fp_stage<false>(a, b, y0 - 2, x0 - 2, IH, IW, sx, sy, sa, sb, [](const FpPixel&, int, int) {});
     __syncthreads();
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int px = x0 + tx;
     const int cx = px < W ? px : W - 1;   // (a thread past the image shadows the last pixel and stores nothing)
     flow::Sample q[FP_R];
@@ -282,40 +235,22 @@ __global__ __launch_bounds__(256) void flow_photo_bwd_kernel(FpArgs a, FpTerms t
         gi[k] = 0.0f;
         gix[k] = 0.0f;
         giy[k] = 0.0f;
-        if (t.on_ter) {   // ternary_bwd_kernel's gather; G is 0 outside the pixels the forward counts, the gray values 0 outside the image
-            const int p = (ly + 2) * IW + tx + 2;
-            const float c = sa[p], cpv = sb[p];
+        if (t.on_ter) {   // G is 0 outside the pixels the forward counts, the gray values 0 outside the image
             const float gp = fp_inner(px, py, H, W) ? g_ter : 0.0f;
-            float ax = 0.0f;
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    if (dy == 1 && dx == 1) continue;
-                    const int o = (ly + 1 + dy) * IW + tx + 1 + dx;
-                    const float w = gp + (fp_inner(px - 1 + dx, py - 1 + dy, H, W) ? g_ter : 0.0f);
-                    ax += w * ternary_deriv(sa[o] - c, sb[o] - cpv).dt;
-                }
-            }
-            gi[k] = -ax * 255.0f;
+            // (the stage has a halo of 2, the patch one of 1: its planes start a row and a column in)
+            const CensusGrad a1 = census_tile_gather<1, 3, false>(sa + IW + 1, sb + IW + 1, IW, ly, tx, [&](int, int oy, int ox) {
+                return gp + (fp_inner(px + ox, py + oy, H, W) ? g_ter : 0.0f);
+            });
+            gi[k] = -a1.x * 255.0f;
         }
     }
 #pragma unroll 1
     for (int ch = 0; ch < 3; ++ch) {
+        const float* xc = sx + ch * IN;
+        const float* yc = sy + ch * IN;
         if (t.on_ssim) {
             if (ch > 0) __syncthreads();   // the gather of the channel before is done with the coefficients
-            const float* xc = sx + ch * IN;
-            const float* yc = sy + ch * IN;
-            for (int i = threadIdx.x; i < CH * CW; i += 256) {
-                const int wr = i / CW, wc = i - wr * CW;
-                const int wy = y0 - 2 + wr, wx = x0 - 2 + wc;   // the window's first pixel
-                SsimCoef c{0.0f, 0.0f, 0.0f, 0.0f};
-                if (wy >= 0 && wy < OH && wx >= 0 && wx < OW)
-                    c = ssim_coef(ssim_window(ssim_sums<3>(xc + wr * IW + wc, yc + wr * IW + wc, IW), 9.0f), g_dist);
-                cp[i] = c.p;
-                cq[i] = c.q;
-                cr[i] = c.r;
-            }
+            ssim_tile_coef<1, FP_TH, false>(xc, yc, x0, y0, OH, OW, [=](int, int) { return g_dist; }, cp, nullptr, cq, cr);
             __syncthreads();
         }
         const float gray = ch == 0 ? 0.2989f : (ch == 1 ? 0.5870f : 0.1140f);
@@ -328,20 +263,7 @@ __global__ __launch_bounds__(256) void flow_photo_bwd_kernel(FpArgs a, FpTerms t
             const float d = a.im[((size_t)b * 3 + ch) * HW + cy * W + cx] - flow::value(q[k], v);
             float gw = 0.0f;
             if (t.on_l1) gw = -(g_l1 * sign0(d)) * m[k];
-            if (t.on_ssim) {
-                const int p = ch * IN + (ly + 2) * IW + tx + 2;
-                const float xp = sx[p], yp = sy[p];
-                float ax = 0.0f;
-#pragma unroll
-                for (int dy = 2; dy >= 0; --dy) {       // the window dy rows above the pixel, dx columns left of it:
-#pragma unroll
-                    for (int dx = 2; dx >= 0; --dx) {   // top to bottom, left to right
-                        const int ci = (ly + 2 - dy) * CW + (tx + 2 - dx);
-                        ax += (cp[ci] + cq[ci] * xp) + cr[ci] * yp;
-                    }
-                }
-                gw += m[k] * (ax / 9.0f);
-            }
+            if (t.on_ssim) gw += m[k] * ssim_tile_gather<1, false>(xc, yc, cp, nullptr, cq, cr, ly, tx).x;
             if (t.on_ter) gw += m[k] * (gi[k] * gray);
             if (q[k].any()) {   // flow_warp_grad_flow_kernel's sum over the channels
                 gix[k] += flow::d_ix(q[k], v) * gw;
@@ -359,10 +281,9 @@ __global__ __launch_bounds__(256) void flow_photo_bwd_kernel(FpArgs a, FpTerms t
     }
 }
 
-inline int tiles(int n, int tile) { return (n + tile - 1) / tile; }
-inline size_t n_blocks(int B, int H, int W) { return (size_t)B * tiles(W, FP_TW) * tiles(H, FP_TH); }
+inline size_t n_blocks(int B, int H, int W) { return (size_t)B * tiles(W, TILE_W) * tiles(H, FP_TH); }
 
-size_t workspace_bytes(int B, int H, int W) { return (4 * n_blocks(B, H, W) * sizeof(float) + 255) / 256 * 256; }
+size_t workspace_bytes(int B, int H, int W) { return partial_sums_bytes(4, n_blocks(B, H, W)); }
 
 // a weight as torch forms it from the Python number, and whether its term is on (the reference's `if w > 0`: a NaN is off)
 FpTerms terms_of(double w_l1, double w_ssim, double w_ternary, int B, int H, int W) {
@@ -415,7 +336,7 @@ int pdepth_flow_photo_f32(const float* im, const float* other, const float* flow
     const FpTerms t = terms_of(w_l1, w_ssim, w_ternary, B, H, W);
     float* part = static_cast<float*>(workspace);
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(tiles(W, FP_TW), tiles(H, FP_TH), B);
+    const dim3 grid(tiles(W, TILE_W), tiles(H, FP_TH), B);
     hipLaunchKernelGGL(flow_photo_fwd_kernel, grid, dim3(256), 0, s, a, t.on_ssim, t.on_ter, part);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return launched(err, who);
@@ -431,7 +352,7 @@ int pdepth_flow_photo_backward_f32(const float* im, const float* other, const fl
     if (int rc = check_flow_photo(who, B, H, W, pad, w_ssim, w_ternary)) return rc;
     if ((const float*)g_flow == flow) return fail(PDEPTH_E_ARG, "%s: the output may not alias the flow", who);
     const FpArgs a{im, other, flow, mask, flow::geometry(H, W), pad};
-    const dim3 grid(tiles(W, FP_TW), tiles(H, FP_TH), B);
+    const dim3 grid(tiles(W, TILE_W), tiles(H, FP_TH), B);
     hipLaunchKernelGGL(flow_photo_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, terms_of(w_l1, w_ssim, w_ternary, B, H, W),
                        count, g_value, g_flow);
     return launched(hipGetLastError(), who);

@@ -24,7 +24,7 @@ __device__ __forceinline__ float smooth1_weight(const float* __restrict__ im, in
 }
 
 // sums of w |d flo| along x and along y; grid (blocks of 256 pixels, B)
-__global__ __launch_bounds__(256) void loss_smooth1_kernel(const float* __restrict__ flo, const float* __restrict__ image, int B, int Cf,
+__global__ __launch_bounds__(256) void loss_smooth1_kernel(const float* __restrict__ flo, const float* __restrict__ image, int Cf,
                                                            int Ci, int H, int W, float alpha, float* __restrict__ part) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     const int HW = H * W;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void loss_smooth1_kernel(const float* __restri
             for (int c = 0; c < Cf; ++c) sy += w * fabsf(f[(size_t)c * HW + pix + W] - f[(size_t)c * HW + pix]);
         }
     }
-    block_partial(sx, sy, part, B);
+    block_partial({sx, sy}, part);
 }
 
 // gx = g / (4 Nx), gy = g / (4 Ny): the weights of the four pairs a pixel takes part in, then the flow's channels
@@ -100,10 +100,10 @@ int pdepth_loss_smooth1_f32(const float* flo, const float* image, int32_t B, int
     if (!flo || !image) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     if (!value) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
     if (int rc = check_smooth1(who, B, Cf, Ci, H, W, alpha)) return rc;
-    if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, H, W))) return rc;
+    if (int rc = check_workspace(who, workspace, workspace_bytes_given, two_sums_workspace_bytes(B, H, W))) return rc;
     const int nblk = n_blocks(H, W);
     float* part = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(loss_smooth1_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, flo, image, B, Cf, Ci, H, W, alpha, part);
+    hipLaunchKernelGGL(loss_smooth1_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, flo, image, Cf, Ci, H, W, alpha, part);
     // the partial sums of all items as those of one: [2][B][nblk] read as [2][1][B nblk]
     return launched(finish<false>(part, 1, B * nblk, pairs4(B, Cf, H, W - 1), pairs4(B, Cf, H - 1, W), value, nullptr, (hipStream_t)stream), who);
 }

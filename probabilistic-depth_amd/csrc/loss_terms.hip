@@ -46,7 +46,7 @@ namespace pdepth {
 namespace {
 
 // ---- depth stereo consistency (the per-pixel chain: loss_terms_math.hpp) ----------------------------------------------------------
-__global__ __launch_bounds__(256) void loss_dsc_kernel(DscArgs g, int B, float* __restrict__ part) {
+__global__ __launch_bounds__(256) void loss_dsc_kernel(DscArgs g, float* __restrict__ part) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     float num = 0.0f, den = 0.0f;
     if (pix < g.H * g.W) {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void loss_dsc_kernel(DscArgs g, int B, float* 
         num = rel_diff(p.a, p.b).diff * p.m;
         den = p.m;
     }
-    block_partial(num, den, part, B);
+    block_partial({num, den}, part);
 }
 
 // g_src (cleared by the launcher) and g_tgt may be nullptr
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void loss_dsc_bwd_kernel(DscArgs g, const floa
 
 // ---- RGB stereo consistency ----------------------------------------------------------------------------------------------------
 // (the per-pixel chain and the camera products of the backward: loss_terms_math.hpp)
-__global__ __launch_bounds__(256) void loss_rsc_kernel(RscArgs g, int B, float* __restrict__ part) {
+__global__ __launch_bounds__(256) void loss_rsc_kernel(RscArgs g, float* __restrict__ part) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     float num = 0.0f, den = 0.0f;
     if (pix < g.H * g.W) {
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void loss_rsc_kernel(RscArgs g, int B, float* 
         num = (fabsf(p.d[0]) * p.m + fabsf(p.d[1]) * p.m) + fabsf(p.d[2]) * p.m;
         den = p.m;
     }
-    block_partial(num, den, part, B);
+    block_partial({num, den}, part);
 }
 
 // The position gradient as inverse_warp_bwd_kernel<0> forms it (inverse_warp_math.hpp: the derivatives of the bilinear value,
@@ -141,7 +141,7 @@ __device__ __forceinline__ DcPixel dc_pixel(const float* __restrict__ large, con
     return p;
 }
 
-__global__ __launch_bounds__(256) void loss_dc_kernel(const float* __restrict__ large, const float* __restrict__ small, int B, int H,
+__global__ __launch_bounds__(256) void loss_dc_kernel(const float* __restrict__ large, const float* __restrict__ small, int H,
                                                       int W, int h, int w, float* __restrict__ part) {
     const int lp = blockIdx.x * 256 + threadIdx.x;
     float num = 0.0f, den = 0.0f;
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void loss_dc_kernel(const float* __restrict__ 
         num = rel_diff(p.p, p.s).diff * p.keep;
         den = p.keep;
     }
-    block_partial(num, den, part, B);
+    block_partial({num, den}, part);
 }
 
 // g_large (rows and columns past 4 h, 4 w cleared by the launcher) and g_small may be nullptr
@@ -193,7 +193,7 @@ __device__ __forceinline__ void smooth_pair(const float* __restrict__ d, const f
     wgt = expf(-(((a0 + a1) + a2) / 3.0f));
 }
 
-__global__ __launch_bounds__(256) void loss_smooth_kernel(const float* __restrict__ depth, const float* __restrict__ rgb, int B, int H,
+__global__ __launch_bounds__(256) void loss_smooth_kernel(const float* __restrict__ depth, const float* __restrict__ rgb, int H,
                                                           int W, float* __restrict__ part) {
     const int pix = blockIdx.x * 256 + threadIdx.x;
     const int HW = H * W;
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void loss_smooth_kernel(const float* __restric
             cols = fabsf(diff) * wgt;
         }
     }
-    block_partial(rows, cols, part, B);
+    block_partial({rows, cols}, part);
 }
 
 // each pixel gathers the up-to-four differences it takes part in
@@ -264,7 +264,7 @@ using namespace pdepth::capi;
 extern "C" {
 
 size_t pdepth_loss_terms_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-    return (B > 0 && H > 0 && W > 0 && (long long)H * W <= (1ll << 24)) ? workspace_bytes(B, H, W) : 0;
+    return (B > 0 && H > 0 && W > 0 && (long long)H * W <= (1ll << 24)) ? two_sums_workspace_bytes(B, H, W) : 0;
 }
 
 // depth_stereo_consistency_loss per item (losses/loss_blocks.py:147-171; transform_dmap utils/inverse_warp.py:212-253)
@@ -275,11 +275,11 @@ int pdepth_loss_dsc_f32(const float* src_depth, const float* tgt_depth, const fl
     if (!src_depth || !tgt_depth || !src_mask || !Kinv || !proj || !pose_row || !intr) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     if (!value || !count) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
     if (int rc = check_map(who, B, H, W, 2)) return rc;
-    if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, H, W))) return rc;
+    if (int rc = check_workspace(who, workspace, workspace_bytes_given, two_sums_workspace_bytes(B, H, W))) return rc;
     const DscArgs a{src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, pose_batched ? 4 : 0, H, W};
     const int nblk = n_blocks(H, W);
     float* part = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(loss_dsc_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, a, B, part);
+    hipLaunchKernelGGL(loss_dsc_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, a, part);
     return launched(finish<true>(part, B, nblk, 1.0f, 0.0f, value, count, (hipStream_t)stream), who);
 }
 
@@ -310,11 +310,11 @@ int pdepth_loss_rsc_f32(const float* src_rgb, const float* tgt_rgb, const float*
     if (!src_rgb || !tgt_rgb || !tgt_depth || !Kinv || !proj) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     if (!value || !count) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
     if (int rc = check_map(who, B, H, W, 2)) return rc;
-    if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, H, W))) return rc;
+    if (int rc = check_workspace(who, workspace, workspace_bytes_given, two_sums_workspace_bytes(B, H, W))) return rc;
     const RscArgs a{src_rgb, tgt_rgb, tgt_depth, Kinv, proj, H, W};
     const int nblk = n_blocks(H, W);
     float* part = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(loss_rsc_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, a, B, part);
+    hipLaunchKernelGGL(loss_rsc_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, a, part);
     return launched(finish<true>(part, B, nblk, 3.0f, 0.0f, value, count, (hipStream_t)stream), who);
 }
 
@@ -338,10 +338,10 @@ int pdepth_loss_dc_f32(const float* large, const float* small, int32_t B, int32_
     if (!value || !count) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
     if (int rc = check_map(who, B, H, W, 4)) return rc;
     const int h = H / 4, w = W / 4;
-    if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, h, w))) return rc;
+    if (int rc = check_workspace(who, workspace, workspace_bytes_given, two_sums_workspace_bytes(B, h, w))) return rc;
     const int nblk = n_blocks(h, w);
     float* part = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(loss_dc_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, large, small, B, H, W, h, w, part);
+    hipLaunchKernelGGL(loss_dc_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, large, small, H, W, h, w, part);
     return launched(finish<true>(part, B, nblk, 1.0f, 0.0f, value, count, (hipStream_t)stream), who);
 }
 
@@ -368,10 +368,10 @@ int pdepth_loss_smooth_f32(const float* depth, const float* rgb, int32_t B, int3
     if (!depth || !rgb) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
     if (!value) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
     if (int rc = check_map(who, B, H, W, 2)) return rc;
-    if (int rc = check_workspace(who, workspace, workspace_bytes_given, workspace_bytes(B, H, W))) return rc;
+    if (int rc = check_workspace(who, workspace, workspace_bytes_given, two_sums_workspace_bytes(B, H, W))) return rc;
     const int nblk = n_blocks(H, W);
     float* part = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(loss_smooth_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, depth, rgb, B, H, W, part);
+    hipLaunchKernelGGL(loss_smooth_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, depth, rgb, H, W, part);
     return launched(finish<false>(part, B, nblk, (float)((H - 1) * W), (float)(H * (W - 1)), value, nullptr, (hipStream_t)stream), who);
 }
 

@@ -13,12 +13,13 @@
 //
 // Every piece of arithmetic is a shared header's: the sample position, `valid`, the taps, the bilinear value and its derivatives
 // (inverse_warp_math.hpp) through the per-pixel chain of the rsc term (loss_terms_math.hpp: rsc_sample, rsc_channel, rsc_pixel,
-// rsc_depth_grad), the window sums in ATen's order, the window chain and its coefficients (ssim_math.hpp).  So the mask has the
-// bits of pdepth_inverse_warp_f32's `valid`, a window the bits it has in ssim.hip on the same x and y, and the backward's clamp
-// decision is the forward's.  The products with the mask stay products: a NaN behind a zero mask makes its item NaN, as in the
-// composition; an empty mask is 0 / 0 = NaN for its item alone.
+// rsc_depth_grad), the window sums in ATen's order, the window chain and its coefficients (ssim_math.hpp); and so is every walk
+// over the tile: the window of a pixel, the coefficient planes and the gather (window_tile.hpp), the sums (loss_terms_sum.hpp).
+// So the mask has the bits of pdepth_inverse_warp_f32's `valid`, a window the bits it has in ssim.hip on the same x and y, and
+// the backward's clamp decision is the forward's.  The products with the mask stay products: a NaN behind a zero mask makes its
+// item NaN, as in the composition; an empty mask is 0 / 0 = NaN for its item alone.
 //
-// Tile.  A workgroup of 256 threads owns 64 x 16 pixels of one item (blockIdx.z), lanes along W, as ssim.hip.
+// Tile.  A workgroup of 256 threads owns 64 x 16 pixels of one item (blockIdx.z), lanes along W (window_tile.hpp).
 //   forward   evaluates the chain for its pixels and a halo of md on every side ((64 + 2 md)(16 + 2 md) pixels, zeros outside the
 //             image) and stages x and y, three channels each, in LDS; the thread that evaluates a pixel of the tile adds its L1
 //             numerator and its m, and every thread adds the SSIM distance of the windows centred on its 4 pixels (one column,
@@ -28,8 +29,8 @@
 //   backward  one channel at a time (three channels of the (64 + 4 md)(16 + 4 md) staged pixels and their coefficients do not fit
 //             the 64 KiB of static LDS at md = 3): stage x_c, y_c; phase 1 writes G P, G Q, G R of the (64 + 2 md)(16 + 2 md)
 //             windows that touch the tile (zeros for windows that do not exist; P' is not needed, only x carries a gradient);
-//             phase 2 gathers per pixel the (2 md + 1)^2 windows that contain it, rows top to bottom, left to right, as
-//             ssim_bwd_kernel.  Behind the three channels each pixel forms
+//             phase 2 gathers per pixel the (2 md + 1)^2 windows that contain it, rows top to bottom, left to right
+//             (ssim_tile_coef, ssim_tile_gather).  Behind the three channels each pixel forms
 //                 g_warped_c = -(1 - w) g / (3 count) sign0(d_c) m  +  m sum_{windows containing p} (G P + G Q x_p + G R y_p) / n
 //             with G = -1/2 g w / (n_w count / (H W)) on the windows that pass the clamp (inclusive rule), and from it the
 //             gradient of the depth exactly as loss_rsc_bwd_kernel does.  A gather in a fixed order: two calls give the same bits.
@@ -43,27 +44,24 @@
 #include "inverse_warp_math.hpp"
 #include "kernels.hpp"
 #include "loss_terms_math.hpp"
-#include "ssim_math.hpp"
+#include "loss_terms_sum.hpp"
+#include "window_tile.hpp"
 
 namespace pdepth {
 
 namespace {
 
-constexpr int PHOTO_TW = 64;   // tile width: one wave row
 constexpr int PHOTO_TH = 16;   // tile height
-constexpr int PHOTO_R = 4;     // rows of the tile per thread (256 threads = 64 columns x 4 strips)
 
 template <int MD>
-__global__ __launch_bounds__(256) void photo_fwd_kernel(RscArgs g, int B, float* __restrict__ part) {
-    constexpr int K = 2 * MD + 1, LW = PHOTO_TW + 2 * MD, LH = PHOTO_TH + 2 * MD;
+__global__ __launch_bounds__(256) void photo_fwd_kernel(RscArgs g, float* __restrict__ part) {
+    using T = WindowTile<MD, PHOTO_TH>;
+    constexpr int LW = T::LW, LH = T::LH;
     __shared__ float sx[3][LH * LW];
     __shared__ float sy[3][LH * LW];
-    __shared__ float s0[4];
-    __shared__ float s1[4];
-    __shared__ float s2[4];
     const int H = g.H, W = g.W;
     const int b = blockIdx.z;
-    const int x0 = blockIdx.x * PHOTO_TW, y0 = blockIdx.y * PHOTO_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * PHOTO_TH;
     float num = 0.0f, den = 0.0f, dist = 0.0f;
     for (int i = threadIdx.x; i < LH * LW; i += 256) {
         const int r = i / LW, c = i - r * LW;
@@ -76,7 +74,7 @@ __global__ __launch_bounds__(256) void photo_fwd_kernel(RscArgs g, int B, float*
                 vx[ch] = p.x[ch];
                 vy[ch] = p.y[ch];
             }
-            if (r >= MD && r < MD + PHOTO_TH && c >= MD && c < MD + PHOTO_TW) {   // a pixel of the tile itself
+            if (r >= MD && r < MD + PHOTO_TH && c >= MD && c < MD + TILE_W) {   // a pixel of the tile itself
                 num += (fabsf(p.d[0]) * p.m + fabsf(p.d[1]) * p.m) + fabsf(p.d[2]) * p.m;
                 den += p.m;
             }
@@ -88,80 +86,53 @@ __global__ __launch_bounds__(256) void photo_fwd_kernel(RscArgs g, int B, float*
         }
     }
     __syncthreads();
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int px = x0 + tx;
 #pragma unroll
-    for (int k = 0; k < PHOTO_R; ++k) {
-        const int ly = ty * PHOTO_R + k;
+    for (int k = 0; k < T::R; ++k) {
+        const int ly = ty * T::R + k;
         const int py = y0 + ly;
         if (px >= MD && px < W - MD && py >= MD && py < H - MD) {   // the window centred on (px, py): first pixel (ly, tx) of the stage
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const SsimWindow w = ssim_window(ssim_sums<K>(sx[ch] + ly * LW + tx, sy[ch] + ly * LW + tx, LW), (float)(K * K));
-                dist += ssim_clamp01(w.d);
-            }
+            for (int ch = 0; ch < 3; ++ch) dist += ssim_tile_dist<MD>(sx[ch], sy[ch], ly, tx);
         }
     }
-    wg_sum_put(num, s0);
-    wg_sum_put(den, s1);
-    wg_sum_put(dist, s2);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const size_t nblk = (size_t)gridDim.x * gridDim.y;
-        const size_t slot = (size_t)b * nblk + (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        part[slot] = wg_sum_get(s0);
-        part[(size_t)B * nblk + slot] = wg_sum_get(s1);
-        part[(size_t)2 * B * nblk + slot] = wg_sum_get(s2);
-    }
+    block_partial({num, den, dist}, part);
 }
 
-// the three partial sums of an item in a fixed order, in double (as loss_terms_final_kernel):
+// the three partial sums of an item in a fixed order, in double (partial_sums):
 // value = omw t0 / (3 t1) + w (t2 / n_w) / (t1 / hw), count = t1 (0 / 0 = NaN for an empty mask)
 __global__ __launch_bounds__(256) void photo_final_kernel(const float* __restrict__ part, int B, int nblk, float w, float omw, float n_w,
                                                           float hw, float* __restrict__ value, float* __restrict__ count) {
-    __shared__ double sa[4];
-    __shared__ double sb[4];
-    __shared__ double sc[4];
     const int b = blockIdx.x;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-        a0 += (double)part[(size_t)b * nblk + i];
-        a1 += (double)part[((size_t)B + b) * nblk + i];
-        a2 += (double)part[((size_t)2 * B + b) * nblk + i];
-    }
-    wg_sum_put(a0, sa);
-    wg_sum_put(a1, sb);
-    wg_sum_put(a2, sc);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t0 = (float)wg_sum_get(sa), t1 = (float)wg_sum_get(sb), t2 = (float)wg_sum_get(sc);
-        const float l1 = t0 / (3.0f * t1);
-        const float structural = (t2 / n_w) / (t1 / hw);
-        value[b] = omw * l1 + w * structural;
-        count[b] = t1;
-    }
+    float t[3];
+    partial_sums(part, (size_t)B * nblk, (size_t)b * nblk, nblk, t);
+    if (threadIdx.x != 0) return;
+    const float l1 = t[0] / (3.0f * t[1]);
+    const float structural = (t[2] / n_w) / (t[1] / hw);
+    value[b] = omw * l1 + w * structural;
+    count[b] = t[1];
 }
 
 template <int MD>
 __global__ __launch_bounds__(256) void photo_bwd_kernel(RscArgs g, const float* __restrict__ count, const float* __restrict__ g_value,
                                                         float w, float omw, float* __restrict__ g_depth) {
-    constexpr int K = 2 * MD + 1;
-    constexpr int CW = PHOTO_TW + 2 * MD, CH = PHOTO_TH + 2 * MD;   // the windows that touch the tile
-    constexpr int IW = PHOTO_TW + 4 * MD, IH = PHOTO_TH + 4 * MD;   // the pixels those windows read
+    using T = WindowTile<MD, PHOTO_TH>;
+    constexpr int IW = T::IW, IH = T::IH;
     __shared__ float sx[IH * IW];
     __shared__ float sy[IH * IW];
-    __shared__ float cp[CH * CW];
-    __shared__ float cq[CH * CW];
-    __shared__ float cr[CH * CW];
-    __shared__ float gs[3][PHOTO_TH * PHOTO_TW];   // d L / d x_c of the tile's pixels through the SSIM
+    __shared__ float cp[T::LH * T::LW];
+    __shared__ float cq[T::LH * T::LW];
+    __shared__ float cr[T::LH * T::LW];
+    __shared__ float gs[3][PHOTO_TH * TILE_W];   // d L / d x_c of the tile's pixels through the SSIM
     const int H = g.H, W = g.W, HW = H * W;
     const int OH = H - 2 * MD, OW = W - 2 * MD;
     const int b = blockIdx.z;
-    const int x0 = blockIdx.x * PHOTO_TW, y0 = blockIdx.y * PHOTO_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * PHOTO_TH;
     const float cnt = count[b], gv = g_value[b];
     const float g_dist = (gv * w) / ((float)(3 * OH * OW) * (cnt / (float)HW));   // d L / d dist of every window of the item
     const float g_l1 = (omw * gv) / (3.0f * cnt);                                  // d L / d |d_c| m of every pixel
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int px = x0 + tx;
     // (one channel, then one pixel at a time: the unrolled form of the whole holds every load of the gather in registers and spills)
 #pragma unroll 1
@@ -181,38 +152,18 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(RscArgs g, const float* 
             sy[i] = vy;
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < CH * CW; i += 256) {
-            const int wr = i / CW, wc = i - wr * CW;
-            const int wy = y0 - 2 * MD + wr, wx = x0 - 2 * MD + wc;   // the window's first pixel
-            SsimCoef c{0.0f, 0.0f, 0.0f, 0.0f};
-            if (wy >= 0 && wy < OH && wx >= 0 && wx < OW)
-                c = ssim_coef(ssim_window(ssim_sums<K>(sx + wr * IW + wc, sy + wr * IW + wc, IW), (float)(K * K)), g_dist);
-            cp[i] = c.p;
-            cq[i] = c.q;
-            cr[i] = c.r;
-        }
+        ssim_tile_coef<MD, PHOTO_TH, false>(sx, sy, x0, y0, OH, OW, [=](int, int) { return g_dist; }, cp, nullptr, cq, cr);
         __syncthreads();
 #pragma unroll 1
-        for (int k = 0; k < PHOTO_R; ++k) {
-            const int ly = ty * PHOTO_R + k;
-            const float xp = sx[(ly + 2 * MD) * IW + tx + 2 * MD];
-            const float yp = sy[(ly + 2 * MD) * IW + tx + 2 * MD];
-            float ax = 0.0f;
-#pragma unroll
-            for (int dy = K - 1; dy >= 0; --dy) {       // the window dy rows above the pixel, dx columns left of it:
-#pragma unroll
-                for (int dx = K - 1; dx >= 0; --dx) {   // top to bottom, left to right
-                    const int ci = (ly + 2 * MD - dy) * CW + (tx + 2 * MD - dx);
-                    ax += (cp[ci] + cq[ci] * xp) + cr[ci] * yp;
-                }
-            }
-            gs[ch][ly * PHOTO_TW + tx] = ax / (float)(K * K);   // read back by this thread alone
+        for (int k = 0; k < T::R; ++k) {
+            const int ly = ty * T::R + k;
+            gs[ch][ly * TILE_W + tx] = ssim_tile_gather<MD, false>(sx, sy, cp, nullptr, cq, cr, ly, tx).x;   // read back by this thread alone
         }
     }
     // the position gradient and the products behind it, as loss_rsc_bwd_kernel forms them
 #pragma unroll 1
-    for (int k = 0; k < PHOTO_R; ++k) {
-        const int ly = ty * PHOTO_R + k;
+    for (int k = 0; k < T::R; ++k) {
+        const int ly = ty * T::R + k;
         const int py = y0 + ly;
         if (px >= W || py >= H) continue;
         const int pix = py * W + px;
@@ -221,7 +172,7 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(RscArgs g, const float* 
         float gix = 0.0f, giy = 0.0f;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            const float gw = -(gd * sign0(p.d[ch])) * p.m + p.m * gs[ch][ly * PHOTO_TW + tx];
+            const float gw = -(gd * sign0(p.d[ch])) * p.m + p.m * gs[ch][ly * TILE_W + tx];
             gix = __builtin_fmaf(gw, p.gx[ch], gix);
             giy = __builtin_fmaf(gw, p.gy[ch], giy);
         }
@@ -229,21 +180,20 @@ __global__ __launch_bounds__(256) void photo_bwd_kernel(RscArgs g, const float* 
     }
 }
 
-inline int tiles(int n, int tile) { return (n + tile - 1) / tile; }
-inline int n_tiles(int H, int W) { return tiles(W, PHOTO_TW) * tiles(H, PHOTO_TH); }
+inline int n_tiles(int H, int W) { return tiles(W, TILE_W) * tiles(H, PHOTO_TH); }
 
-size_t workspace_bytes(int B, int H, int W) { return ((size_t)3 * B * n_tiles(H, W) * sizeof(float) + 255) / 256 * 256; }
+size_t workspace_bytes(int B, int H, int W) { return partial_sums_bytes(3, (size_t)B * n_tiles(H, W)); }
 
 template <int MD>
 void launch_fwd(const RscArgs& a, int B, float* part, hipStream_t stream) {
-    const dim3 grid(tiles(a.W, PHOTO_TW), tiles(a.H, PHOTO_TH), B);
-    hipLaunchKernelGGL(photo_fwd_kernel<MD>, grid, dim3(256), 0, stream, a, B, part);
+    const dim3 grid(tiles(a.W, TILE_W), tiles(a.H, PHOTO_TH), B);
+    hipLaunchKernelGGL(photo_fwd_kernel<MD>, grid, dim3(256), 0, stream, a, part);
 }
 
 template <int MD>
 void launch_bwd(const RscArgs& a, int B, const float* count, const float* g_value, float w, float omw, float* g_depth,
                 hipStream_t stream) {
-    const dim3 grid(tiles(a.W, PHOTO_TW), tiles(a.H, PHOTO_TH), B);
+    const dim3 grid(tiles(a.W, TILE_W), tiles(a.H, PHOTO_TH), B);
     hipLaunchKernelGGL(photo_bwd_kernel<MD>, grid, dim3(256), 0, stream, a, count, g_value, w, omw, g_depth);
 }
 
@@ -261,9 +211,7 @@ using namespace pdepth::capi;
 // B, H, W, md of both entries: a map of check_map's sizes, md in 1..3, at least one window, a tile row per grid y
 int check_photo(const char* who, int32_t B, int32_t H, int32_t W, int32_t md) {
     if (int rc = check_map(who, B, H, W, 1)) return rc;
-    if (md < 1 || md > 3) return fail(PDEPTH_E_ARG, "%s: md=%d: the window is (2 md + 1)^2 with md = 1, 2 or 3", who, md);
-    if (H < 2 * md + 1 || W < 2 * md + 1)
-        return fail(PDEPTH_E_ARG, "%s: H=%d, W=%d: md=%d needs H and W of at least %d", who, H, W, md, 2 * md + 1);
+    if (int rc = check_window(who, "window", H, W, md)) return rc;
     if (H > 65535 * PHOTO_TH) return fail(PDEPTH_E_ARG, "%s: H must be at most %d", who, 65535 * PHOTO_TH);
     return PDEPTH_OK;
 }
@@ -292,9 +240,7 @@ int pdepth_loss_photo_f32(const float* src_rgb, const float* tgt_rgb, const floa
     const RscArgs a{src_rgb, tgt_rgb, tgt_depth, Kinv, proj, H, W};
     float* part = static_cast<float*>(workspace);
     hipStream_t s = (hipStream_t)stream;
-    if (md == 1) launch_fwd<1>(a, B, part, s);
-    else if (md == 2) launch_fwd<2>(a, B, part, s);
-    else launch_fwd<3>(a, B, part, s);
+    for_md(md, [&](auto m) { launch_fwd<decltype(m)::value>(a, B, part, s); });
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return launched(err, who);
     const float n_w = (float)(3 * (H - 2 * md) * (W - 2 * md));
@@ -313,9 +259,7 @@ int pdepth_loss_photo_backward_f32(const float* src_rgb, const float* tgt_rgb, c
     const RscArgs a{src_rgb, tgt_rgb, tgt_depth, Kinv, proj, H, W};
     const float w = weight_of(ssim_weight), omw = rest_of(ssim_weight);
     hipStream_t s = (hipStream_t)stream;
-    if (md == 1) launch_bwd<1>(a, B, count, g_value, w, omw, g_tgt_depth, s);
-    else if (md == 2) launch_bwd<2>(a, B, count, g_value, w, omw, g_tgt_depth, s);
-    else launch_bwd<3>(a, B, count, g_value, w, omw, g_tgt_depth, s);
+    for_md(md, [&](auto m) { launch_bwd<decltype(m)::value>(a, B, count, g_value, w, omw, g_tgt_depth, s); });
     return launched(hipGetLastError(), who);
 }
 

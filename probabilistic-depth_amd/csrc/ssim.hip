@@ -15,6 +15,8 @@
 //   backward  phase 1 writes G P, G P', G Q, G R of the (64 + 2 md) x (16 + 2 md) windows that touch the tile into LDS (zeros for the
 //             windows that do not exist); phase 2 gathers, per pixel, the (2 md + 1)^2 windows that contain it, rows top to bottom,
 //             left to right.  A gather in a fixed order, no atomics: two calls give the same bits.
+// The tile's geometry, the window of a tile pixel and both phases of the backward are window_tile.hpp's, where photo.hip and
+// flow_photo.hip take them too; what is this file's own is the staging of two planes and the upstream gradient per window.
 // The halo is read again by the neighbouring workgroups (from L2): (64 + 2 md)(16 + 2 md) / 1024 = 1.16 / 1.33 / 1.50 times the
 // plane for the forward, 1.33 / 1.69 / 2.09 times for the backward.
 //
@@ -24,15 +26,13 @@
 
 #include "capi_util.hpp"
 #include "kernels.hpp"
-#include "ssim_math.hpp"
+#include "window_tile.hpp"
 
 namespace pdepth {
 
 namespace {
 
-constexpr int SSIM_TW = 64;   // tile width: one wave row
 constexpr int SSIM_TH = 16;   // tile height
-constexpr int SSIM_R = 4;     // rows of the tile per thread (256 threads = 64 columns x 4 strips)
 
 // rows x cols floats of x and y from (gy0, gx0) of a plane into LDS; zeros outside the plane
 __device__ __forceinline__ void ssim_stage(const float* __restrict__ x, const float* __restrict__ y, int H, int W, int gy0, int gx0,
@@ -51,23 +51,23 @@ __device__ __forceinline__ void ssim_stage(const float* __restrict__ x, const fl
 template <int MD>
 __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int H, int W,
                                                        float* __restrict__ out) {
-    constexpr int K = 2 * MD + 1, LW = SSIM_TW + 2 * MD, LH = SSIM_TH + 2 * MD;
-    __shared__ float sx[LH * LW];
-    __shared__ float sy[LH * LW];
+    using T = WindowTile<MD, SSIM_TH>;
+    __shared__ float sx[T::LH * T::LW];
+    __shared__ float sy[T::LH * T::LW];
     const int OH = H - 2 * MD, OW = W - 2 * MD;
-    const int x0 = blockIdx.x * SSIM_TW, y0 = blockIdx.y * SSIM_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * SSIM_TH;
     const size_t plane = (size_t)blockIdx.z * H * W;
-    ssim_stage(x + plane, y + plane, H, W, y0, x0, LH, LW, sx, sy);
+    ssim_stage(x + plane, y + plane, H, W, y0, x0, T::LH, T::LW, sx, sy);
     __syncthreads();
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int ox = x0 + tx;
     float* o = out + (size_t)blockIdx.z * OH * OW;
 #pragma unroll
-    for (int k = 0; k < SSIM_R; ++k) {
-        const int ly = ty * SSIM_R + k;
-        const SsimWindow w = ssim_window(ssim_sums<K>(sx + ly * LW + tx, sy + ly * LW + tx, LW), (float)(K * K));
+    for (int k = 0; k < T::R; ++k) {
+        const int ly = ty * T::R + k;
+        const float d = ssim_tile_dist<MD>(sx, sy, ly, tx);
         const int oy = y0 + ly;
-        if (ox < OW && oy < OH) o[(size_t)oy * OW + ox] = ssim_clamp01(w.d);
+        if (ox < OW && oy < OH) o[(size_t)oy * OW + ox] = d;
     }
 }
 
@@ -76,73 +76,45 @@ template <int MD>
 __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                        const float* __restrict__ g_out, int H, int W, float* __restrict__ g_x,
                                                        float* __restrict__ g_y) {
-    constexpr int K = 2 * MD + 1;
-    constexpr int CW = SSIM_TW + 2 * MD, CH = SSIM_TH + 2 * MD;   // the windows that touch the tile
-    constexpr int IW = SSIM_TW + 4 * MD, IH = SSIM_TH + 4 * MD;   // the pixels those windows read
-    __shared__ float sx[IH * IW];
-    __shared__ float sy[IH * IW];
-    __shared__ float cp[CH * CW];
-    __shared__ float cpp[CH * CW];
-    __shared__ float cq[CH * CW];
-    __shared__ float cr[CH * CW];
+    using T = WindowTile<MD, SSIM_TH>;
+    __shared__ float sx[T::IH * T::IW];
+    __shared__ float sy[T::IH * T::IW];
+    __shared__ float cp[T::LH * T::LW];
+    __shared__ float cpp[T::LH * T::LW];
+    __shared__ float cq[T::LH * T::LW];
+    __shared__ float cr[T::LH * T::LW];
     const int OH = H - 2 * MD, OW = W - 2 * MD;
-    const int x0 = blockIdx.x * SSIM_TW, y0 = blockIdx.y * SSIM_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * SSIM_TH;
     const size_t plane = (size_t)blockIdx.z * H * W;
-    ssim_stage(x + plane, y + plane, H, W, y0 - 2 * MD, x0 - 2 * MD, IH, IW, sx, sy);
+    ssim_stage(x + plane, y + plane, H, W, y0 - 2 * MD, x0 - 2 * MD, T::IH, T::IW, sx, sy);
     __syncthreads();
     const float* go = g_out + (size_t)blockIdx.z * OH * OW;
-    for (int i = threadIdx.x; i < CH * CW; i += 256) {
-        const int wr = i / CW, wc = i - wr * CW;
-        const int wy = y0 - 2 * MD + wr, wx = x0 - 2 * MD + wc;   // the window's first pixel = its index in the output
-        SsimCoef c{0.0f, 0.0f, 0.0f, 0.0f};
-        if (wy >= 0 && wy < OH && wx >= 0 && wx < OW) {
-            const SsimSums t = ssim_sums<K>(sx + wr * IW + wc, sy + wr * IW + wc, IW);
-            c = ssim_coef(ssim_window(t, (float)(K * K)), go[(size_t)wy * OW + wx]);
-        }
-        cp[i] = c.p;
-        cpp[i] = c.pp;
-        cq[i] = c.q;
-        cr[i] = c.r;
-    }
+    ssim_tile_coef<MD, SSIM_TH, true>(sx, sy, x0, y0, OH, OW, [=](int wy, int wx) { return go[(size_t)wy * OW + wx]; }, cp, cpp, cq, cr);
     __syncthreads();
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int px = x0 + tx;
 #pragma unroll
-    for (int k = 0; k < SSIM_R; ++k) {
-        const int ly = ty * SSIM_R + k;
+    for (int k = 0; k < T::R; ++k) {
+        const int ly = ty * T::R + k;
         const int py = y0 + ly;
-        const float xp = sx[(ly + 2 * MD) * IW + tx + 2 * MD];
-        const float yp = sy[(ly + 2 * MD) * IW + tx + 2 * MD];
-        float ax = 0.0f, ay = 0.0f;
-#pragma unroll
-        for (int dy = K - 1; dy >= 0; --dy) {       // the window dy rows above the pixel, dx columns left of it:
-#pragma unroll
-            for (int dx = K - 1; dx >= 0; --dx) {   // top to bottom, left to right
-                const int ci = (ly + 2 * MD - dy) * CW + (tx + 2 * MD - dx);
-                const float p = cp[ci], pp = cpp[ci], q = cq[ci], r = cr[ci];
-                ax += (p + q * xp) + r * yp;
-                ay += (pp + q * yp) + r * xp;
-            }
-        }
+        const SsimGrad g = ssim_tile_gather<MD, true>(sx, sy, cp, cpp, cq, cr, ly, tx);
         if (px < W && py < H) {
             const size_t at = plane + (size_t)py * W + px;
-            if (g_x) g_x[at] = ax / (float)(K * K);
-            if (g_y) g_y[at] = ay / (float)(K * K);
+            if (g_x) g_x[at] = g.x;
+            if (g_y) g_y[at] = g.y;
         }
     }
 }
 
-inline unsigned tiles(int n, int tile) { return (unsigned)((n + tile - 1) / tile); }
-
 template <int MD>
 void launch_fwd(const float* x, const float* y, int BC, int H, int W, float* out, hipStream_t stream) {
-    const dim3 grid(tiles(W - 2 * MD, SSIM_TW), tiles(H - 2 * MD, SSIM_TH), BC);
+    const dim3 grid(tiles(W - 2 * MD, TILE_W), tiles(H - 2 * MD, SSIM_TH), BC);
     hipLaunchKernelGGL(ssim_fwd_kernel<MD>, grid, dim3(256), 0, stream, x, y, H, W, out);
 }
 
 template <int MD>
 void launch_bwd(const float* x, const float* y, const float* g_out, int BC, int H, int W, float* g_x, float* g_y, hipStream_t stream) {
-    const dim3 grid(tiles(W, SSIM_TW), tiles(H, SSIM_TH), BC);
+    const dim3 grid(tiles(W, TILE_W), tiles(H, SSIM_TH), BC);
     hipLaunchKernelGGL(ssim_bwd_kernel<MD>, grid, dim3(256), 0, stream, x, y, g_out, H, W, g_x, g_y);
 }
 
@@ -160,9 +132,7 @@ using namespace pdepth::capi;
 // B, C, H, W, md of both entries: positive, md in 1..3, at least one window, one plane per grid z, a plane's offsets in an int
 int check_ssim(const char* who, int32_t B, int32_t C, int32_t H, int32_t W, int32_t md) {
     if (int rc = check_dims(who, B, C, H, W)) return rc;
-    if (md < 1 || md > 3) return fail(PDEPTH_E_ARG, "%s: md=%d: the window is (2 md + 1)^2 with md = 1, 2 or 3", who, md);
-    if (H < 2 * md + 1 || W < 2 * md + 1)
-        return fail(PDEPTH_E_ARG, "%s: H=%d, W=%d: md=%d needs H and W of at least %d", who, H, W, md, 2 * md + 1);
+    if (int rc = check_window(who, "window", H, W, md)) return rc;
     if ((long long)B * C > 65535 || (long long)H * W > (1ll << 30) || H > 65535 * SSIM_TH)
         return fail(PDEPTH_E_ARG, "%s: B*C must be at most 65535, H*W at most 2^30 and H at most %d", who, 65535 * SSIM_TH);
     return PDEPTH_OK;
@@ -178,9 +148,7 @@ int pdepth_ssim_f32(const float* x, const float* y, int32_t B, int32_t C, int32_
     if (!out) return fail(PDEPTH_E_ARG, "%s: null output pointer", who);
     if (int rc = check_ssim(who, B, C, H, W, md)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (md == 1) launch_fwd<1>(x, y, B * C, H, W, out, s);
-    else if (md == 2) launch_fwd<2>(x, y, B * C, H, W, out, s);
-    else launch_fwd<3>(x, y, B * C, H, W, out, s);
+    for_md(md, [&](auto m) { launch_fwd<decltype(m)::value>(x, y, B * C, H, W, out, s); });
     return launched(hipGetLastError(), who);
 }
 
@@ -194,9 +162,7 @@ int pdepth_ssim_backward_f32(const float* x, const float* y, const float* g_out,
         (const float*)g_y == y || (const float*)g_y == g_out)
         return fail(PDEPTH_E_ARG, "%s: the outputs may not alias each other or an input", who);
     hipStream_t s = (hipStream_t)stream;
-    if (md == 1) launch_bwd<1>(x, y, g_out, B * C, H, W, g_x, g_y, s);
-    else if (md == 2) launch_bwd<2>(x, y, g_out, B * C, H, W, g_x, g_y, s);
-    else launch_bwd<3>(x, y, g_out, B * C, H, W, g_x, g_y, s);
+    for_md(md, [&](auto m) { launch_bwd<decltype(m)::value>(x, y, g_out, B * C, H, W, g_x, g_y, s); });
     return launched(hipGetLastError(), who);
 }
 

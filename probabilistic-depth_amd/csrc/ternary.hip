@@ -21,22 +21,23 @@
 //                 g_I(p) = -sum_o (G(p) + G(p+o)) D(p, p+o)
 //             one chain per offset, not two, in a fixed order: no atomics, two calls give the same bits.  Outside the image G is 0,
 //             and so is G(p) of any p that has a neighbour there.  g_x = g_I 255 (0.2989, 0.5870, 0.1140), likewise g_y.
+// The sum and the gather over a patch are window_tile.hpp's (census_tile_sum, census_tile_gather), where flow_photo.hip takes them
+// too; what is this file's own is the staging of the gray planes and of G, and how many rows of a patch the backward unrolls.
 //
 // Bytes per pixel (H W large against md): forward 12 + 12 read, 4 written; backward 12 + 12 + 4 read, 12 + 12 written.
 #include <hip/hip_runtime.h>
 
 #include "capi_util.hpp"
 #include "kernels.hpp"
-#include "ternary_math.hpp"
+#include "window_tile.hpp"
 
 namespace pdepth {
 
 namespace {
 
-constexpr int TERN_TW = 64;   // tile width: one wave row
+constexpr int TERN_TW = 64;   // tile width, for tests/util_ternary.py, which reads this line and the next to lay out its shapes
 constexpr int TERN_TH = 8;    // tile height
-constexpr int TERN_R = 2;     // rows of the tile per thread (256 threads = 64 columns x 4 strips)
-static_assert(TERN_TW * TERN_TH == 256 * TERN_R, "a thread per column and strip");
+static_assert(TERN_TW == TILE_W, "the census tile is window_tile.hpp's");
 
 // rows x cols texels of I and I' from (gy0, gx0) of an item into LDS; zeros outside the image (the reference's zero padding)
 __device__ __forceinline__ void ternary_stage(const float* __restrict__ x, const float* __restrict__ y, int H, int W, int gy0, int gx0,
@@ -57,30 +58,21 @@ __device__ __forceinline__ void ternary_stage(const float* __restrict__ x, const
 template <int MD>
 __global__ __launch_bounds__(256) void ternary_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, int H, int W,
                                                           float* __restrict__ out) {
-    constexpr int K = 2 * MD + 1, LW = TERN_TW + 2 * MD, LH = TERN_TH + 2 * MD;
+    using T = WindowTile<MD, TERN_TH>;
+    constexpr int K = T::K, LW = T::LW, LH = T::LH;
     __shared__ float sa[LH * LW];
     __shared__ float sb[LH * LW];
-    const int x0 = blockIdx.x * TERN_TW, y0 = blockIdx.y * TERN_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * TERN_TH;
     const size_t hw = (size_t)H * W, item = (size_t)blockIdx.z * 3 * hw;
     ternary_stage(x + item, y + item, H, W, y0 - MD, x0 - MD, LH, LW, sa, sb);
     __syncthreads();
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int px = x0 + tx;
 #pragma unroll
-    for (int k = 0; k < TERN_R; ++k) {
-        const int ly = ty * TERN_R + k;
+    for (int k = 0; k < T::R; ++k) {
+        const int ly = ty * T::R + k;
         const int py = y0 + ly;
-        const float c = sa[(ly + MD) * LW + tx + MD], cp = sb[(ly + MD) * LW + tx + MD];
-        float sum = 0.0f;
-#pragma unroll
-        for (int dy = 0; dy < K; ++dy) {
-#pragma unroll
-            for (int dx = 0; dx < K; ++dx) {
-                if (dy == MD && dx == MD) continue;
-                const int q = (ly + dy) * LW + tx + dx;
-                sum += ternary_h(sa[q] - c, sb[q] - cp);
-            }
-        }
+        const float sum = census_tile_sum<MD>(sa, sb, LW, ly, tx);
         const bool inner = px >= MD && px < W - MD && py >= MD && py < H - MD;
         if (px < W && py < H) out[(size_t)blockIdx.z * hw + (size_t)py * W + px] = inner ? sum / (float)(K * K) : 0.0f;
     }
@@ -91,11 +83,12 @@ template <int MD>
 __global__ __launch_bounds__(256, 2) void ternary_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                           const float* __restrict__ g_out, int H, int W, float* __restrict__ g_x,
                                                           float* __restrict__ g_y) {
-    constexpr int K = 2 * MD + 1, LW = TERN_TW + 2 * MD, LH = TERN_TH + 2 * MD;
+    using T = WindowTile<MD, TERN_TH>;
+    constexpr int K = T::K, LW = T::LW, LH = T::LH;
     __shared__ float sa[LH * LW];
     __shared__ float sb[LH * LW];
     __shared__ float sg[LH * LW];
-    const int x0 = blockIdx.x * TERN_TW, y0 = blockIdx.y * TERN_TH;
+    const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * TERN_TH;
     const size_t hw = (size_t)H * W, item = (size_t)blockIdx.z * 3 * hw;
     ternary_stage(x + item, y + item, H, W, y0 - MD, x0 - MD, LH, LW, sa, sb);
     const float* go = g_out + (size_t)blockIdx.z * hw;
@@ -107,33 +100,20 @@ __global__ __launch_bounds__(256, 2) void ternary_bwd_kernel(const float* __rest
         sg[i] = inner ? g / (float)(K * K) : 0.0f;
     }
     __syncthreads();
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const auto [tx, ty] = tile_thread();
     const int px = x0 + tx;
     // one pixel at a time, and at md = 3 one row of offsets at a time: more chains at once do not fit the registers of two waves
     // per SIMD (all 48 of md = 3 spill), and one wave alone issues at half the SIMD's rate
     constexpr int ROWS_AT_ONCE = MD < 3 ? K : 1;
 #pragma unroll 1
-    for (int k = 0; k < TERN_R; ++k) {
-        const int ly = ty * TERN_R + k;
+    for (int k = 0; k < T::R; ++k) {
+        const int ly = ty * T::R + k;
         const int py = y0 + ly;
-        const int p = (ly + MD) * LW + tx + MD;
-        const float c = sa[p], cp = sb[p], gp = sg[p];
-        float ax = 0.0f, ay = 0.0f;
-#pragma unroll ROWS_AT_ONCE
-        for (int dy = 0; dy < K; ++dy) {
-#pragma unroll
-            for (int dx = 0; dx < K; ++dx) {
-                if (dy == MD && dx == MD) continue;
-                const int q = (ly + dy) * LW + tx + dx;
-                const TernaryDeriv d = ternary_deriv(sa[q] - c, sb[q] - cp);
-                const float w = gp + sg[q];
-                ax += w * d.dt;
-                ay += w * d.dtp;
-            }
-        }
+        const float gp = sg[(ly + MD) * LW + tx + MD];
+        const CensusGrad a = census_tile_gather<MD, ROWS_AT_ONCE, true>(sa, sb, LW, ly, tx, [&](int q, int, int) { return gp + sg[q]; });
         if (px < W && py < H) {
             const size_t at = item + (size_t)py * W + px;
-            const float gi = -ax * 255.0f, gip = -ay * 255.0f;
+            const float gi = -a.x * 255.0f, gip = -a.y * 255.0f;
             if (g_x) {
                 g_x[at] = gi * 0.2989f;
                 g_x[at + hw] = gi * 0.5870f;
@@ -148,17 +128,15 @@ __global__ __launch_bounds__(256, 2) void ternary_bwd_kernel(const float* __rest
     }
 }
 
-inline unsigned tiles(int n, int tile) { return (unsigned)((n + tile - 1) / tile); }
-
 template <int MD>
 void launch_fwd(const float* x, const float* y, int B, int H, int W, float* out, hipStream_t stream) {
-    const dim3 grid(tiles(W, TERN_TW), tiles(H, TERN_TH), B);
+    const dim3 grid(tiles(W, TILE_W), tiles(H, TERN_TH), B);
     hipLaunchKernelGGL(ternary_fwd_kernel<MD>, grid, dim3(256), 0, stream, x, y, H, W, out);
 }
 
 template <int MD>
 void launch_bwd(const float* x, const float* y, const float* g_out, int B, int H, int W, float* g_x, float* g_y, hipStream_t stream) {
-    const dim3 grid(tiles(W, TERN_TW), tiles(H, TERN_TH), B);
+    const dim3 grid(tiles(W, TILE_W), tiles(H, TERN_TH), B);
     hipLaunchKernelGGL(ternary_bwd_kernel<MD>, grid, dim3(256), 0, stream, x, y, g_out, H, W, g_x, g_y);
 }
 
@@ -176,9 +154,7 @@ using namespace pdepth::capi;
 // B, H, W, md of both entries: positive, md in 1..3, at least one interior pixel, an item per grid z, a plane's offsets in an int
 int check_ternary(const char* who, int32_t B, int32_t H, int32_t W, int32_t md) {
     if (int rc = check_dims(who, B, 3, H, W)) return rc;
-    if (md < 1 || md > 3) return fail(PDEPTH_E_ARG, "%s: md=%d: the patch is (2 md + 1)^2 with md = 1, 2 or 3", who, md);
-    if (H < 2 * md + 1 || W < 2 * md + 1)
-        return fail(PDEPTH_E_ARG, "%s: H=%d, W=%d: md=%d needs H and W of at least %d", who, H, W, md, 2 * md + 1);
+    if (int rc = check_window(who, "patch", H, W, md)) return rc;
     if (B > 65535 || (long long)H * W > (1ll << 30) || H > 65535 * TERN_TH)
         return fail(PDEPTH_E_ARG, "%s: B must be at most 65535, H*W at most 2^30 and H at most %d", who, 65535 * TERN_TH);
     return PDEPTH_OK;
@@ -195,9 +171,7 @@ int pdepth_ternary_f32(const float* x, const float* y, int32_t B, int32_t H, int
     if (int rc = check_ternary(who, B, H, W, md)) return rc;
     if ((const float*)out == x || (const float*)out == y) return fail(PDEPTH_E_ARG, "%s: the output may not alias an input", who);
     hipStream_t s = (hipStream_t)stream;
-    if (md == 1) launch_fwd<1>(x, y, B, H, W, out, s);
-    else if (md == 2) launch_fwd<2>(x, y, B, H, W, out, s);
-    else launch_fwd<3>(x, y, B, H, W, out, s);
+    for_md(md, [&](auto m) { launch_fwd<decltype(m)::value>(x, y, B, H, W, out, s); });
     return launched(hipGetLastError(), who);
 }
 
@@ -211,9 +185,7 @@ int pdepth_ternary_backward_f32(const float* x, const float* y, const float* g_o
         (const float*)g_y == y || (const float*)g_y == g_out)
         return fail(PDEPTH_E_ARG, "%s: the outputs may not alias each other or an input", who);
     hipStream_t s = (hipStream_t)stream;
-    if (md == 1) launch_bwd<1>(x, y, g_out, B, H, W, g_x, g_y, s);
-    else if (md == 2) launch_bwd<2>(x, y, g_out, B, H, W, g_x, g_y, s);
-    else launch_bwd<3>(x, y, g_out, B, H, W, g_x, g_y, s);
+    for_md(md, [&](auto m) { launch_bwd<decltype(m)::value>(x, y, g_out, B, H, W, g_x, g_y, s); });
     return launched(hipGetLastError(), who);
 }
 
