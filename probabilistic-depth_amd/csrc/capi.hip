@@ -1,4 +1,5 @@
-// C ABI of the hot path (include/pdepth.h): argument validation + kernel dispatch.
+// C ABI of the hot path (include/pdepth.h): argument validation + kernel dispatch of the sweep, pack, reduce, expect, warp_feature,
+// sample_coords, ufield and backward entries, and pdepth_last_error().  Every other op keeps its entries beside its kernels.
 // No torch types, no allocation, no host synchronisation.
 #include <hip/hip_runtime.h>
 
@@ -206,14 +207,6 @@ int pdepth_dpv_expect_f32(const float* dpv, const float* d_candi, int32_t B, int
                                               (hipStream_t)stream), "pdepth_dpv_expect_f32");
 }
 
-int pdepth_dpv_moments_f32(const float* dpv, const float* d_candi, int32_t B, int32_t D, int32_t H,
-                           int32_t W, int32_t bv_log, float* mean, float* variance, void* stream) {
-    if (!dpv || !d_candi || !variance) return fail(PDEPTH_E_ARG, "pdepth_dpv_moments_f32: null pointer");
-    if (int rc = check_dims("pdepth_dpv_moments_f32", B, D, H, W)) return rc;
-    return launched(pdepth::launch_dpv_moments(dpv, d_candi, B, D, H, W, bv_log, mean, variance,
-                                               (hipStream_t)stream), "pdepth_dpv_moments_f32");
-}
-
 int pdepth_warp_feature_f32(const pdepth_sweep_desc* desc, const pdepth_camera* cam, const float* src,
                             const float* d_candi, float* out, void* stream) {
     if (int rc = check_desc(desc, cam, "pdepth_warp_feature_f32")) return rc;
@@ -254,138 +247,6 @@ int pdepth_ufield_f32(const float* dpv, const float* d_candi, const float* intr,
         return fail(PDEPTH_E_WORKSPACE, "%s: needs %zu bytes of workspace (got %zu)", who, need, workspace_bytes);
     return launched(pdepth::launch_ufield(dpv, d_candi, intr, mask, B, D, H, W, bv_log, unc_ang, z_start, z_end, min_depth,
                                           quash, oob_depth, plane, depth_zero, workspace, (hipStream_t)stream), who);
-}
-
-int pdepth_dpv_fuse_f32(const float* logp, const float* dmaps, const float* masks, const float* d_candi,
-                        int32_t B, int32_t D, int32_t H, int32_t W, float var, float eps, float* fused,
-                        float* logfused, void* stream) {
-    if (!logp || !dmaps || !masks || !d_candi) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: null input");
-    if (!fused && !logfused) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: no output requested");
-    if (int rc = check_dims("pdepth_dpv_fuse_f32", B, D, H, W)) return rc;
-    if (int rc = check_launch_limits("pdepth_dpv_fuse_f32", B, H, W)) return rc;   // (B is grid.y, like in the backward)
-    if (!(var > 0.0f)) return fail(PDEPTH_E_ARG, "pdepth_dpv_fuse_f32: var must be positive");
-    return launched(pdepth::launch_dpv_fuse(logp, dmaps, masks, d_candi, B, D, H, W, var, eps, fused, logfused,
-                                            (hipStream_t)stream), "pdepth_dpv_fuse_f32");
-}
-
-}  // extern "C" (reopened below)
-
-namespace {
-// kernel_size odd, strides >= 1, and no index of the reference's kernel outside its padded buffers
-int check_corr(const char* who, int32_t B, int32_t C, int32_t H, int32_t W, int32_t pad, int32_t k, int32_t md, int32_t s1, int32_t s2,
-               int* oH, int* oW) {
-    if (int rc = check_dims(who, B, C, H, W)) return rc;
-    if (pad < 0 || k < 1 || (k & 1) == 0 || md < 0 || s1 < 1 || s2 < 1)
-        return fail(PDEPTH_E_ARG, "%s: bad configuration (pad %d, kernel %d, max_displacement %d, stride1 %d, stride2 %d)", who, pad, k, md, s1, s2);
-    if (md - (md / s2) * s2 - (k - 1) / 2 < 0)
-        return fail(PDEPTH_E_ARG, "%s: kernel_size %d with max_displacement %d / stride2 %d reads outside the padded input in the "
-                    "reference kernel (needs (kernel_size-1)/2 <= max_displacement mod stride2)", who, k, md, s2);
-    if (!pdepth::correlation_output_size(H, W, pad, k, md, s1, oH, oW))
-        return fail(PDEPTH_E_ARG, "%s: empty output (pad %d too small for max_displacement %d, kernel %d)", who, pad, md, k);
-    // (one thread per output / input element in a 1-D grid of 256-thread blocks: below the 2^31 - 1 block limit with room to spare)
-    if ((long long)(2 * (md / s2) + 1) * (2 * (md / s2) + 1) * *oH * *oW * B >= (1ll << 38))
-        return fail(PDEPTH_E_ARG, "%s: output too large for one launch (2^38 elements)", who);
-    if ((long long)B * C * H * W >= (1ll << 38))
-        return fail(PDEPTH_E_ARG, "%s: input too large for one launch (2^38 elements)", who);
-    return PDEPTH_OK;
-}
-bool corr_fast_path(int32_t pad, int32_t k, int32_t md, int32_t s1, int32_t s2) {   // the configuration of pwclite.py:123-125 and kin
-    return k == 1 && s1 == 1 && pad == md && md >= 1 && md % s2 == 0 && md / s2 <= pdepth::correlation_max_radius();
-}
-}  // namespace
-
-extern "C" {
-
-int pdepth_correlation_output_size(int32_t H, int32_t W, int32_t pad_size, int32_t kernel_size, int32_t max_displacement, int32_t stride1,
-                                   int32_t stride2, int32_t* out_channels, int32_t* out_height, int32_t* out_width) {
-    int oH = 0, oW = 0;
-    if (int rc = check_corr("pdepth_correlation_output_size", 1, 1, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oH, &oW))
-        return rc;
-    if (out_channels) *out_channels = (2 * (max_displacement / stride2) + 1) * (2 * (max_displacement / stride2) + 1);
-    if (out_height) *out_height = oH;
-    if (out_width) *out_width = oW;
-    return PDEPTH_OK;
-}
-
-int pdepth_correlation_forward_f32(const float* input1, const float* input2, int32_t B, int32_t C, int32_t H,
-                                   int32_t W, int32_t pad_size, int32_t kernel_size, int32_t max_displacement,
-                                   int32_t stride1, int32_t stride2, int32_t corr_multiply, float* output,
-                                   void* stream) {
-    (void)corr_multiply;
-    const char* who = "pdepth_correlation_forward_f32";
-    if (!input1 || !input2 || !output) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    int oH, oW;
-    if (int rc = check_corr(who, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oH, &oW)) return rc;
-    if (corr_fast_path(pad_size, kernel_size, max_displacement, stride1, stride2) &&
-        pdepth::correlation_forward_fits(max_displacement / stride2, stride2))
-        return launched(pdepth::launch_correlation_forward(input1, input2, B, C, H, W, max_displacement / stride2, stride2,
-                                                           output, (hipStream_t)stream), who);
-    return launched(pdepth::launch_correlation_general_forward(input1, input2, 0, B, C, H, W, pad_size, kernel_size, max_displacement,
-                                                               stride1, stride2, output, (hipStream_t)stream), who);
-}
-
-int pdepth_correlation_backward_f32(const float* input1, const float* input2, const float* grad_output, int32_t B,
-                                    int32_t C, int32_t H, int32_t W, int32_t pad_size, int32_t kernel_size,
-                                    int32_t max_displacement, int32_t stride1, int32_t stride2, int32_t corr_multiply,
-                                    float* grad_input1, float* grad_input2, void* stream) {
-    (void)corr_multiply;
-    const char* who = "pdepth_correlation_backward_f32";
-    if (!input1 || !input2 || !grad_output || (!grad_input1 && !grad_input2)) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    int oH, oW;
-    if (int rc = check_corr(who, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oH, &oW)) return rc;
-    if (corr_fast_path(pad_size, kernel_size, max_displacement, stride1, stride2) &&
-        pdepth::correlation_backward_fits(max_displacement / stride2, stride2))
-        return launched(pdepth::launch_correlation_backward(input1, input2, grad_output, B, C, H, W, max_displacement / stride2,
-                                                            stride2, grad_input1, grad_input2, (hipStream_t)stream), who);
-    return launched(pdepth::launch_correlation_general_backward(input1, input2, grad_output, 0, B, C, H, W, pad_size, kernel_size,
-                                                                max_displacement, stride1, stride2, grad_input1, grad_input2,
-                                                                (hipStream_t)stream), who);
-}
-
-int pdepth_correlation_forward_f16(const void* input1, const void* input2, int32_t B, int32_t C, int32_t H, int32_t W, int32_t pad_size,
-                                   int32_t kernel_size, int32_t max_displacement, int32_t stride1, int32_t stride2,
-                                   int32_t corr_multiply, void* output, void* stream) {
-    (void)corr_multiply;
-    const char* who = "pdepth_correlation_forward_f16";
-    if (!input1 || !input2 || !output) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    int oH, oW;
-    if (int rc = check_corr(who, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oH, &oW)) return rc;
-    return launched(pdepth::launch_correlation_general_forward(input1, input2, 1, B, C, H, W, pad_size, kernel_size, max_displacement,
-                                                               stride1, stride2, output, (hipStream_t)stream), who);
-}
-
-int pdepth_correlation_backward_f16(const void* input1, const void* input2, const void* grad_output, int32_t B, int32_t C, int32_t H,
-                                    int32_t W, int32_t pad_size, int32_t kernel_size, int32_t max_displacement, int32_t stride1,
-                                    int32_t stride2, int32_t corr_multiply, void* grad_input1, void* grad_input2, void* stream) {
-    (void)corr_multiply;
-    const char* who = "pdepth_correlation_backward_f16";
-    if (!input1 || !input2 || !grad_output || (!grad_input1 && !grad_input2)) return fail(PDEPTH_E_ARG, "%s: null pointer", who);
-    int oH, oW;
-    if (int rc = check_corr(who, B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oH, &oW)) return rc;
-    return launched(pdepth::launch_correlation_general_backward(input1, input2, grad_output, 1, B, C, H, W, pad_size, kernel_size,
-                                                                max_displacement, stride1, stride2, grad_input1, grad_input2,
-                                                                (hipStream_t)stream), who);
-}
-
-int pdepth_inverse_warp_f32(const float* img, const float* depth, const float* Kinv, const float* proj, int32_t B,
-                            int32_t C, int32_t H, int32_t W, int32_t mode, float* out, uint8_t* valid, void* stream) {
-    if (!img || !depth || !Kinv || !proj || !out) return fail(PDEPTH_E_ARG, "pdepth_inverse_warp_f32: null pointer");
-    if (B <= 0 || C <= 0 || H <= 1 || W <= 1) return fail(PDEPTH_E_ARG, "pdepth_inverse_warp_f32: bad dimension");
-    if (mode != PDEPTH_SAMPLE_BILINEAR && mode != PDEPTH_SAMPLE_NEAREST) return fail(PDEPTH_E_ARG, "pdepth_inverse_warp_f32: unknown mode %d", mode);
-    return launched(pdepth::launch_inverse_warp(img, depth, Kinv, proj, B, C, H, W, mode, out, valid, (hipStream_t)stream),
-                    "pdepth_inverse_warp_f32");
-}
-
-int pdepth_inverse_warp_backward_f32(const float* img, const float* depth, const float* Kinv, const float* proj,
-                                     const float* grad_out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t mode,
-                                     float* grad_img, float* grad_point, void* stream) {
-    if (!img || !depth || !Kinv || !proj || !grad_out || (!grad_img && !grad_point))
-        return fail(PDEPTH_E_ARG, "pdepth_inverse_warp_backward_f32: null pointer");
-    if (B <= 0 || C <= 0 || H <= 1 || W <= 1) return fail(PDEPTH_E_ARG, "pdepth_inverse_warp_backward_f32: bad dimension");
-    if (mode != PDEPTH_SAMPLE_BILINEAR && mode != PDEPTH_SAMPLE_NEAREST)
-        return fail(PDEPTH_E_ARG, "pdepth_inverse_warp_backward_f32: unknown mode %d", mode);
-    return launched(pdepth::launch_inverse_warp_backward(img, depth, Kinv, proj, grad_out, B, C, H, W, mode, grad_img,
-                                                         grad_point, (hipStream_t)stream), "pdepth_inverse_warp_backward_f32");
 }
 
 // est_swp_volume_v4 backward (warping/homography.py:98-135, :170-198, :80-86), features only

@@ -2,7 +2,7 @@
 // correlation_cuda_kernel.cu:41-114; backward: the gradient of exactly that sum, which :116-300 compute over the padded
 // NHWC repacks), in fp32 and in fp16 I/O with fp32 accumulation (the reference dispatches AT_DISPATCH_FLOATING_TYPES_AND_HALF,
 // .cu:352-369).  The configuration the reference instantiates (kernel 1, stride1 1, pad = max_displacement: pwclite.py:123-125)
-// has its own LDS-tiled fp32 kernels in extras.hip, as far as their tiles fit the LDS; this file is the general path.
+// has its own LDS-tiled fp32 kernels in correlation.hip, as far as their tiles fit the LDS; this file is the general path.
 //
 // Index arithmetic, as the reference's, in the coordinates of the zero-padded inputs (pad_size on every side):
 //     kr = (kernel_size - 1) / 2,  dr = max_displacement / stride2,  ds = 2 dr + 1,  border = kr + max_displacement

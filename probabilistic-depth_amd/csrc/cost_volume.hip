@@ -5,7 +5,7 @@
 // outside the image.  The warped image and the pre-activation volume never reach global memory.
 //
 //   forward   block = 16 x 16 output pixels of one item, all (2 md + 1)^2 displacements: 81 accumulators per thread and NO split of
-//             the displacement rows over blocks (extras.hip: correlation_fwd_kernel splits them).  A split stages the x2 tile
+//             the displacement rows over blocks (correlation.hip: correlation_fwd_kernel splits them).  A split stages the x2 tile
 //             once per row of displacements; here a staged texel is a warped texel -- a sample chain in double and four gathers
 //             per channel instead of one load -- and nine times that is the larger price.  The sample of each of the
 //             (16 + 2 md)^2 halo texels (flow_warp_sample.hpp, the chain of flow_warp.hip bit for bit) is formed ONCE, before the
@@ -14,7 +14,7 @@
 //             pixel only).  Sum over c in ascending order in fp32: a chunk's 8 products by one fma each, the chunks' sums added in
 //             turn (a shorter chain of roundings than one fma per channel); times 1 / C, the activation in registers, one store.
 //             A halo texel outside the image is the correlation's zero padding: staged as 0 and multiplied (0 x inf = NaN).
-//   backward  launch 1, the gather of extras.hip: correlation_bwd_kernel (block = 16 x 16 pixels x 8 channels, no atomics) over the
+//   backward  launch 1, the gather of correlation.hip: correlation_bwd_kernel (block = 16 x 16 pixels x 8 channels, no atomics) over the
 //             re-warped x2 halo tile (the same loader) and the x1 halo tile: grad_x1, and g_warp, the gradient of the warped image,
 //             from grad_out x (out > 0 ? 1 : slope) -- the factor is read from the saved output (0, -0 and NaN take the slope).
 //             launch 2: flow_warp's own backward (flow_warp_launch.hpp) with g_warp as its grad_out: grad_x2 by the float-atomic

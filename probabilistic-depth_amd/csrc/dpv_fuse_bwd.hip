@@ -1,4 +1,4 @@
-// Backward of the DPV Bayesian fusion (extras.hip: dpv_fuse) with respect to the incoming log-DPV -- what autograd does behind
+// Backward of the DPV Bayesian fusion (dpv_fuse.hip) with respect to the incoming log-DPV -- what autograd does behind
 // models/models.py:666-672 for BV_cur; the depth map, the mask and the candidates are data.
 //
 // Per pixel, x_k the incoming log-DPV (not necessarily normalised):

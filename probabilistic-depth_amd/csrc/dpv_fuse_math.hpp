@@ -1,4 +1,4 @@
-// exp / log / divide of the DPV fusion kernels (extras.hip: forward; dpv_fuse_bwd.hip: backward).  Both include this header, so
+// exp / log / divide of the DPV fusion kernels (dpv_fuse.hip: forward; dpv_fuse_bwd.hip: backward).  Both include this header, so
 // the backward recomputes the forward's values bit for bit and decides the clamp on the number the forward clamped.
 // That claim is tested on every pair of forward and backward kernels (tests/test_fuse_gpu.py: test_forward_and_backward_agree_on_q,
 // test_forward_and_backward_agree_on_the_clamp).

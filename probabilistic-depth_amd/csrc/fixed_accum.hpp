@@ -1,7 +1,7 @@
 // Order-independent sums of fp32 contributions: exact integer accumulation.  Users: sweep_bwd_det.hip (exponent from a bound, its
 // own policies in sweep_bwd_body.hpp); scatter_det.hip and warp_bwd.hip (exponent from the exact maximum: the sinks,
 // max_exponent_pass and max_exponent_scatter below); occlusion.hip (exponent known before the launch: fixed_exponent_scatter);
-// extras.hip and loss_terms.hip take FloatAtomics for the same scatter bodies.
+// inverse_warp.hip and loss_terms.hip take FloatAtomics for the same scatter bodies.
 //
 // Float addition is not associative, integer addition is.  A contribution q (fp32) is scaled by 2^S (exact: the product is
 // formed in double, whose exponent range holds every fp32 times every 2^S chosen below), rounded to the nearest integer, ties to

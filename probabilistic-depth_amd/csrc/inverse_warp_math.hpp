@@ -1,5 +1,5 @@
 // The per-pixel chain of inverse_warp (utils/inverse_warp.py:174-210: pixel2cam :26-40, cam2pixel :43-69, then the un-normalised
-// sample position of F.grid_sample with align_corners=False), shared by the warp kernels of extras.hip and the loss terms of
+// sample position of F.grid_sample with align_corners=False), shared by the warp kernels of inverse_warp.hip and the loss terms of
 // loss_terms.hip: both see the same bits of position, validity and tap, so a mask formed inside a loss kernel is the mask the
 // warp's `valid` output and its nearest tap would have given.  Every object is built with -ffp-contract=off: the fmas below are
 // the only ones.
@@ -7,7 +7,7 @@
 // Behind the position: the in-bounds taps (TapMask), the masked load of a channel's four texels, their bilinear value and its two
 // derivatives with respect to the position, the gradient of the projected point, and the scatter of an upstream gradient to the
 // taps through a sink (fixed_accum.hpp: FloatAtomics, MaxOfAbs, IntegerSum) -- each once, for the forward and backward kernels of
-// extras.hip, the rsc term of loss_terms.hip, the integer sums of scatter_det.hip and the range map of occlusion.hip.
+// inverse_warp.hip, the rsc term of loss_terms.hip, the integer sums of scatter_det.hip and the range map of occlusion.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

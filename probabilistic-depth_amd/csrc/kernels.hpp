@@ -1,4 +1,4 @@
-// Internal launch interface between the C ABI (capi.hip) and the kernel translation units.
+// Internal launch interface between translation units: what the C ABI of capi.hip launches, and what one kernel file calls of another.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,7 +92,7 @@ hipError_t launch_dpv_reduce_backward(const float* logp, const float* d_candi, i
 hipError_t launch_dpv_expect_backward(const float* dpv, const float* d_candi, int B, int D, int H, int W, int bv_log,
                                       const float* g_depth, float* g_dpv, hipStream_t stream);
 
-// dpv_fuse_bwd.hip: gradient of launch_dpv_fuse (extras.hip) with respect to logp, recomputed from the forward's inputs; g_fused
+// dpv_fuse_bwd.hip: gradient of launch_dpv_fuse (dpv_fuse.hip) with respect to logp, recomputed from the forward's inputs; g_fused
 // (into fused) / g_logfused (into logfused) may be nullptr, not both
 hipError_t launch_dpv_fuse_backward(const float* logp, const float* dmaps, const float* masks, const float* d_candi,
                                     const float* g_fused, const float* g_logfused, int B, int D, int H, int W, float var, float eps,
@@ -150,29 +150,14 @@ hipError_t launch_ufield(const float* dpv, const float* d_candi, const float* in
                          int W, int bv_log, float unc_ang, float zstart, float zend, float mind, int quash, float oob_depth,
                          float* plane, float* depth_zero, void* workspace, hipStream_t stream);
 
-// extras.hip
-hipError_t launch_dpv_moments(const float* dpv, const float* d_candi, int B, int D, int H, int W, int bv_log,
-                              float* mean, float* var, hipStream_t stream);
-hipError_t launch_dpv_fuse(const float* logp, const float* dmaps, const float* masks, const float* d_candi,
-                           int B, int D, int H, int W, float var, float eps, float* fused, float* logfused,
-                           hipStream_t stream);
-hipError_t launch_correlation_forward(const float* x1, const float* x2, int B, int C, int H, int W, int radius,
-                                      int stride2, float* out, hipStream_t stream);
-int correlation_max_radius();
-// whether the tiled kernels' LDS tile of a (radius, stride2) fits the CU (extras.hip states the arithmetic); the C entries ask
-// before they launch anything, and a configuration that does not fit runs the general kernels
-bool correlation_forward_fits(int radius, int stride2);
-bool correlation_backward_fits(int radius, int stride2);
-// correlation_general.hip: every configuration of the reference's kernel, fp32 or fp16 I/O (half != 0), fp32 accumulation
+// correlation_general.hip (called by the dispatch of correlation.hip): every configuration of the reference's kernel, fp32 or
+// fp16 I/O (half != 0), fp32 accumulation
 bool correlation_output_size(int H, int W, int pad, int k, int md, int s1, int* oH, int* oW);
 hipError_t launch_correlation_general_forward(const void* x1, const void* x2, int half, int B, int C, int H, int W, int pad, int k, int md,
                                               int s1, int s2, void* out, hipStream_t stream);
 hipError_t launch_correlation_general_backward(const void* x1, const void* x2, const void* go, int half, int B, int C, int H, int W, int pad,
                                                int k, int md, int s1, int s2, void* g1, void* g2, hipStream_t stream);
-hipError_t launch_correlation_backward(const float* x1, const float* x2, const float* go, int B, int C, int H, int W,
-                                       int radius, int stride2, float* g1, float* g2, hipStream_t stream);
-hipError_t launch_inverse_warp(const float* img, const float* depth, const float* Kinv, const float* proj, int B,
-                               int C, int H, int W, int mode, float* out, unsigned char* valid, hipStream_t stream);
+// inverse_warp.hip (scatter_det.hip calls it for the gradient of the projected point)
 hipError_t launch_inverse_warp_backward(const float* img, const float* depth, const float* Kinv, const float* proj,
                                         const float* grad_out, int B, int C, int H, int W, int mode, float* grad_img,
                                         float* grad_pc, hipStream_t stream);

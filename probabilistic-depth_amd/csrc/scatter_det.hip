@@ -1,5 +1,5 @@
 // The two scattered gradients of the training loss as order-independent sums (fixed_accum.hpp): g_src_depth of the depth stereo
-// consistency term (loss_terms.hip: loss_dsc_bwd_kernel) and grad_img of inverse_warp (extras.hip: inverse_warp_bwd_kernel, both
+// consistency term (loss_terms.hip: loss_dsc_bwd_kernel) and grad_img of inverse_warp (inverse_warp.hip: inverse_warp_bwd_kernel, both
 // sampling modes).  The same bits from call to call, and an item's result does not depend on its neighbours in the batch.
 //
 // Both are one-thread-per-pixel kernels, and each has one scatter body -- dsc_scatter (loss_terms_math.hpp), scatter_sample

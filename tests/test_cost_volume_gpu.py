@@ -113,6 +113,42 @@ def test_backward_bits(run, dev, monkeypatch):
     assert seen == [True, False] and all(torch.equal(p, q) for p, q in zip(a, c)) and float((d[1] - a[1]).abs().max()) <= ref.tol_g_x2
 
 
+# the no-flow cases, and one at md = 1: two tile rows and three tile columns, ragged both ways; the second channel chunk holds one
+# channel; the tile (18 x 18) is narrower than the kernel's static allocation (24 x 24)
+GATHER_CASES = [c for c in U.CASES if not c[2]] + [((1, 9, 17, 35), 1, False)]
+
+
+@pytest.mark.parametrize("case", GATHER_CASES, ids=U.case_id)
+def test_gather_has_the_bits_of_the_correlation_backward(case, dev):
+    """Without a flow, launch 1 of the backward IS the correlation's backward on grad_out (out > 0 ? 1 : slope): flow_cost_volume_bwd_kernel
+    (csrc/cost_volume.hip) restates the displacement loop and the store of correlation_bwd_kernel (csrc/correlation.hip), in the same
+    order, so both gradients agree bit for bit, and each gradient alone has the bits of its twin from the both-gradients call, on
+    either entry."""
+    shape, md, _ = case
+    if case in U.CASES:
+        x1, x2, _, go = _device(case, dev)
+    else:
+        g = torch.Generator().manual_seed(2990)
+        x1, x2 = (torch.randn(*shape, generator=g).to(dev) for _ in range(2))
+        go = torch.randn(shape[0], (2 * md + 1) ** 2, *shape[2:], generator=g).to(dev)
+    out = ops.flow_cost_volume(x1, x2, None, max_displacement=md, negative_slope=U.SLOPE)
+
+    def fused(**want):
+        return _native.flow_cost_volume_backward(x1, x2, None, out, go, max_displacement=md, negative_slope=U.SLOPE, **want)[:2]
+
+    def composed(**want):
+        return _native.correlation_backward(x1, x2, torch.where(out > 0, go, go * U.SLOPE), md, 1, md, 1, 1, 1, **want)
+    f, c = fused(), composed()
+    alone = ((fused(want_x2=False)[0], f[0]), (fused(want_x1=False)[1], f[1]),
+             (composed(want2=False)[0], c[0]), (composed(want1=False)[1], c[1]))
+    apart = [int((p.view(torch.int32) != q.view(torch.int32)).sum()) for p, q in tuple(zip(f, c)) + alone]
+    print(f"gather {U.case_id(case)}: elements with other bits, fused against correlation (grad_x1, grad_x2) {apart[:2]}, "
+          f"each gradient alone against its twin (fused x1, x2; correlation x1, x2) {apart[2:]}")
+    assert tuple(f[0].shape) == tuple(f[1].shape) == tuple(shape)
+    assert all(torch.equal(p, q) for p, q in zip(f, c))
+    assert all(torch.equal(p, q) for p, q in alone)
+
+
 @pytest.mark.parametrize("pad", U.PADS)
 def test_non_finite_reaches_what_the_composition_makes_non_finite(pad, dev):
     case = U.CASES[1]   # (2, 3, 19, 27), md = 4

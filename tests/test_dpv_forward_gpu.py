@@ -1,4 +1,4 @@
-"""The forward of the DPV reductions (csrc/dpv.hip, csrc/dpv_reduce_body.hpp, csrc/extras.hip, csrc/dpv_half.hip) against the
+"""The forward of the DPV reductions (csrc/dpv.hip, csrc/dpv_reduce_body.hpp, csrc/dpv_moments.hip, csrc/dpv_half.hip) against the
 float64 restatement of tests/util_dpv_forward.py: every plane of every pixel inside the a-priori per-element bound derived
 there, on every shape of its table (each reaches the kernel the table names) and every column kind -- peaked, tied, flat, offset
 by +-1e4, a third of the planes at -inf, one-hot -- for ops.dpv_reduce (plain and in place), ops.dpv_reduce_ex (all outputs at

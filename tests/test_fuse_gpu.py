@@ -1,4 +1,4 @@
-"""GPU suite: ops.dpv_fuse, forward (csrc/extras.hip: dpv_fuse_reg_kernel<64|128>, dpv_fuse_kernel) and backward
+"""GPU suite: ops.dpv_fuse, forward (csrc/dpv_fuse.hip: dpv_fuse_reg_kernel<64|128>, dpv_fuse_kernel) and backward
 (csrc/dpv_fuse_bwd.hip: the register form FULL and !FULL, the re-reading form with the fast and with libm's arithmetic), against
 the float64 restatement of tests/util_fuse.py inside its a-priori bound on every plane of every column -- no pixel is left
 out -- and the two claims no reference can check: that the backward recomputes the forward's q bit for bit, and that it

@@ -128,7 +128,7 @@ def test_correlation_and_warps_on_random_shapes():
 
 
 def test_correlation_forward_matrix_pipe_on_random_shapes():
-    """The matrix-pipe forward of the fast configuration (kernel 1, stride1 1, pad = max_displacement; extras.hip) over channel
+    """The matrix-pipe forward of the fast configuration (kernel 1, stride1 1, pad = max_displacement; correlation.hip) over channel
     counts on both sides of its three instantiations (C <= 64 / 128 / 256), image widths around the 16-pixel groups and the
     64-pixel workgroups, every radius and displacement stride it takes -- against the restatement of the reference's kernel."""
     rng = np.random.default_rng(77)

@@ -20,8 +20,8 @@ CSRC = os.path.join(REPO, "probabilistic-depth_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm",
          "-amdgpu-atomic-optimizer-strategy=None", "-Wno-unused-function", "-Wno-inline-asm"]
-OBJS = ["capi.o", "sweep_direct.o", "sweep_pack.o", "pack_dist.o", "sweep_tiled.o", "dpv.o", "warp.o", "extras.o",
-        "correlation_general.o", "ufield.o", "sweep_bwd.o", "dpv_bwd.o", "sweep_tiled_n2.o"]
+OBJS = ["capi.o", "sweep_direct.o", "sweep_pack.o", "pack_dist.o", "sweep_tiled.o", "dpv.o", "warp.o", "dpv_fuse.o",
+        "dpv_moments.o", "correlation.o", "inverse_warp.o", "correlation_general.o", "ufield.o", "sweep_bwd.o", "dpv_bwd.o", "sweep_tiled_n2.o"]
 
 CHILD = r"""
 import sys, torch

@@ -1,4 +1,4 @@
-"""warp_feature (csrc/warp.hip) and inverse_warp forward + backward (csrc/extras.hip, utils/inverse_warp.py) against the
+"""warp_feature (csrc/warp.hip) and inverse_warp forward + backward (csrc/inverse_warp.hip, utils/inverse_warp.py) against the
 float64 references of tests/util_warps.py, on the shapes and poses where such kernels go wrong.
 
 warp_feature: |got - exact64| <= 4 eps32 max|src[b, v]| wherever the oracle's position is finite (the derivation is in

@@ -1,5 +1,5 @@
 """Shared by tests/test_correlation_host.py and tests/test_correlation_gpu.py: a float64 restatement of the correlation
-operator (include/pdepth.h; csrc/extras.hip: correlation_fwd_kernel<R>, correlation_fwd_mfma_kernel<KMAX>,
+operator (include/pdepth.h; csrc/correlation.hip: correlation_fwd_kernel<R>, correlation_fwd_mfma_kernel<KMAX>,
 correlation_bwd_kernel<WANT1,WANT2>; csrc/correlation_general.hip: corr_general_fwd, corr_general_bwd), forward and both
 gradients, the a-priori per-element bound a float32 (or fp16 I/O) evaluation of it is held to, a restatement of the dispatch
 (which_kernel), float32 emulations of the kernels' summation orders and the mistakes the bound must catch for the host test,
@@ -28,8 +28,8 @@ at most m roundings, one per addition above it); the rounding of 1/n to float32 
 compared.  Where the reference is not finite, the result must be of the same class (+inf, -inf, NaN): ratio().  No number here
 comes from a kernel's output.
 
-Which kernel a call runs (which_kernel restates corr_fast_path of csrc/capi.hip, the two LDS predicates and
-launch_correlation_forward of csrc/extras.hip):
+Which kernel a call runs (which_kernel restates the dispatch of csrc/correlation.hip: corr_fast_path, the two LDS predicates and
+launch_correlation_forward):
     fp16, or not (k = 1, s1 = 1, pad = md >= 1, md % s2 = 0, md / s2 <= 4)                                 general
     forward : LDS (8 * 16 * (16 + 2 md) + 8 * 256) * 4 > 160 KiB   (md >= 145)                             general
               C <= 256, md <= 16, C H W 4 < 2^31, B H ceil(W / 64) < 2^31       matrix pipe, KMAX 16 | 32 | 64 for C <= 64 | 128 | 256

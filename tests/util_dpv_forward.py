@@ -1,5 +1,5 @@
 """Shared by tests/test_dpv_forward_host.py and tests/test_dpv_forward_gpu.py: a float64 restatement of the FORWARD of the DPV
-reductions (csrc/dpv.hip, csrc/dpv_reduce_body.hpp, csrc/extras.hip: dpv_reduce, dpv_reduce_ex, dpv_expect, dpv_moments), the
+reductions (csrc/dpv.hip, csrc/dpv_reduce_body.hpp, csrc/dpv_moments.hip: dpv_reduce, dpv_reduce_ex, dpv_expect, dpv_moments), the
 per-element a-priori bound a float32 evaluation of it is held to, a float32 emulation of the kernels' two summation orders for
 the host test (with the mistakes the bound must catch), and the tables of shapes, column kinds and dispatch.
 
@@ -43,7 +43,7 @@ E_lp < 1e-3.  A result below the normal range (p = e^-100 on a peaked column) fa
 E_z = 2 u z + TINY32 (BV_log: expf of an exact input) or 0 (linear).  No number here comes from a kernel's output.
 
 Which order a call runs (order_of restates launch_dpv_reduce, launch_dpv_reduce_ex, launch_dpv_expect, launch_dpv_moments of
-csrc/dpv.hip and csrc/extras.hip, and launch_reduce_lp of csrc/dpv_half.hip):
+csrc/dpv.hip and csrc/dpv_moments.hip, and launch_reduce_lp of csrc/dpv_half.hip):
     dpv_reduce      lanes iff H W % 4 == 0, D <= 128 and logits / logp / depth on 16-byte boundaries
     dpv_reduce_ex   lanes iff W % 4 == 0, D <= 128, every tensor on a 16-byte boundary and not (in place with an addend);
                     in place = logp written over the logits: a call that asks for no logp is not in place

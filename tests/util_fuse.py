@@ -1,4 +1,4 @@
-"""Shared by tests/test_fuse_host.py and tests/test_fuse_gpu.py: a float64 restatement of the DPV fusion (csrc/extras.hip:
+"""Shared by tests/test_fuse_host.py and tests/test_fuse_gpu.py: a float64 restatement of the DPV fusion (csrc/dpv_fuse.hip:
 dpv_fuse_reg_kernel<64|128>, dpv_fuse_kernel) and of its gradient (csrc/dpv_fuse_bwd.hip), the classifier of columns, the
 per-element a-priori bound a float32 evaluation is held to, a float32 emulation of the kernels' loops with the mistakes the bound
 must catch, and the tables of shapes and column kinds.

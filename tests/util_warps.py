@@ -6,7 +6,7 @@ warp_feature (csrc/warp.hip) is a bilinear gather at positions the suite already
 (test_hip_parity.py::test_sample_coordinates_bit_exact), so its reference takes the oracle's float32 positions as they are
 and evaluates only the gather in float64: bilinear64.  It is written with torch ops and differentiable in `src`.
 
-inverse_warp (csrc/extras.hip, utils/inverse_warp.py) computes its positions itself, from a depth map, so its reference is
+inverse_warp (csrc/inverse_warp.hip, utils/inverse_warp.py) computes its positions itself, from a depth map, so its reference is
 the whole chain in float64 under autograd: inverse_warp64, the lines of oracle.ref_cpu.inverse_warp restated so that the
 projected point and the sample position come back too (the host test pins the restatement to the oracle bit for bit)."""
 import numpy as np
