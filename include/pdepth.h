@@ -70,7 +70,8 @@ extern "C" {
                                 *    pdepth_flow_warp_f32, pdepth_flow_warp_backward_f32, pdepth_flow_warp_backward_det_f32 and its
                                 *    _det_workspace_bytes, pdepth_flow_fb_check_f32; pdepth_loss_smooth1_f32 and its _backward_f32;
                                 *    pdepth_flow_cost_volume_f32, its _backward_f32 and _backward_det_f32 and their workspace queries;
-                                *    pdepth_flow_photo_workspace_bytes, pdepth_flow_photo_f32, pdepth_flow_photo_backward_f32 */
+                                *    pdepth_flow_photo_workspace_bytes, pdepth_flow_photo_f32, pdepth_flow_photo_backward_f32;
+                                *    pdepth_flow_metrics_workspace_bytes, pdepth_flow_metrics_f32, pdepth_flow_resize_f32 */
 
 enum {
     PDEPTH_OK = 0,
@@ -992,6 +993,52 @@ int pdepth_flow_photo_f32(const float *im, const float *other, const float *flow
 int pdepth_flow_photo_backward_f32(const float *im, const float *other, const float *flow, const float *mask, const float *count,
                                    const float *g_value, int32_t B, int32_t H, int32_t W, int32_t pad, double w_l1, double w_ssim,
                                    double w_ternary, float *g_flow, void *stream);
+
+/*
+ * Optical-flow evaluation: end-point error means, the KITTI outlier rate ("Fl") and the mask sums per item of a batch, on the
+ * device (utils/flow_utils.py:61-123 evaluate_flow, which copies the prediction to the host, rescales it, resizes it with
+ * cv2.resize and loops over the items; its callers: trainer/sintel_trainer.py:92-151).
+ *   gt        [B,gt_channels,H,W]: gt_channels 2 = (u, v), or 4 = (u, v, valid, noc) as the KITTI loaders stack them;
+ *   pred      [B,2,h,w], h and w any size (larger, smaller or equal, each axis on its own);
+ *   move_mask [B,H,W] or NULL, with gt_channels == 4 only.
+ * Per item b and ground-truth pixel (y, x):
+ *     u' = (u / (float)w) * (float)W,  v' = (v / (float)h) * (float)H         the reference's two float operations, in its order
+ *                                                                            (flow_utils.py:77-80), applied to each tap
+ *     (up, vp) = the bilinear sample of (u', v') under cv2.resize's INTER_LINEAR rule: half-pixel centres,
+ *                sx = (x + 0.5) w / W - 0.5, x0 = floor(sx); x0 < 0: tap 0 with weight 1; x0 >= w - 1: tap w - 1 with weight 1;
+ *                otherwise taps x0, x0 + 1 with weights 1 - (sx - x0), sx - x0; rows alike; the two rows are interpolated first,
+ *                then the column; no antialiasing when shrinking (in exact arithmetic: F.interpolate(mode='bilinear',
+ *                align_corners=False)).  The position is formed in double, the weights and the sums of products in float.
+ *     epe = sqrtf((up - gu)^2 + (vp - gv)^2)
+ *     bad(m) <=> epe m > 3 && epe m / max(sqrtf(gu^2 + gv^2), 1e-10) > 0.05    (float, as numpy's float32)
+ *   errors[b, 0..7] = { epe, epe_noc, epe_occ, fl, epe_move, epe_static, fl_move, fl_static }
+ *   counts[b, 0..4] = { S valid, S noc, S (valid - noc), S valid move, S valid (1 - move) }
+ *     gt_channels == 2: epe = S epe / (H W), counts[b,0] = H W; every other column is NaN.
+ *     gt_channels == 4: epe = S epe valid / S valid, epe_noc = S epe noc / S noc,
+ *                       epe_occ = S epe (valid - noc) / max(S (valid - noc), 1), fl = 100 #bad(valid) / S valid;
+ *     with move_mask:   epe_move = S epe valid move / S valid move, epe_static = S epe valid (1 - move) / S valid (1 - move),
+ *                       fl_move = 100 #bad(valid move) / S valid move, fl_static = 100 #bad(valid (1 - move)) / S valid (1 - move);
+ *                       without it columns 4..7 of errors and 3..4 of counts are NaN.
+ *     A mean or rate whose denominator is 0 is NaN (numpy divides by zero there); epe_occ of such an item is 0.
+ *   flow_up   [B,2,H,W] or NULL: receives (up, vp), the rescaled, resized flow, from the same pass; asking for it changes no bit
+ *             of errors or counts.  With h == H and w == W it holds the bits of numpy's float32 pred / w * W.
+ *   The per-pixel terms are fp32, their sums fp64; reproducible bit for bit: one record per workgroup of 256 pixels in the
+ *   workspace, added in a fixed order by a second launch -- no atomics.  16-byte loads of the truth where H W is a multiple of 4
+ *   and gt and move_mask are 16-byte aligned, the same values otherwise.
+ *   workspace: pdepth_flow_metrics_workspace_bytes(B, H, W) bytes (104 bytes per 256 pixels), 256-byte aligned; 0 for
+ *   non-positive sizes.  H W and h w at most 2^30, B at most 65535; a null pointer, gt_channels other than 2 or 4, a move mask
+ *   with 2 channels: PDEPTH_E_ARG; a missing, short or misaligned workspace: PDEPTH_E_WORKSPACE; all before any launch.
+ *
+ * pdepth_flow_resize_f32: the rescale and the resize alone, the same sampling: flow [B,2,h,w] -> out [B,2,H,W] (not in place).
+ *   align_corners 0: the rule above (the bits of flow_up).  align_corners 1: sx = x (w - 1) / (W - 1), 0 when W == 1, rows
+ *   alike: utils/flow_utils.py:50-58 resize_flow (F.interpolate(align_corners=True), then the division by w / W and h / H).
+ */
+size_t pdepth_flow_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int pdepth_flow_metrics_f32(const float *gt, int32_t gt_channels, const float *pred, int32_t h, int32_t w, const float *move_mask,
+                            int32_t B, int32_t H, int32_t W, float *errors, float *counts, float *flow_up, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int pdepth_flow_resize_f32(const float *flow, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W, int32_t align_corners,
+                           float *out, void *stream);
 
 #ifdef __cplusplus
 }

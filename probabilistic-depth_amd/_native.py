@@ -123,6 +123,9 @@ _SIGNATURES = {
     "pdepth_flow_photo_workspace_bytes": (_Z, [_I] * 3),
     "pdepth_flow_photo_f32": (c_int, [_P] * 4 + [_I] * 4 + [c_double] * 3 + [_P] * 3 + [_Z, _P]),
     "pdepth_flow_photo_backward_f32": (c_int, [_P] * 6 + [_I] * 4 + [c_double] * 3 + [_P] * 2),
+    "pdepth_flow_metrics_workspace_bytes": (_Z, [_I] * 3),
+    "pdepth_flow_metrics_f32": (c_int, [_P, _I, _P, _I, _I, _P] + [_I] * 3 + [_P] * 4 + [_Z, _P]),
+    "pdepth_flow_resize_f32": (c_int, [_P] + [_I] * 6 + [_P] * 2),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM, census and range-map entries live in objects of their own: part of an entry's name -> the source file.  The
@@ -132,7 +135,7 @@ _SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_loss_smooth1_": "csrc/lo
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
                     "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip", "_ternary_": "csrc/ternary.hip",
                     "_range_map_": "csrc/occlusion.hip", "_flow_cost_volume_": "csrc/cost_volume.hip", "_flow_photo_": "csrc/flow_photo.hip",
-                    "_flow_": "csrc/flow_warp.hip",
+                    "_flow_metrics_": "csrc/flow_metrics.hip", "_flow_resize_": "csrc/flow_metrics.hip", "_flow_": "csrc/flow_warp.hip",
                     "_soft_ce_": "csrc/loss.hip", "_depth_metrics_": "csrc/metrics.hip", "_fuse_backward_": "csrc/dpv_fuse_bwd.hip",
                     "_lidar_depth_": "csrc/lidar_depth.hip", "_loss_": "csrc/loss_terms.hip", "_reduce_ex_lp": "csrc/dpv_half.hip",
                     "_reduce_backward_lp": "csrc/dpv_half.hip"}
@@ -1822,6 +1825,64 @@ def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_ma
                                                      _stream(dev))
     _check(rc, lib)
     return metrics, count, depth
+
+
+# ---- flow evaluation (ops.flow_metrics, ops.flow_resize) ------------------------------------------------------------------------
+def _flow_tensor(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
+    return t.contiguous().float()
+
+
+def flow_metrics(gt, pred, move_mask=None, want_flow=False):
+    """gt [B,2|4,H,W], pred [B,2,h,w] [, move_mask [B,H,W]] -> (errors [B,8], counts [B,5], flow_up [B,2,H,W] | None):
+    pdepth_flow_metrics_f32 on the current stream, no host synchronisation."""
+    who = "flow_metrics"
+    lib = load()
+    _no_autograd(who, gt, pred, move_mask)
+    if gt.dim() != 4 or gt.shape[1] not in (2, 4):
+        raise RuntimeError(f"{who}: gt must be [B,2,H,W] or [B,4,H,W], got {list(gt.shape)}")
+    B, C, H, W = gt.shape
+    if pred.dim() != 4 or pred.shape[0] != B or pred.shape[1] != 2:
+        raise RuntimeError(f"{who}: pred must be [{B}, 2, h, w], got {list(pred.shape)}")
+    h, w = pred.shape[2:]
+    if move_mask is not None:
+        if C != 4:
+            raise RuntimeError(f"{who}: a move mask needs a truth of 4 channels (it multiplies valid)")
+        _shape(move_mask, (B, H, W), "move_mask", who)
+    gt, pred = _flow_tensor(gt, "gt"), _flow_tensor(pred, "pred")
+    move_mask = None if move_mask is None else _flow_tensor(move_mask, "move_mask")
+    dev = gt.device
+    if pred.device != dev or (move_mask is not None and move_mask.device != dev):
+        raise RuntimeError(f"{who}: gt, pred and move_mask must be on one device")
+    out = torch.empty(B * 13, dtype=torch.float32, device=dev)
+    errors, counts = out[:B * 8].view(B, 8), out[B * 8:].view(B, 5)
+    flow_up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if want_flow else None
+    ws_bytes = _entry(lib, "pdepth_flow_metrics_workspace_bytes")(B, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _entry(lib, "pdepth_flow_metrics_f32")(gt.data_ptr(), C, pred.data_ptr(), h, w, _ptr(move_mask), B, H, W, errors.data_ptr(),
+                                                    counts.data_ptr(), _ptr(flow_up), ws.data_ptr(), ws_bytes, _stream(dev))
+    _check(rc, lib)
+    return errors, counts, flow_up
+
+
+def flow_resize(flow, size, align_corners=False):
+    """flow [B,2,h,w] -> [B,2,H,W], rescaled by W / w and H / h and resized: pdepth_flow_resize_f32 on the current stream."""
+    who = "flow_resize"
+    lib = load()
+    _no_autograd(who, flow)
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise RuntimeError(f"{who}: flow must be [B,2,h,w], got {list(flow.shape)}")
+    B, _, h, w = flow.shape
+    H, W = (int(s) for s in size)
+    flow = _flow_tensor(flow, "flow")
+    out = torch.empty((B, 2, H, W), dtype=torch.float32, device=flow.device)
+    with _on_device(flow.device):
+        rc = _entry(lib, "pdepth_flow_resize_f32")(flow.data_ptr(), B, h, w, H, W, 1 if align_corners else 0, out.data_ptr(),
+                                                   _stream(flow.device))
+    _check(rc, lib)
+    return out
 
 
 # ---- ground truth from LiDAR (ops.lidar_depth) ----------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // What the C entries (include/pdepth.h) of capi.hip, dpv_fuse.hip, dpv_moments.hip, correlation.hip, inverse_warp.hip, loss.hip, loss_terms.hip, metrics.hip, lidar_depth.hip, dpv_fuse_bwd.hip,
-// sweep_bwd_det.hip, scatter_det.hip, warp_bwd.hip, ssim.hip, photo.hip, ternary.hip, occlusion.hip, flow_warp.hip and loss_smooth1.hip check and report alike.
+// sweep_bwd_det.hip, scatter_det.hip, warp_bwd.hip, ssim.hip, photo.hip, ternary.hip, occlusion.hip, flow_warp.hip, loss_smooth1.hip and flow_metrics.hip check and report alike.
 // Inline, and in need of nothing but pdepth::api_error (capi.o): an object that includes this refers to no other object, so a
 // library linked from a subset of the objects (tests/test_sweep_prefetch.py) still links.  (cost_volume.hip and flow_photo.hip
 // also include this; they alone need a second object, flow_warp.o, whose backward the first launches and whose check of sizes

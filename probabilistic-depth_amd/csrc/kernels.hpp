@@ -118,6 +118,14 @@ hipError_t launch_depth_metrics(const float* logp, const float* pred, const floa
                                 float clamp_max, int B, int D, int H, int W, float* metrics, float* count, float* depth,
                                 void* workspace, hipStream_t stream);
 
+// flow_metrics.hip: the flow evaluation per item of a batch (end-point error means, outlier rates, mask sums) of pred [B,2,h,w]
+// rescaled and resized to gt [B,gt_channels,H,W]; move_mask [B,H,W] and flow_up [B,2,H,W] may be nullptr.  launch_flow_resize:
+// the rescale and resize alone, half-pixel centres or align_corners
+size_t flow_metrics_workspace_bytes(int B, int H, int W);
+hipError_t launch_flow_metrics(const float* gt, int gt_channels, const float* pred, int h, int w, const float* move_mask, int B, int H,
+                               int W, float* errors, float* counts, float* flow_up, void* workspace, hipStream_t stream);
+hipError_t launch_flow_resize(const float* flow, int B, int h, int w, int H, int W, bool align_corners, float* out, hipStream_t stream);
+
 // lidar_depth.hip: LiDAR scans -> z-buffered, filtered depth maps and masks at full and quarter resolution.  points [B,Nmax,dim]
 // (dim 3: w = 1), counts [B], M [4,4] | [B,4,4], intr [3,4] | [B,3,4]; the workspace is the z-buffer
 size_t lidar_depth_workspace_bytes(int B, int H, int W);

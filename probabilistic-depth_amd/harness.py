@@ -135,6 +135,36 @@ def validate(model, frames, cfg=None, sync_debug="error"):
             "results": results, "results_refined": results_refined, "steps": steps}
 
 
+@torch.no_grad()
+def validate_flow(model, batches, sync_debug="error"):
+    """The evaluation of a flow network (the loop of trainer/sintel_trainer.py:92-151): batches = [(img_pair [B,6,H,W], gt_flow
+    [B,2|4,Hg,Wg][, move_mask [B,Hg,Wg]]), ...] on the device.  Per batch model(img_pair)['flows_fw'][0] is rescaled, resized
+    and compared with the truth by ops.flow_metrics.  Returns {"errors": {name: mean over every item of every batch}, "names",
+    "steps"}: names = the columns the truth defines, in the order of ops.FLOW_METRIC_NAMES (evaluate_flow's values first), the
+    mean what AverageMeter.update(es, B) accumulates (sintel_trainer.py:121-122); steps = the per-batch {"flow", "errors" [B,8],
+    "counts" [B,5]} tensors.  As in validate the loop never waits for the device -- it runs under
+    torch.cuda.set_sync_debug_mode(sync_debug) -- and the per-item table is read back in one copy at the end."""
+    batches = list(batches)
+    steps = []
+    before = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode(sync_debug)
+    try:
+        for batch in batches:
+            img_pair, gt_flow = batch[0], batch[1]
+            flow = model(img_pair)["flows_fw"][0]
+            errs, counts, _ = ops.flow_metrics(gt_flow, flow, move_mask=batch[2] if len(batch) > 2 else None)
+            steps.append({"flow": flow, "errors": errs, "counts": counts})
+        table = torch.cat([s["errors"] for s in steps]) if steps else None
+    finally:
+        torch.cuda.set_sync_debug_mode(before)
+    if table is None:
+        raise RuntimeError("validate_flow: no batch to evaluate")
+    table = table.cpu().numpy().astype(np.float64)   # the one read-back
+    n = 1 if batches[0][1].shape[1] == 2 else (4 if len(batches[0]) < 3 else 8)
+    names = ops.FLOW_METRIC_NAMES[:n]
+    return {"errors": {name: float(table[:, j].mean()) for j, name in enumerate(names)}, "names": names, "steps": steps}
+
+
 def _lidar_params(params):
     """(filtering, filterdiff) of the reference's parameter dict / attribute dict; upsample != 0 is refused."""
     get = params.get if hasattr(params, "get") else (lambda k, d=None: getattr(params, k, d))

@@ -222,6 +222,38 @@ def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_ma
     return _native.depth_metrics(truth, pred=pred, logp=logp, d_candi=dc, mask=mask, clamp_max=clamp_max, want_depth=want_depth)
 
 
+# the columns of flow_metrics' errors: evaluate_flow's values in its order (utils/flow_utils.py:117-121), then the two rates it
+# accumulates for the move mask and does not return
+FLOW_METRIC_NAMES = ("epe", "epe_noc", "epe_occ", "fl", "epe_move", "epe_static", "fl_move", "fl_static")
+
+
+def flow_metrics(gt, pred, move_mask=None, want_flow=False):
+    """The flow evaluation per item, on the device: (errors [B,8] in the order of FLOW_METRIC_NAMES, counts [B,5] = the sums of
+    valid, noc, valid - noc, valid * move, valid * (1 - move), flow_up [B,2,H,W] | None).  utils/flow_utils.evaluate_flow
+    (utils/flow_utils.py:61-123) for the whole batch, without copying the prediction to the host.
+
+    gt [B,2,H,W] = (u, v) or [B,4,H,W] = (u, v, valid, noc); pred [B,2,h,w] of any size; move_mask [B,H,W] | [B,1,H,W] | None
+    (4-channel truth only).  The prediction is rescaled (u / w * W, v / h * H in float, in that order) and resized to H x W with
+    cv2.resize's INTER_LINEAR rule (half-pixel centres, no antialiasing); want_flow returns that map from the same pass and
+    changes no bit of the rest.  epe = |flow_up - gt_uv|; a 2-channel truth gives its plain mean in column 0; a 4-channel truth
+    the means over valid, noc and valid - noc (the last divided by max(sum, 1)) and fl = 100 * #(epe * valid > 3 and
+    epe * valid / max(|gt_uv|, 1e-10) > 0.05) / sum(valid); the move mask adds columns 4 to 7.  A column the inputs do not
+    define is NaN, and so is a mean over no pixel.  Sums are float64 in a fixed order: the same bits from call to call.  Not
+    differentiable."""
+    if isinstance(move_mask, torch.Tensor) and move_mask.dim() == 4:
+        move_mask = move_mask[:, 0]
+    _refuse_grad("flow_metrics", gt=gt, pred=pred, move_mask=move_mask)
+    return _native.flow_metrics(gt, pred, move_mask=move_mask, want_flow=want_flow)
+
+
+def flow_resize(flow, size, align_corners=False):
+    """flow [B,2,h,w] -> [B,2,H,W] for size = (H, W): every tap rescaled (u / w * W, v / h * H), then the bilinear sample.
+    align_corners=False: cv2.resize's INTER_LINEAR rule, the bits of flow_metrics' flow_up; True: the coordinates of
+    F.interpolate(align_corners=True), what utils/flow_utils.resize_flow computes (utils/flow_utils.py:50-58).  Not differentiable."""
+    _refuse_grad("flow_resize", flow=flow)
+    return _native.flow_resize(flow, size, align_corners=align_corners)
+
+
 def lidar_depth(points, counts, M_velo2cam, intr, width, height, filtering=2, filterdiff=1.0, pool=4, pool_default=1000.0):
     """The ground truth of a batch from its LiDAR scans, on the device: generate_depth (external/utils_lib/python/utils_lib.cpp:
     86-160, upsample = 0) for every item, then the loader's quarter-resolution map and masks (kittiloader/kitti.py:683-729), in
