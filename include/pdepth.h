@@ -441,8 +441,8 @@ int pdepth_inverse_warp_backward_f32(const float *img, const float *depth, const
  *   backward evaluates every plane directly in fp32 on the NCHW features, positions from the gather kernel's arithmetic);
  *   grad_cost [B,D,H,W] contiguous;
  *   grad_ref  [B,C,H,W] contiguous or NULL: a per-pixel gather, no atomics, bitwise reproducible;
- *   grad_src  [B,V,C,H,W] contiguous or NULL: zeroed on the stream, then scattered with float atomics (summed per workgroup
- *             in LDS first); the last bits depend on the order in which the adds arrive (pdepth_sweep_backward_det_f32: they do not).
+ *   grad_src  [B,V,C,H,W] contiguous or NULL: zeroed on the stream by a launch (not a memset: the call can be captured and
+ *             replayed), then scattered with float atomics (summed per workgroup in LDS first); the last bits depend on the order in which the adds arrive (pdepth_sweep_backward_det_f32: they do not).
  * At least one output must be non-NULL.  Taps outside the image receive nothing (ATen's grid_sampler_2d backward).
  */
 int pdepth_sweep_backward_f32(const pdepth_sweep_desc *desc, const pdepth_camera *cam, const float *ref, const float *src,
@@ -714,7 +714,7 @@ int pdepth_inverse_warp_backward_det_f32(const float *img, const float *depth, c
  * desc is read as pdepth_warp_feature_f32 reads it (C == D planes, algo, blas_mode); src_vstride = D H W and src_bstride = V D H W
  * describe grad_src, which must be contiguous [B,V,D,H,W], as grad_out is.  D <= 512, H W <= 2^30, B <= 65535; grad_src may not
  * alias grad_out.
- *   pdepth_warp_feature_backward_f32      float atomics into grad_src (zeroed by the call on the stream): the last bits depend on
+ *   pdepth_warp_feature_backward_f32      float atomics into grad_src (zeroed by the call on the stream, by a launch): the last bits depend on
  *                                         the order in which the adds arrive; a non-finite grad_out stays in the texels it reaches.
  *   pdepth_warp_feature_backward_det_f32  the order-independent sum described above: q_i = g w_tap, M_b = the exact maximum of
  *                                         |q_i| over item b (a first run of the chain), N = H W (a sample puts at most one of its
@@ -841,8 +841,8 @@ int pdepth_ternary_backward_f32(const float *x, const float *y, const float *g_o
  *
  * Workspace: roundup256(8 B H W) bytes, 256-byte aligned, cleared by the call; the query returns 0 for sizes out of range; missing,
  * too small or misaligned: PDEPTH_E_WORKSPACE.  H * W <= 2^24, B <= 65535, H, W >= 1 (the depth form: >= 2); a null input, no
- * output, a non-positive size or th NaN: PDEPTH_E_ARG, before any launch.  A memset and two launches on `stream`; nothing is
- * allocated, nothing waits for the host.
+ * output, a non-positive size or th NaN: PDEPTH_E_ARG, before any launch.  Three launches on `stream` (the zero fill of the
+ * workspace is a kernel: the call can be captured in a graph and replayed); nothing is allocated, nothing waits for the host.
  */
 size_t pdepth_range_map_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int pdepth_range_map_f32(const float *coords, int32_t B, int32_t H, int32_t W, float th, float *range, float *visible,
@@ -875,7 +875,7 @@ int pdepth_depth_range_map_f32(const float *depth, const float *src_mask, const 
  *       order: no atomics, the same bits from call to call.  d ix / d flow_x = (W / 2) (2 / (W - 1)); with border padding the factor
  *       is 0 where the position was clamped from strictly outside [0, W - 1] and 1 at exactly 0 or W - 1 (likewise y).
  *       grad_x is a scatter of g w_tap: an in-bounds tap receives g w even when w == 0, an out-of-bounds tap nothing (the rules
- *       of pdepth_warp_feature_backward_f32); float atomics into grad_x, zeroed by the call on the stream.
+ *       of pdepth_warp_feature_backward_f32); float atomics into grad_x, zeroed by the call on the stream, by a launch.
  *   pdepth_flow_warp_backward_det_f32  grad_x as the order-independent sum of "Deterministic backward" above: its fifth case,
  *       q_i = g w_tap, N = 4 H W, M_b the exact maximum of |q_i| over item b (a first run of the chain); M_b == 0, NaN and overflow
  *       as the other _det entries.  grad_flow has the bits of the atomic entry.  Workspace: roundup256(4 B) + roundup256(8 B C H W)
@@ -932,7 +932,7 @@ int pdepth_loss_smooth1_backward_f32(const float *flo, const float *image, const
  *       (grad_flow must be NULL without a flow).  `out` is the forward's saved result: the activation's factor is
  *       out > 0 ? 1 : negative_slope (0, -0 and NaN take the slope); no pre-activation is kept.  Launch 1 gathers, without atomics,
  *       grad_x1 and the gradient of the warped image into the workspace; launch 2 is pdepth_flow_warp_backward_f32's own work on that
- *       gradient: grad_x2 by float atomics (zeroed by the call on the stream), grad_flow per owner.  Without a flow the gradient of
+ *       gradient: grad_x2 by float atomics (zeroed by the call on the stream, by a launch), grad_flow per owner.  Without a flow the gradient of
  *       the "warped" image is grad_x2 itself: one launch, no workspace.
  *   pdepth_flow_cost_volume_backward_det_f32  grad_x2 by the order-independent sum of pdepth_flow_warp_backward_det_f32 (the fifth
  *       case of "Deterministic backward" above); everything else has the bits of the entry without _det.

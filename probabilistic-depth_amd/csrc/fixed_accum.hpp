@@ -23,6 +23,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "kernels.hpp"   // launch_zero (clear.hip)
+
 namespace pdepth {
 namespace fixed {
 
@@ -165,7 +167,7 @@ inline hipError_t det_convert(void* workspace, int B, size_t per_item, Exponent 
 template <class Launch>
 inline hipError_t max_exponent_scatter(void* workspace, int B, size_t per_item, long long n, float* out, hipStream_t stream,
                                        Launch launch) {
-    hipError_t e = hipMemsetAsync(workspace, 0, det_workspace_bytes(B, MaxExponent::WORDS, per_item), stream);
+    hipError_t e = launch_zero(workspace, det_workspace_bytes(B, MaxExponent::WORDS, per_item), stream);
     if (e != hipSuccess) return e;
     uint32_t* hdr = static_cast<uint32_t*>(workspace);
     unsigned long long* acc = det_accumulator(workspace, B, MaxExponent::WORDS);
@@ -189,7 +191,7 @@ struct FixedExponent {
 // (det_workspace_bytes(B, FixedExponent::WORDS, per_item)) and that S is an exponent.
 template <class Launch>
 inline hipError_t fixed_exponent_scatter(void* workspace, int B, size_t per_item, int S, hipStream_t stream, Launch launch) {
-    hipError_t e = hipMemsetAsync(workspace, 0, det_workspace_bytes(B, FixedExponent::WORDS, per_item), stream);
+    hipError_t e = launch_zero(workspace, det_workspace_bytes(B, FixedExponent::WORDS, per_item), stream);
     if (e != hipSuccess) return e;
     launch(IntegerSum{det_accumulator(workspace, B, FixedExponent::WORDS), S});
     return hipGetLastError();

@@ -168,7 +168,7 @@ hipError_t launch_warp_backward(const float* x, const float* flo, const float* g
                                 float* gflow, hipStream_t s) {
     if (gflow) launch_grad_flow(x, flo, gout, B, C, H, W, pad, gflow, s);
     if (gx) {
-        if (hipError_t e = hipMemsetAsync(gx, 0, (size_t)B * C * H * W * sizeof(float), s)) return e;
+        if (hipError_t e = launch_zero(gx, (size_t)B * C * H * W * sizeof(float), s)) return e;
         hipLaunchKernelGGL(flow_warp_bwd_kernel, grid_of(B, H, W, channel_chunks(B, C, H, W)), dim3(256), 0, s, flo, gout, C,
                            flow::geometry(H, W), pad, gx);
     }

@@ -97,7 +97,7 @@ hipError_t launch_inverse_warp_backward(const float* img, const float* depth, co
                                         const float* grad_out, int B, int C, int H, int W, int mode, float* grad_img,
                                         float* grad_pc, hipStream_t stream) {
     if (grad_img) {
-        hipError_t e = hipMemsetAsync(grad_img, 0, (size_t)B * C * H * W * sizeof(float), stream);
+        hipError_t e = launch_zero(grad_img, (size_t)B * C * H * W * sizeof(float), stream);
         if (e != hipSuccess) return e;
     }
     dim3 grid((H * W + 255) / 256, B);

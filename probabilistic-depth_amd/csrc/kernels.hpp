@@ -126,6 +126,12 @@ hipError_t launch_flow_metrics(const float* gt, int gt_channels, const float* pr
                                int W, float* errors, float* counts, float* flow_up, void* workspace, hipStream_t stream);
 hipError_t launch_flow_resize(const float* flow, int B, int h, int w, int H, int W, bool align_corners, float* out, hipStream_t stream);
 
+// clear.hip: dst[0, bytes) set to one 32-bit word by one launch on the stream (dst 4-byte aligned, bytes a multiple of 4; 16-byte
+// stores between the 16-byte boundaries, single words outside them).  What clears a scatter's destination, an integer-sum workspace
+// or a z-buffer: a kernel, because a hipMemsetAsync in front of a scatter does not survive a graph replay on new data (clear.hip)
+hipError_t launch_fill32(void* dst, uint32_t word, size_t bytes, hipStream_t stream);
+inline hipError_t launch_zero(void* dst, size_t bytes, hipStream_t stream) { return launch_fill32(dst, 0u, bytes, stream); }
+
 // lidar_depth.hip: LiDAR scans -> z-buffered, filtered depth maps and masks at full and quarter resolution.  points [B,Nmax,dim]
 // (dim 3: w = 1), counts [B], M [4,4] | [B,4,4], intr [3,4] | [B,3,4]; the workspace is the z-buffer
 size_t lidar_depth_workspace_bytes(int B, int H, int W);

@@ -23,9 +23,10 @@
 //                with zeros lifted to pool_default, a block whose minimum equals pool_default becomes 0 (so a depth >= 1000
 //                beside an empty pixel disappears, as in the reference); its mask and product likewise.  [H/4] x [W/4]: a
 //                ragged remainder is dropped.
-// The z-buffer is initialised by a launch of its own (all bits set = empty, above every float's pattern) -- a kernel, not
-// hipMemsetAsync: with a memset node in front, a captured call replayed on new points did not reproduce the eager call
-// (DESIGN.md 6.4).  Nothing is allocated, nothing waits for the host: the call can be captured in a graph.
+// The z-buffer is initialised by a launch of its own (all bits set = empty, above every float's pattern) -- the fill kernel of
+// clear.hip, not hipMemsetAsync: with a memset node in front, a captured call replayed on new points did not reproduce the eager
+// call (every memset-fronted scatter of the library turned out to behave so, and clear.hip is what they all use
+// now).  Nothing is allocated, nothing waits for the host: the call can be captured in a graph.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -51,12 +52,6 @@ struct LidarArgs {
     unsigned* zbuf;        // [B,H,W]
     float *dmap, *mask, *dmap_q, *mask_q;
 };
-
-// the whole workspace (a multiple of 256 bytes, 256-byte aligned): 16 bytes per thread
-__global__ __launch_bounds__(256) void lidar_clear_kernel(uint4* __restrict__ z, size_t n16) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n16) z[i] = make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
-}
 
 __global__ __launch_bounds__(256) void lidar_points_kernel(LidarArgs a) {
     const int b = blockIdx.y;
@@ -180,9 +175,7 @@ hipError_t launch_lidar_depth(const float* points, const int* counts, const floa
     a.filterdiff = filterdiff; a.pool_default = pool_default;
     a.zbuf = static_cast<unsigned*>(workspace);
     a.dmap = dmap; a.mask = mask; a.dmap_q = dmap_q; a.mask_q = mask_q;
-    const size_t n16 = lidar_depth_workspace_bytes(B, H, W) / 16;   // (B H W <= 2^40: the grid fits)
-    hipLaunchKernelGGL(lidar_clear_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, stream, static_cast<uint4*>(workspace), n16);
-    hipError_t err = hipGetLastError();
+    hipError_t err = launch_fill32(workspace, EMPTY, lidar_depth_workspace_bytes(B, H, W), stream);   // (clear.hip)
     if (err != hipSuccess) return err;
     if (Nmax > 0) {
         hipLaunchKernelGGL(lidar_points_kernel, dim3((Nmax + 255) / 256, B), dim3(256), 0, stream, a);

@@ -293,7 +293,7 @@ int pdepth_loss_dsc_backward_f32(const float* src_depth, const float* tgt_depth,
     if (!g_src_depth && !g_tgt_depth) return fail(PDEPTH_E_ARG, "%s: no gradient requested", who);
     if (int rc = check_map(who, B, H, W, 2)) return rc;
     if (g_src_depth) {
-        hipError_t e = hipMemsetAsync(g_src_depth, 0, (size_t)B * H * W * sizeof(float), (hipStream_t)stream);
+        hipError_t e = pdepth::launch_zero(g_src_depth, (size_t)B * H * W * sizeof(float), (hipStream_t)stream);
         if (e != hipSuccess) return launched(e, who);
     }
     const DscArgs a{src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr, pose_batched ? 4 : 0, H, W};
@@ -353,7 +353,7 @@ int pdepth_loss_dc_backward_f32(const float* large, const float* small, const fl
     if (int rc = check_map(who, B, H, W, 4)) return rc;
     const int h = H / 4, w = W / 4;
     if (g_large && (H % 4 != 0 || W % 4 != 0)) {   // the rows and columns max_pool2d drops
-        hipError_t e = hipMemsetAsync(g_large, 0, (size_t)B * H * W * sizeof(float), (hipStream_t)stream);
+        hipError_t e = pdepth::launch_zero(g_large, (size_t)B * H * W * sizeof(float), (hipStream_t)stream);
         if (e != hipSuccess) return launched(e, who);
     }
     hipLaunchKernelGGL(loss_dc_bwd_kernel, dim3(n_blocks(h, w), B), dim3(256), 0, (hipStream_t)stream, large, small, count, g_value, H,

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(BTHREADS) void sweep_bwd_kernel(SweepArgs a, const 
 hipError_t launch_sweep_backward(const SweepArgs& a, const float* grad_cost, float* grad_ref, float* grad_src, hipStream_t stream) {
     const size_t HW = (size_t)a.H * a.W;
     if (grad_src) {
-        hipError_t e = hipMemsetAsync(grad_src, 0, (size_t)a.B * a.V * a.C * HW * sizeof(float), stream);
+        hipError_t e = launch_zero(grad_src, (size_t)a.B * a.V * a.C * HW * sizeof(float), stream);
         if (e != hipSuccess) return e;
     }
     auto go = [&](auto kern, auto policy) -> hipError_t {

@@ -9,7 +9,7 @@
 // and a last pass converts the accumulator into g_src.
 //
 // Launch sequence, all on the caller's stream, no host synchronisation, no copy to the host:
-//   1. hipMemsetAsync of the workspace (the per-item header and the accumulator);
+//   1. zero fill (clear.hip) of the workspace (the per-item header and the accumulator);
 //   2. bounds pre-pass: per item max |g_cost[b]| and, for L2, max |src[b]| and max |ref[b]|, as atomicMax over the bit patterns
 //      of |x| (order-independent; a NaN or an infinity wins the maximum);
 //   3. scatter (L2 / L1).  Every workgroup derives S_b of its item from the header (ItemExponent: a few integer operations):
@@ -98,7 +98,7 @@ hipError_t launch_sweep_backward_det(const SweepArgs& a, const float* grad_cost,
     const size_t HW = (size_t)a.H * a.W;
     uint32_t* hdr = static_cast<uint32_t*>(workspace);
     unsigned long long* acc = det_accumulator(workspace, a.B, HDR_WORDS);
-    hipError_t e = hipMemsetAsync(workspace, 0, sweep_backward_det_workspace_bytes(a.B, a.V, a.C, a.H, a.W), stream);
+    hipError_t e = launch_zero(workspace, sweep_backward_det_workspace_bytes(a.B, a.V, a.C, a.H, a.W), stream);
     if (e != hipSuccess) return e;
     const size_t per_block = 256 * 16;   // (elements a block of the pre-pass reads at least, up to 512 blocks per item and array)
     const size_t want = ((size_t)(a.D > a.C ? a.D : a.C) * HW + per_block - 1) / per_block;

@@ -82,7 +82,7 @@ size_t per_item(const SweepArgs& a) { return (size_t)a.V * a.D * a.H * a.W; }
 }  // namespace
 
 hipError_t launch_warp_feature_backward(const SweepArgs& a, const float* grad_out, float* grad_src, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(grad_src, 0, (size_t)a.B * per_item(a) * sizeof(float), stream);
+    hipError_t e = launch_zero(grad_src, (size_t)a.B * per_item(a) * sizeof(float), stream);
     if (e != hipSuccess) return e;
     const int nchunk = plane_chunks(a);
     hipLaunchKernelGGL(warp_bwd_kernel, grid(a, nchunk), dim3(256), 0, stream, a, nchunk, grad_out, grad_src);

@@ -369,7 +369,7 @@ def ternary(x, y, md=1):
 
 
 def range_map(coords):
-    """Range map of a forward splat (utils/warp_utils.py:25-79, get_corresponding_map), a memset and two HIP passes: coords
+    """Range map of a forward splat (utils/warp_utils.py:25-79, get_corresponding_map), three HIP launches (clear, splat, convert): coords
     [B,2,H,W], un-normalised (x, y) positions of the source pixels, fp32 -> [B,1,H,W], the bilinear mass every pixel receives.  Only
     in-bounds taps count; a NaN or infinite position adds nothing.  The sum is an order-independent integer sum (csrc/occlusion.hip):
     the same bits from call to call.  Not differentiable: coords that require grad are refused."""

@@ -166,11 +166,15 @@ def _metadata(name):
 
 
 def test_lidar_kernels_no_spills_no_scratch():
-    """Read from the code-object metadata of `make lidar_depth.s` alone: the clearing kernel, the point kernel and the map kernel
-    in its five instantiations (filtering 0 .. 4)."""
+    """Read from the code-object metadata of `make lidar_depth.s` and `make clear.s` alone: the point kernel and the map kernel in
+    its five instantiations (filtering 0 .. 4), and the fill kernel that clears the z-buffer (csrc/clear.hip, shared with every
+    scatter of the library)."""
     ks = _metadata("lidar_depth")
     assert len([n for n in ks if "lidar_points_kernel" in n]) == 1 and len([n for n in ks if "lidar_maps_kernel" in n]) == 5, sorted(ks)
-    assert len([n for n in ks if "lidar_clear_kernel" in n]) == 1 and len(ks) == 7
+    assert len(ks) == 6, sorted(ks)
+    fill = _metadata("clear")
+    assert len(fill) == 1 and "fill32_kernel" in next(iter(fill)), sorted(fill)
+    ks.update(fill)
     for name, md in ks.items():
         assert md["wavefront_size"] == 64, name
         assert md["sgpr_spill_count"] == 0 and md["vgpr_spill_count"] == 0, (name, md)

@@ -21,7 +21,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm",
          "-amdgpu-atomic-optimizer-strategy=None", "-Wno-unused-function", "-Wno-inline-asm"]
 OBJS = ["capi.o", "sweep_direct.o", "sweep_pack.o", "pack_dist.o", "sweep_tiled.o", "dpv.o", "warp.o", "dpv_fuse.o",
-        "dpv_moments.o", "correlation.o", "inverse_warp.o", "correlation_general.o", "ufield.o", "sweep_bwd.o", "dpv_bwd.o", "sweep_tiled_n2.o"]
+        "dpv_moments.o", "correlation.o", "inverse_warp.o", "correlation_general.o", "ufield.o", "sweep_bwd.o", "dpv_bwd.o", "clear.o", "sweep_tiled_n2.o"]
 
 CHILD = r"""
 import sys, torch
