@@ -6,6 +6,7 @@ memory and the current HIP stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
@@ -128,9 +129,9 @@ _SIGNATURES = {
     "pdepth_flow_resize_f32": (c_int, [_P] + [_I] * 6 + [_P] * 2),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-# The loss, loss-term, photometric, metrics, fusion-backward, LiDAR, deterministic-backward, SSIM, census and range-map entries live in objects of their own: part of an entry's name -> the source file.  The
-# product library must have them; an experiment library named by PDEPTH_LIB may be linked from a subset of the objects: it
-# loads, and a call of such an entry on it raises (_entry)
+# The entries that live in an object of their own, outside the sweep's: a part of the entry's name -> its source file (the first
+# part that matches names it).  The product library must have them all; an experiment library named by PDEPTH_LIB may be linked
+# from a subset of the objects: it loads, and a call of such an entry on it raises (_entry)
 _SOURCE_OF_ENTRY = {"_loss_photo_": "csrc/photo.hip", "_loss_smooth1_": "csrc/loss_smooth1.hip", "_det_scale_": "csrc/sweep_bwd_det.hip", "_sweep_backward_det_": "csrc/sweep_bwd_det.hip",
                     "_dsc_backward_det_": "csrc/scatter_det.hip", "_inverse_warp_backward_det_": "csrc/scatter_det.hip",
                     "_warp_feature_backward_": "csrc/warp_bwd.hip", "_ssim_": "csrc/ssim.hip", "_ternary_": "csrc/ternary.hip",
@@ -162,7 +163,6 @@ def host_blas_mode():
     if env in ("fma", "separate"):
         _host_blas = BLAS_FMA if env == "fma" else BLAS_SEPARATE
         return _host_blas
-    import numpy as np
     g = torch.Generator().manual_seed(7)
     A = (torch.randn(3, 3, generator=g) * 100).float()
     Bm = torch.randn(3, 4096, generator=g).float()
@@ -243,14 +243,49 @@ def _volume_dims(who, volume, d_candi, name):
     return tuple(volume.shape)
 
 
-def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> int:
+def _refuse(t, name, dtype=None, device=True):
+    """Raise what is wrong with tensor argument `name`: the three refusals of a tensor, stated here and nowhere else, tried in this
+    order -- not a tensor; not on the device (unless device=False: judged later); not of `dtype` (if one is given).  Callers test the
+    conditions inline, so a well-formed call pays for no message and no frame."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a torch.Tensor")
-    if not t.is_cuda:
+    if device and not t.is_cuda:
         raise RuntimeError(f"{name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-    if t.dtype != dtype:
+    if dtype is not None and t.dtype != dtype:
         raise RuntimeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {t.dtype}")
+
+
+def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> int:
+    """data_ptr() of one device tensor of `dtype` (contiguity is the caller's business)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+        _refuse(t, name, dtype)
     return t.data_ptr()
+
+
+def _tensors(who, fp32="cast", **named):
+    """The contiguous device tensors an entry takes, in the order given (shapes are the caller's business).  who: the prefix of the
+    message, or None for the bare name.  fp32 = "cast": the device is judged tensor by tensor, then each is widened to fp32 (a loss
+    term reads a mask or a half map as fp32); "insist": every tensor must be fp32 already, judged for all of them before any device
+    (a position in half precision is another position); None: the dtypes are the caller's business."""
+    if fp32 == "insist":
+        for name, t in named.items():
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                _refuse(t, f"{who}: {name}" if who else name, torch.float32, device=False)
+    out = []
+    for name, t in named.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            _refuse(t, f"{who}: {name}" if who else name)
+        out.append(t.float().contiguous() if fp32 == "cast" else t.contiguous())
+    return out
+
+
+def _optional(**named):
+    """_tensors (bare names, cast to fp32) over arguments that may be None: None stays None."""
+    return [t if t is None else _tensors(None, **{name: t})[0] for name, t in named.items()]
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
 
 
 # the element types of the half-precision reductions (pdepth_dpv_reduce_ex_lp): torch dtype -> PDEPTH_DTYPE_*
@@ -268,30 +303,42 @@ def _stream(dev) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-class _on_device:
+_DEVICE_IS_CURRENT = contextlib.nullcontext()
+
+
+def _on_device(dev):
     """torch.cuda.device(dev) only when another device is current (the context manager costs more than a small sweep's launch)."""
+    return _DEVICE_IS_CURRENT if dev.index is None or torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
-    def __init__(self, dev):
-        self.ctx = None if dev.index is None or torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
+def _call(name, dev, *args):
+    """C entry `name` on torch's current stream of `dev`: resolved through _entry, the device made current only if it is not, the
+    stream appended as the last argument, the return code checked."""
+    lib = _lib if _lib is not None else load()
+    with _on_device(dev):
+        rc = _entry(lib, name)(*args, _stream(dev))
+    _check(rc, lib)
 
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            return self.ctx.__exit__(*exc)
-        return False
+
+def _ask(name, *args):
+    """What a C entry that takes no stream answers: a workspace size, a layout, an exponent."""
+    return _entry(_lib if _lib is not None else load(), name)(*args)
+
+
+def _workspace(nbytes, dev):
+    """(tensor | None, nbytes) of an entry's workspace: None at zero bytes, which the size queries answer only for sizes the entry
+    refuses before it looks at its workspace."""
+    return (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes) if nbytes else (None, 0)
 
 
 _desc_cache = {}   # (B, V, C, D, H, W, metric, algo) -> (workspace bytes, staging layout): two library calls saved per sweep
 
 
-def _workspace_and_layout(lib, desc):
+def _workspace_and_layout(desc):
     key = (desc.B, desc.V, desc.C, desc.D, desc.H, desc.W, desc.metric, desc.algo)
     hit = _desc_cache.get(key)
     if hit is None:
-        hit = (lib.pdepth_sweep_workspace_bytes(ctypes.byref(desc)), lib.pdepth_sweep_source_layout(ctypes.byref(desc)))
+        hit = (_ask("pdepth_sweep_workspace_bytes", ctypes.byref(desc)), _ask("pdepth_sweep_source_layout", ctypes.byref(desc)))
         if len(_desc_cache) < 4096:
             _desc_cache[key] = hit
     return hit
@@ -323,9 +370,8 @@ def _blas(blas_mode):
 
 def selected_kernel(B, V, C, D, H, W, metric=METRIC_L2, algo=ALGO_AUTO):
     """Name of the sweep kernel family a descriptor selects ('dist' | 'tiled' | 'direct'): pdepth_sweep_source_layout."""
-    lib = load()
     desc = SweepDesc(B, V, C, D, H, W, int(metric), int(algo), BLAS_FMA, 1.0, C * H * W, V * C * H * W, C * H * W)
-    return {LAYOUT_DIST16: "dist", LAYOUT_C4: "tiled"}.get(lib.pdepth_sweep_source_layout(ctypes.byref(desc)), "direct")
+    return {LAYOUT_DIST16: "dist", LAYOUT_C4: "tiled"}.get(_ask("pdepth_sweep_source_layout", ctypes.byref(desc)), "direct")
 
 
 class PackedSource:
@@ -346,7 +392,6 @@ class PackedSource:
 def pack_source(src, n_planes=64, algo=ALGO_AUTO, metric=METRIC_L2):
     """src [B,V,C,H,W] fp32 device tensor -> PackedSource (n_planes and algo only select the kernel that will sweep it, like
     desc.D and desc.algo: the layout the distance-form kernel takes is mean-centred, the LDS-tiled kernel's is not)."""
-    lib = load()
     _no_autograd("pack_source", src)
     _dev(src, "src")
     if src.dim() != 5:
@@ -356,12 +401,9 @@ def pack_source(src, n_planes=64, algo=ALGO_AUTO, metric=METRIC_L2):
         src = src.contiguous()
     desc = SweepDesc(B, V, C, int(n_planes), H, W, int(metric), int(algo), BLAS_FMA, 1.0, C * H * W,
                      src.stride(0) if B > 1 else V * C * H * W, src.stride(1) if V > 1 else C * H * W)
-    ws_bytes = lib.pdepth_sweep_workspace_bytes(ctypes.byref(desc))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=src.device)
-    with torch.cuda.device(src.device):
-        rc = lib.pdepth_pack_source_f32(ctypes.byref(desc), _dev(src, "src"), ws.data_ptr(), ws_bytes, _stream(src.device))
-    _check(rc, lib)
-    return PackedSource(ws, (B, V, C, H, W), lib.pdepth_sweep_source_layout(ctypes.byref(desc)))
+    ws, ws_bytes = _workspace(_ask("pdepth_sweep_workspace_bytes", ctypes.byref(desc)), src.device)
+    _call("pdepth_pack_source_f32", src.device, ctypes.byref(desc), src.data_ptr(), _ptr(ws), ws_bytes)
+    return PackedSource(ws, (B, V, C, H, W), _ask("pdepth_sweep_source_layout", ctypes.byref(desc)))
 
 
 def pack_views(feat, rgb, n_views, n_planes=64):
@@ -369,7 +411,6 @@ def pack_views(feat, rgb, n_views, n_planes=64):
     item = the reference view), rgb [B*V1, 3, H, W] -> (PackedSource of the V1-1 source views with Cf+3 channels -- the
     pooled image appended like models/models.py:518-520 --, reference-view features [B, Cf+3, h, w]).  Raises for shapes
     the packed sweep does not take (callers fall back to cat + sweep)."""
-    lib = load()
     _no_autograd("pack_views", feat, rgb)
     _dev(feat, "feat"), _dev(rgb, "rgb")
     if feat.dim() != 4 or rgb.dim() != 4 or feat.shape[0] != rgb.shape[0] or rgb.shape[1] != 3 or feat.shape[0] % n_views:
@@ -383,14 +424,10 @@ def pack_views(feat, rgb, n_views, n_planes=64):
                                % (rgb.shape[2], rgb.shape[3], h, w))
     B, V, C = N // n_views, n_views - 1, Cf + 3
     desc = SweepDesc(B, V, C, int(n_planes), h, w, METRIC_L2, ALGO_AUTO, BLAS_FMA, 1.0, C * h * w, V * C * h * w, C * h * w)
-    ws_bytes = lib.pdepth_sweep_workspace_bytes(ctypes.byref(desc))
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=feat.device)
+    ws, ws_bytes = _workspace(_ask("pdepth_sweep_workspace_bytes", ctypes.byref(desc)), feat.device)
     ref = torch.empty((B, C, h, w), dtype=torch.float32, device=feat.device)
-    with torch.cuda.device(feat.device):
-        rc = lib.pdepth_pack_views_f32(ctypes.byref(desc), feat.data_ptr(), rgb.data_ptr(), rate, ref.data_ptr(), ws.data_ptr(),
-                                       ws_bytes, _stream(feat.device))
-    _check(rc, lib)
-    return PackedSource(ws, (B, V, C, h, w), lib.pdepth_sweep_source_layout(ctypes.byref(desc))), ref
+    _call("pdepth_pack_views_f32", feat.device, ctypes.byref(desc), feat.data_ptr(), rgb.data_ptr(), rate, ref.data_ptr(), _ptr(ws), ws_bytes)
+    return PackedSource(ws, (B, V, C, h, w), _ask("pdepth_sweep_source_layout", ctypes.byref(desc))), ref
 
 
 def sweep(ref, src, K, R, t, rays, cxcy, d_candi, sigma, metric=METRIC_L2, algo=ALGO_AUTO,
@@ -401,7 +438,6 @@ def sweep(ref, src, K, R, t, rays, cxcy, d_candi, sigma, metric=METRIC_L2, algo=
     R [B,V,3,3], t [B,V,3], rays [B,3,HW], cxcy [B,2], d_candi [D] -- fp32 device tensors.
     Returns (cost | None, logp | None, depth | None).
     """
-    lib = load()
     packed = src if isinstance(src, PackedSource) else None
     _no_autograd("sweep", ref, None if packed else src)
     _dev(ref, "ref")
@@ -433,7 +469,7 @@ def sweep(ref, src, K, R, t, rays, cxcy, d_candi, sigma, metric=METRIC_L2, algo=
                      ref.stride(0) if B > 1 else C * H * W,
                      (src.stride(0) if B > 1 else V * C * H * W) if not packed else V * C * H * W,
                      (src.stride(1) if V > 1 else C * H * W) if not packed else C * H * W)
-    ws_bytes, layout = _workspace_and_layout(lib, desc)
+    ws_bytes, layout = _workspace_and_layout(desc)
     if packed:
         if ws_bytes == 0 or packed.ws.numel() < ws_bytes:
             raise RuntimeError("sweep: this shape / algorithm does not run on a packed source")
@@ -442,23 +478,13 @@ def sweep(ref, src, K, R, t, rays, cxcy, d_candi, sigma, metric=METRIC_L2, algo=
                                "the algo / n_planes / metric it will be swept with" % (packed.layout, packed.centred))
         ws = packed.ws
     else:
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev) if ws_bytes else None
+        ws, ws_bytes = _workspace(ws_bytes, dev)
     cost = torch.empty((B, D, H, W), dtype=torch.float32, device=dev) if want_cost else None
     logp = torch.empty((B, D, H, W), dtype=torch.float32, device=dev) if want_logp else None
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
-    with _on_device(dev):
-        if packed:
-            rc = lib.pdepth_sweep_dpv_packed_f32(
-                ctypes.byref(desc), ctypes.byref(cam), _dev(ref, "ref"), _dev(d_candi, "d_candi"),
-                cost.data_ptr() if want_cost else None, logp.data_ptr() if want_logp else None,
-                depth.data_ptr() if want_depth else None, ws.data_ptr(), ws_bytes, _stream(dev))
-        else:
-            rc = lib.pdepth_sweep_dpv_f32(
-                ctypes.byref(desc), ctypes.byref(cam), _dev(ref, "ref"), _dev(src, "src"), _dev(d_candi, "d_candi"),
-                cost.data_ptr() if want_cost else None, logp.data_ptr() if want_logp else None,
-                depth.data_ptr() if want_depth else None, ws.data_ptr() if ws is not None else None, ws_bytes,
-                _stream(dev))
-    _check(rc, lib)
+    inputs = (ref.data_ptr(),) if packed else (ref.data_ptr(), src.data_ptr())   # (the packed entry reads the source from the workspace)
+    _call("pdepth_sweep_dpv_packed_f32" if packed else "pdepth_sweep_dpv_f32", dev, ctypes.byref(desc), ctypes.byref(cam), *inputs,
+          _dev(d_candi, "d_candi"), _ptr(cost), _ptr(logp), _ptr(depth), _ptr(ws), ws_bytes)
     del keep
     global _last_workspace
     _last_workspace = ws  # diagnostics only: tile flags of the last sweep (see fallback_tiles())
@@ -502,7 +528,6 @@ def fallback_tiles(B, H, W, gather_flag=1):
 
 def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
     """logits [B,D,H,W] -> (logp [B,D,H,W] | None, depth [B,H,W] | None)."""
-    lib = load()
     _no_autograd("dpv_reduce", logits)   # (in place it would also overwrite a tensor that carries a grad_fn)
     if isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in _LP_DTYPES:
         out = dpv_reduce_ex(logits, d_candi, None, want_logp, False, want_depth)   # (fp32 outputs: nothing to write in place)
@@ -513,15 +538,20 @@ def dpv_reduce(logits, d_candi, want_logp=True, want_depth=True, inplace=False):
     dev = logits.device
     logp = (logits if inplace else torch.empty_like(logits)) if want_logp else None
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
-    with torch.cuda.device(dev):
-        rc = lib.pdepth_dpv_reduce_f32(_dev(logits, "logits"), _dev(d_candi, "d_candi"), B, D, H, W,
-                                       logp.data_ptr() if want_logp else None,
-                                       depth.data_ptr() if want_depth else None, _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_dpv_reduce_f32", dev, logits.data_ptr(), _dev(d_candi, "d_candi"), B, D, H, W, _ptr(logp), _ptr(depth))
     return logp, depth
 
 
-def _dpv_reduce_ex_lp(lib, logits, d_candi, addend, want_logp, want_prob, want_depth, want_var, want_quarter, prob_dtype):
+def _reduce_ex_out(B, D, H, W, dev, logp, prob, want_depth, want_var, want_quarter):
+    """dict of the requested outputs of a dpv_reduce_ex call.  logp and prob are the caller's, a tensor or None (their dtype, and
+    whether logp is the input itself, differ between the fp32 and the half entry); the others are fp32 and made here."""
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"logp": logp, "prob": prob, "depth": f32(B, H, W) if want_depth else None, "var": f32(B, H, W) if want_var else None,
+           "quarter": f32(B, D, H // 4, W // 4) if want_quarter else None}
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def _dpv_reduce_ex_lp(logits, d_candi, addend, want_logp, want_prob, want_depth, want_var, want_quarter, prob_dtype):
     """dpv_reduce_ex on fp16 / bf16 logits (pdepth_dpv_reduce_ex_lp): every output fp32, prob in prob_dtype."""
     who, dtype = "dpv_reduce_ex", logits.dtype
     if addend is not None and logits.dim() == 4:
@@ -538,24 +568,11 @@ def _dpv_reduce_ex_lp(lib, logits, d_candi, addend, want_logp, want_prob, want_d
     B, D, H, W = _volume_dims(who, logits, d_candi, "logits")
     logits, d_candi = logits.contiguous(), d_candi.contiguous()
     dev = logits.device
-    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    out = {}
-    if want_logp:
-        out["logp"] = f32(B, D, H, W)
-    if want_prob:
-        out["prob"] = torch.empty_like(logits) if prob_lp else f32(B, D, H, W)
-    if want_depth:
-        out["depth"] = f32(B, H, W)
-    if want_var:
-        out["var"] = f32(B, H, W)
-    if want_quarter:
-        out["quarter"] = f32(B, D, H // 4, W // 4)
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    with torch.cuda.device(dev):
-        rc = _entry(lib, "pdepth_dpv_reduce_ex_lp")(_LP_DTYPES[dtype], logits.data_ptr(), addend.data_ptr() if addend is not None else None,
-                                                    _dev(d_candi, "d_candi"), B, D, H, W, ptr("logp"), ptr("prob"), int(prob_lp),
-                                                    ptr("depth"), ptr("var"), ptr("quarter"), _stream(dev))
-    _check(rc, lib)
+    f32 = lambda: torch.empty((B, D, H, W), dtype=torch.float32, device=dev)
+    out = _reduce_ex_out(B, D, H, W, dev, f32() if want_logp else None,
+                         (torch.empty_like(logits) if prob_lp else f32()) if want_prob else None, want_depth, want_var, want_quarter)
+    _call("pdepth_dpv_reduce_ex_lp", dev, _LP_DTYPES[dtype], logits.data_ptr(), _ptr(addend), _dev(d_candi, "d_candi"), B, D, H, W,
+          _ptr(out.get("logp")), _ptr(out.get("prob")), int(prob_lp), _ptr(out.get("depth")), _ptr(out.get("var")), _ptr(out.get("quarter")))
     return out
 
 
@@ -565,10 +582,9 @@ def dpv_reduce_ex(logits, d_candi, addend=None, want_logp=True, want_prob=False,
     [B,H,W], quarter = nearest quarter-resolution logp [B,D,H//4,W//4] -- one pass (pdepth_dpv_reduce_ex_f32).
     fp16 / bf16 logits (and addend, of the same dtype) are widened in the load (pdepth_dpv_reduce_ex_lp): the outputs are
     fp32, prob is fp32 or, with prob_dtype=logits.dtype, of that dtype; inplace is ignored there, the output being another type."""
-    lib = load()
     _no_autograd("dpv_reduce_ex", logits, addend)
     if isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype in _LP_DTYPES:
-        return _dpv_reduce_ex_lp(lib, logits, d_candi, addend, want_logp, want_prob, want_depth, want_var, want_quarter, prob_dtype)
+        return _dpv_reduce_ex_lp(logits, d_candi, addend, want_logp, want_prob, want_depth, want_var, want_quarter, prob_dtype)
     _dev(logits, "logits")
     if prob_dtype not in (None, torch.float32):
         raise RuntimeError(f"dpv_reduce_ex: prob_dtype must be torch.float32 or the logits' {logits.dtype}, got {prob_dtype}")
@@ -583,29 +599,15 @@ def dpv_reduce_ex(logits, d_candi, addend=None, want_logp=True, want_prob=False,
     B, D, H, W = _volume_dims("dpv_reduce_ex", logits, d_candi, "logits")
     logits, d_candi = logits.contiguous(), d_candi.contiguous()
     dev = logits.device
-    out = {}
-    if want_logp:
-        out["logp"] = logits if inplace else torch.empty_like(logits)
-    if want_prob:
-        out["prob"] = torch.empty_like(logits)
-    if want_depth:
-        out["depth"] = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    if want_var:
-        out["var"] = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    if want_quarter:
-        out["quarter"] = torch.empty((B, D, H // 4, W // 4), dtype=torch.float32, device=dev)
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    with torch.cuda.device(dev):
-        rc = lib.pdepth_dpv_reduce_ex_f32(_dev(logits, "logits"), addend.data_ptr() if addend is not None else None,
-                                          _dev(d_candi, "d_candi"), B, D, H, W, ptr("logp"), ptr("prob"), ptr("depth"),
-                                          ptr("var"), ptr("quarter"), _stream(dev))
-    _check(rc, lib)
+    out = _reduce_ex_out(B, D, H, W, dev, (logits if inplace else torch.empty_like(logits)) if want_logp else None,
+                         torch.empty_like(logits) if want_prob else None, want_depth, want_var, want_quarter)
+    _call("pdepth_dpv_reduce_ex_f32", dev, logits.data_ptr(), _ptr(addend), _dev(d_candi, "d_candi"), B, D, H, W,
+          _ptr(out.get("logp")), _ptr(out.get("prob")), _ptr(out.get("depth")), _ptr(out.get("var")), _ptr(out.get("quarter")))
     return out
 
 
 def ufield(dpv, d_candi, intr, mask, bv_log, unc_ang, z_start, z_end, min_depth, quash, d_sum=None):
     """dpv [B,D,H,W], intr [B,3,3], mask [B,H,W] | None -> (plane [B,D,W], depth_zero [B,H,W])  (pdepth_ufield_f32)."""
-    lib = load()
     _no_autograd("ufield", dpv)
     _dev(dpv, "dpv"), _dev(intr, "intr")
     if dpv.dim() != 4:
@@ -625,54 +627,41 @@ def ufield(dpv, d_candi, intr, mask, bv_log, unc_ang, z_start, z_end, min_depth,
     # sum formed by the caller on the host (ops.ufield); a caller that only has the candidates on the device pays one read-back.
     oob = (float(d_sum) if d_sum is not None else float(d_candi.sum().item())) if bv_log else 0.0
     dev = dpv.device
-    ws_bytes = lib.pdepth_ufield_workspace_bytes(B, H, W)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(_ask("pdepth_ufield_workspace_bytes", B, H, W), dev)
     plane = torch.empty((B, D, W), dtype=torch.float32, device=dev)
     dzero = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.pdepth_ufield_f32(_dev(dpv, "dpv"), _dev(d_candi, "d_candi"), intr.data_ptr(),
-                                   mask.data_ptr() if mask is not None else None, B, D, H, W, 1 if bv_log else 0,
-                                   float(unc_ang), float(np.float32(z_start)), float(np.float32(z_end)), float(min_depth),
-                                   1 if quash else 0, oob, plane.data_ptr(), dzero.data_ptr(), ws.data_ptr(), ws_bytes,
-                                   _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_ufield_f32", dev, dpv.data_ptr(), _dev(d_candi, "d_candi"), intr.data_ptr(), _ptr(mask), B, D, H, W, 1 if bv_log else 0,
+          float(unc_ang), float(np.float32(z_start)), float(np.float32(z_end)), float(min_depth), 1 if quash else 0, oob,
+          plane.data_ptr(), dzero.data_ptr(), _ptr(ws), ws_bytes)
     return plane, dzero
 
 
 def dpv_expect(dpv, d_candi, bv_log):
     """dpv [B,D,H,W] -> depth [B,H,W] = sum_k d_k * (exp(dpv) if bv_log else dpv)."""
-    lib = load()
     _no_autograd("dpv_expect", dpv)
     _dev(dpv, "dpv")
     B, D, H, W = _volume_dims("dpv_expect", dpv, d_candi, "dpv")
     dpv, d_candi = dpv.contiguous(), d_candi.contiguous()
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dpv.device)
-    with torch.cuda.device(dpv.device):
-        rc = lib.pdepth_dpv_expect_f32(_dev(dpv, "dpv"), _dev(d_candi, "d_candi"), B, D, H, W, int(bool(bv_log)),
-                                       depth.data_ptr(), _stream(dpv.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_expect_f32", dpv.device, dpv.data_ptr(), _dev(d_candi, "d_candi"), B, D, H, W, int(bool(bv_log)), depth.data_ptr())
     return depth
 
 
 def dpv_moments(dpv, d_candi, bv_log=True):
     """dpv [B,D,H,W] -> (mean [B,H,W], variance [B,H,W]) of the depth distribution."""
-    lib = load()
     _no_autograd("dpv_moments", dpv)
     _dev(dpv, "dpv")
     B, D, H, W = _volume_dims("dpv_moments", dpv, d_candi, "dpv")
     dpv, d_candi = dpv.contiguous(), d_candi.contiguous()
     mean = torch.empty((B, H, W), dtype=torch.float32, device=dpv.device)
     var = torch.empty_like(mean)
-    with torch.cuda.device(dpv.device):
-        rc = lib.pdepth_dpv_moments_f32(_dev(dpv, "dpv"), _dev(d_candi, "d_candi"), B, D, H, W, int(bool(bv_log)),
-                                        mean.data_ptr(), var.data_ptr(), _stream(dpv.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_moments_f32", dpv.device, dpv.data_ptr(), _dev(d_candi, "d_candi"), B, D, H, W, int(bool(bv_log)),
+          mean.data_ptr(), var.data_ptr())
     return mean, var
 
 
 def warp_feature(src, K, R, t, rays, cxcy, d_candi, blas_mode=None):
     """src [B,V,D,H,W] -> out [B,V,D,H,W], channel i warped with depth plane i."""
-    lib = load()
     _no_autograd("warp_feature", src)
     _dev(src, "src")
     if src.dim() != 5:
@@ -686,10 +675,7 @@ def warp_feature(src, K, R, t, rays, cxcy, d_candi, blas_mode=None):
     desc = SweepDesc(B, V, C, D, H, W, 0, 0, _blas(blas_mode), 1.0, 0, src.stride(0) if B > 1 else V * C * H * W,
                      src.stride(1) if V > 1 else C * H * W)
     out = torch.empty((B, V, D, H, W), dtype=torch.float32, device=src.device)
-    with torch.cuda.device(src.device):
-        rc = lib.pdepth_warp_feature_f32(ctypes.byref(desc), ctypes.byref(cam), _dev(src, "src"),
-                                         _dev(d_candi, "d_candi"), out.data_ptr(), _stream(src.device))
-    _check(rc, lib)
+    _call("pdepth_warp_feature_f32", src.device, ctypes.byref(desc), ctypes.byref(cam), src.data_ptr(), _dev(d_candi, "d_candi"), out.data_ptr())
     del keep
     return out
 
@@ -701,7 +687,6 @@ def warp_feature_backward(g_out, K, R, t, rays, cxcy, d_candi, blas_mode=None, d
     element, allocated here -- the same bits from call to call (a non-finite g_out makes that item's g_src NaN throughout:
     include/pdepth.h)."""
     who = "warp_feature_backward"
-    lib = load()
     _dev(g_out, "g_out")
     if g_out.dim() != 5:
         raise RuntimeError(f"{who}: g_out must be [B,V,D,H,W]")
@@ -714,13 +699,11 @@ def warp_feature_backward(g_out, K, R, t, rays, cxcy, d_candi, blas_mode=None, d
     g_src = torch.empty_like(g_out)
     dev = g_out.device
     args = (ctypes.byref(desc), ctypes.byref(cam), _dev(d_candi, "d_candi"), g_out.data_ptr(), g_src.data_ptr())
-    with _on_device(dev):
-        if deterministic:
-            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_warp_feature_backward_det_workspace_bytes")(ctypes.byref(desc)), dev)
-            rc = _entry(lib, "pdepth_warp_feature_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
-        else:
-            rc = _entry(lib, "pdepth_warp_feature_backward_f32")(*args, _stream(dev))
-    _check(rc, lib)
+    if deterministic:
+        ws, ws_bytes = _workspace(_ask("pdepth_warp_feature_backward_det_workspace_bytes", ctypes.byref(desc)), dev)
+        _call("pdepth_warp_feature_backward_det_f32", dev, *args, _ptr(ws), ws_bytes)
+    else:
+        _call("pdepth_warp_feature_backward_f32", dev, *args)
     del keep
     return g_src
 
@@ -730,7 +713,6 @@ def sample_coords(K, R, t, rays, cxcy, d_candi, H, W, blas_mode=None, algo=ALGO_
 
     algo selects the arithmetic of the sweep kernel of the same name: ALGO_AUTO = the shared-reciprocal divide
     chain of the LDS-tiled kernel, ALGO_DIRECT = the compiler's IEEE divides of the gather kernel."""
-    lib = load()
     _dev(K, "K")
     B, V = R.shape[0], R.shape[1]
     d_candi = d_candi.contiguous()
@@ -739,17 +721,13 @@ def sample_coords(K, R, t, rays, cxcy, d_candi, H, W, blas_mode=None, algo=ALGO_
     desc = SweepDesc(B, V, 1, D, H, W, 0, int(algo), _blas(blas_mode), 1.0, 0, 0, H * W)
     ix = torch.empty((B, V, D, H, W), dtype=torch.float32, device=K.device)
     iy = torch.empty_like(ix)
-    with torch.cuda.device(K.device):
-        rc = lib.pdepth_sample_coords_f32(ctypes.byref(desc), ctypes.byref(cam), _dev(d_candi, "d_candi"),
-                                          ix.data_ptr(), iy.data_ptr(), _stream(K.device))
-    _check(rc, lib)
+    _call("pdepth_sample_coords_f32", K.device, ctypes.byref(desc), ctypes.byref(cam), _dev(d_candi, "d_candi"), ix.data_ptr(), iy.data_ptr())
     del keep
     return ix, iy
 
 
 def dpv_fuse(logp, dmaps, masks, d_candi, var, eps, want_fused=True, want_log=True):
     """logp [B,D,H,W], dmaps [B,H,W], masks [B,H,W] -> (fused | None, log fused | None)."""
-    lib = load()
     _no_autograd("dpv_fuse", logp)
     _dev(logp, "logp")
     logp, dmaps, masks, d_candi = (t.contiguous() for t in (logp, dmaps, masks, d_candi))
@@ -758,20 +736,16 @@ def dpv_fuse(logp, dmaps, masks, d_candi, var, eps, want_fused=True, want_log=Tr
         raise RuntimeError("dpv_fuse: dmaps/masks must be [B,H,W] and d_candi [D]")
     fused = torch.empty_like(logp) if want_fused else None
     logf = torch.empty_like(logp) if want_log else None
-    with torch.cuda.device(logp.device):
-        rc = lib.pdepth_dpv_fuse_f32(_dev(logp, "logp"), _dev(dmaps, "dmaps"), _dev(masks, "masks"),
-                                     _dev(d_candi, "d_candi"), B, D, H, W, float(var), float(eps),
-                                     fused.data_ptr() if want_fused else None, logf.data_ptr() if want_log else None,
-                                     _stream(logp.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_fuse_f32", logp.device, logp.data_ptr(), _dev(dmaps, "dmaps"), _dev(masks, "masks"), _dev(d_candi, "d_candi"),
+          B, D, H, W, float(var), float(eps), _ptr(fused), _ptr(logf))
     return fused, logf
 
 
-def _corr_out_shape(lib, H, W, pad_size, kernel_size, max_displacement, stride1, stride2):
+def _corr_out_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2):
     oc, oh, ow = c_int32(), c_int32(), c_int32()
-    rc = lib.pdepth_correlation_output_size(H, W, int(pad_size), int(kernel_size), int(max_displacement), int(stride1), int(stride2),
-                                            ctypes.byref(oc), ctypes.byref(oh), ctypes.byref(ow))
-    _check(rc, lib)
+    rc = _ask("pdepth_correlation_output_size", H, W, int(pad_size), int(kernel_size), int(max_displacement), int(stride1), int(stride2),
+              ctypes.byref(oc), ctypes.byref(oh), ctypes.byref(ow))
+    _check(rc, load())
     return oc.value, oh.value, ow.value
 
 
@@ -793,42 +767,34 @@ def _dev_any(t, name):
 def correlation_forward(x1, x2, pad_size, kernel_size, max_displacement, stride1, stride2, corr_multiply=1):
     """x1, x2 [B,C,H,W] fp32 or fp16 -> [B,(2*(d/s2)+1)^2,oH,oW] of the same dtype (mean over the kernel window and C of
     shifted products; every configuration of the reference's kernel: include/pdepth.h)."""
-    lib = load()
     _dev_any(x1, "input1"), _dev_any(x2, "input2")
     if x1.shape != x2.shape or x1.dim() != 4:
         raise RuntimeError("correlation: inputs must be two [B,C,H,W] tensors of the same shape")
     half = _corr_dtype(x1, x2)
     x1, x2 = x1.contiguous(), x2.contiguous()
     B, C, H, W = x1.shape
-    oc, oh, ow = _corr_out_shape(lib, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)
+    oc, oh, ow = _corr_out_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2)
     out = torch.empty((B, oc, oh, ow), dtype=x1.dtype, device=x1.device)
-    fn = lib.pdepth_correlation_forward_f16 if half else lib.pdepth_correlation_forward_f32
-    with torch.cuda.device(x1.device):
-        rc = fn(x1.data_ptr(), x2.data_ptr(), B, C, H, W, int(pad_size), int(kernel_size), int(max_displacement), int(stride1),
-                int(stride2), int(corr_multiply), out.data_ptr(), _stream(x1.device))
-    _check(rc, lib)
+    _call("pdepth_correlation_forward_f16" if half else "pdepth_correlation_forward_f32", x1.device, x1.data_ptr(), x2.data_ptr(), B, C, H, W,
+          int(pad_size), int(kernel_size), int(max_displacement), int(stride1), int(stride2), int(corr_multiply), out.data_ptr())
     return out
 
 
 def correlation_backward(x1, x2, grad_out, pad_size, kernel_size, max_displacement, stride1, stride2, corr_multiply=1,
                          want1=True, want2=True):
     """x1, x2 [B,C,H,W], grad_out [B,(2r+1)^2,oH,oW] (fp32 or fp16, all alike) -> (grad_x1 | None, grad_x2 | None)."""
-    lib = load()
     _dev_any(x1, "input1"), _dev_any(x2, "input2"), _dev_any(grad_out, "grad_output")
     half = _corr_dtype(x1, x2)
     x1, x2, grad_out = x1.contiguous(), x2.contiguous(), grad_out.contiguous().to(x1.dtype)
     B, C, H, W = x1.shape
-    oc, oh, ow = _corr_out_shape(lib, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)
+    oc, oh, ow = _corr_out_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2)
     if x2.shape != x1.shape or tuple(grad_out.shape) != (B, oc, oh, ow):
         raise RuntimeError("correlation_backward: shape mismatch")
     g1 = torch.empty_like(x1) if want1 else None
     g2 = torch.empty_like(x2) if want2 else None
-    fn = lib.pdepth_correlation_backward_f16 if half else lib.pdepth_correlation_backward_f32
-    with torch.cuda.device(x1.device):
-        rc = fn(x1.data_ptr(), x2.data_ptr(), grad_out.data_ptr(), B, C, H, W, int(pad_size), int(kernel_size),
-                int(max_displacement), int(stride1), int(stride2), int(corr_multiply),
-                g1.data_ptr() if want1 else None, g2.data_ptr() if want2 else None, _stream(x1.device))
-    _check(rc, lib)
+    _call("pdepth_correlation_backward_f16" if half else "pdepth_correlation_backward_f32", x1.device, x1.data_ptr(), x2.data_ptr(),
+          grad_out.data_ptr(), B, C, H, W, int(pad_size), int(kernel_size), int(max_displacement), int(stride1), int(stride2),
+          int(corr_multiply), _ptr(g1), _ptr(g2))
     return g1, g2
 
 
@@ -837,7 +803,6 @@ SAMPLE_MODES = {"bilinear": 0, "nearest": 1}
 
 def inverse_warp(img, depth, Kinv, proj, mode="bilinear"):
     """img [B,C,H,W], depth [B,H,W], Kinv [B,3,3], proj [B,3,4] -> (warped [B,C,H,W], valid bool [B,H,W])."""
-    lib = load()
     _dev(img, "img")
     img, depth, Kinv, proj = (t.contiguous() for t in (img, depth, Kinv, proj))
     B, C, H, W = img.shape
@@ -845,22 +810,14 @@ def inverse_warp(img, depth, Kinv, proj, mode="bilinear"):
         raise RuntimeError("inverse_warp: expected depth [B,H,W], Kinv [B,3,3], proj [B,3,4]")
     out = torch.empty_like(img)
     valid = torch.empty((B, H, W), dtype=torch.uint8, device=img.device)
-    with torch.cuda.device(img.device):
-        rc = lib.pdepth_inverse_warp_f32(_dev(img, "img"), _dev(depth, "depth"), _dev(Kinv, "Kinv"), _dev(proj, "proj"),
-                                         B, C, H, W, SAMPLE_MODES[mode], out.data_ptr(), valid.data_ptr(), _stream(img.device))
-    _check(rc, lib)
+    _call("pdepth_inverse_warp_f32", img.device, img.data_ptr(), _dev(depth, "depth"), _dev(Kinv, "Kinv"), _dev(proj, "proj"),
+          B, C, H, W, SAMPLE_MODES[mode], out.data_ptr(), valid.data_ptr())
     return out, valid.bool()
-
-
-def _det_workspace(nbytes, dev):
-    """The workspace of a deterministic backward (the int64 accumulator + the per-item header), or (None, 0)."""
-    return (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes) if nbytes else (None, 0)
 
 
 def inverse_warp_backward(img, depth, Kinv, proj, grad_out, mode="bilinear", want_img=True, want_point=True, deterministic=False):
     """-> (grad_img [B,C,H,W] | None, grad_point [B,3,H,W] | None): pdepth_inverse_warp_backward_f32; deterministic:
     pdepth_inverse_warp_backward_det_f32 (grad_img as an order-independent sum; grad_point has the same bits either way)."""
-    lib = load()
     img, depth, Kinv, proj, grad_out = (t.contiguous() for t in (img, depth, Kinv, proj, grad_out))
     B, C, H, W = img.shape
     if tuple(grad_out.shape) != (B, C, H, W):
@@ -868,15 +825,12 @@ def inverse_warp_backward(img, depth, Kinv, proj, grad_out, mode="bilinear", wan
     g_img = torch.empty_like(img) if want_img else None
     g_pt = torch.empty((B, 3, H, W), dtype=torch.float32, device=img.device) if want_point else None
     args = (_dev(img, "img"), _dev(depth, "depth"), _dev(Kinv, "Kinv"), _dev(proj, "proj"), _dev(grad_out, "grad_out"), B, C, H, W,
-            SAMPLE_MODES[mode], g_img.data_ptr() if want_img else None, g_pt.data_ptr() if want_point else None)
-    with torch.cuda.device(img.device):
-        if deterministic:
-            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_inverse_warp_backward_det_workspace_bytes")(B, C, H, W) if want_img else 0,
-                                          img.device)
-            rc = _entry(lib, "pdepth_inverse_warp_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(img.device))
-        else:
-            rc = lib.pdepth_inverse_warp_backward_f32(*args, _stream(img.device))
-    _check(rc, lib)
+            SAMPLE_MODES[mode], _ptr(g_img), _ptr(g_pt))
+    if deterministic:
+        ws, ws_bytes = _workspace(_ask("pdepth_inverse_warp_backward_det_workspace_bytes", B, C, H, W) if want_img else 0, img.device)
+        _call("pdepth_inverse_warp_backward_det_f32", img.device, *args, _ptr(ws), ws_bytes)
+    else:
+        _call("pdepth_inverse_warp_backward_f32", img.device, *args)
     return g_img, g_pt
 
 
@@ -905,7 +859,6 @@ def sweep_backward(ref, src, K, R, t, rays, cxcy, d_candi, grad_cost, sigma, met
     if grad_cost.dim() != 4 or grad_cost.shape[1] != D:
         raise RuntimeError(f"{who}: grad_cost has {grad_cost.shape[1] if grad_cost.dim() == 4 else '?'} planes, d_candi has {D} entries")
     _shape(grad_cost, (B, D, H, W), "grad_cost", who)
-    lib = load()
     _dev(ref, "ref"), _dev(src, "src"), _dev(grad_cost, "grad_cost"), _dev(d_candi, "d_candi")
     ref, src, d_candi, grad_cost = ref.contiguous(), src.contiguous(), d_candi.contiguous(), grad_cost.contiguous()
     cam, keep = _camera(K, R, t, rays, cxcy, B, V, H * W)
@@ -914,41 +867,47 @@ def sweep_backward(ref, src, K, R, t, rays, cxcy, d_candi, grad_cost, sigma, met
     g_src = torch.empty_like(src) if want_src else None
     dev = ref.device
     args = (ctypes.byref(desc), ctypes.byref(cam), ref.data_ptr(), src.data_ptr(), d_candi.data_ptr(), grad_cost.data_ptr(),
-            g_ref.data_ptr() if want_ref else None, g_src.data_ptr() if want_src else None)
-    with _on_device(dev):
-        if deterministic:
-            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_sweep_backward_det_workspace_bytes")(ctypes.byref(desc)) if want_src else 0, dev)
-            rc = _entry(lib, "pdepth_sweep_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
-        else:
-            rc = lib.pdepth_sweep_backward_f32(*args, _stream(dev))
-    _check(rc, lib)
+            _ptr(g_ref), _ptr(g_src))
+    if deterministic:
+        ws, ws_bytes = _workspace(_ask("pdepth_sweep_backward_det_workspace_bytes", ctypes.byref(desc)) if want_src else 0, dev)
+        _call("pdepth_sweep_backward_det_f32", dev, *args, _ptr(ws), ws_bytes)
+    else:
+        _call("pdepth_sweep_backward_f32", dev, *args)
     del keep
     return g_ref, g_src
 
 
-def dpv_reduce_backward(logp, d_candi, g_logp=None, g_prob=None, g_depth=None):
-    """Saved logp [B,D,H,W] + any of g_logp, g_prob [B,D,H,W], g_depth [B,H,W] -> g_logits [B,D,H,W]
-    (pdepth_dpv_reduce_backward_f32)."""
-    who = "dpv_reduce_backward"
+def _grad(g, name, keep=None):
+    """An optional incoming gradient: None, or the contiguous fp32 device tensor of it (left in dtype `keep` if it comes in that)."""
+    if g is None:
+        return None
+    dtype = keep if g.dtype == keep else torch.float32
+    g = g.contiguous().to(dtype)
+    _dev(g, name, dtype)
+    return g
+
+
+def _reduce_backward_args(who, logp, d_candi, g_logp, g_prob, g_depth):
+    """((B, D, H, W), logp, d_candi) of the two dpv_reduce backwards: some gradient comes in, each has the shape of its output (judged
+    where the tensors live), logp and d_candi are fp32 device tensors."""
     if g_logp is None and g_prob is None and g_depth is None:
         raise RuntimeError(f"{who}: no incoming gradient")
     B, D, H, W = _volume_dims(who, logp, d_candi, "logp")
     for nm, g, shp in (("g_logp", g_logp, (B, D, H, W)), ("g_prob", g_prob, (B, D, H, W)), ("g_depth", g_depth, (B, H, W))):
         if g is not None:
             _shape(g, shp, nm, who)
-    lib = load()
     _dev(logp, "logp"), _dev(d_candi, "d_candi")
-    logp, d_candi = logp.contiguous(), d_candi.contiguous()
-    gs = [None if g is None else g.contiguous().float() for g in (g_logp, g_prob, g_depth)]
-    for nm, g in zip(("g_logp", "g_prob", "g_depth"), gs):
-        if g is not None:
-            _dev(g, nm)
+    return (B, D, H, W), logp.contiguous(), d_candi.contiguous()
+
+
+def dpv_reduce_backward(logp, d_candi, g_logp=None, g_prob=None, g_depth=None):
+    """Saved logp [B,D,H,W] + any of g_logp, g_prob [B,D,H,W], g_depth [B,H,W] -> g_logits [B,D,H,W]
+    (pdepth_dpv_reduce_backward_f32)."""
+    (B, D, H, W), logp, d_candi = _reduce_backward_args("dpv_reduce_backward", logp, d_candi, g_logp, g_prob, g_depth)
+    g_logp, g_prob, g_depth = _grad(g_logp, "g_logp"), _grad(g_prob, "g_prob"), _grad(g_depth, "g_depth")
     out = torch.empty_like(logp)
-    with _on_device(logp.device):
-        rc = lib.pdepth_dpv_reduce_backward_f32(logp.data_ptr(), d_candi.data_ptr(), B, D, H, W,
-                                                *[None if g is None else g.data_ptr() for g in gs], out.data_ptr(),
-                                                _stream(logp.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_reduce_backward_f32", logp.device, logp.data_ptr(), d_candi.data_ptr(), B, D, H, W, _ptr(g_logp), _ptr(g_prob),
+          _ptr(g_depth), out.data_ptr())
     return out
 
 
@@ -958,30 +917,12 @@ def dpv_reduce_backward_lp(logp, d_candi, dtype, g_logp=None, g_prob=None, g_dep
     who = "dpv_reduce_backward_lp"
     if dtype not in _LP_DTYPES:
         raise RuntimeError(f"{who}: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
-    if g_logp is None and g_prob is None and g_depth is None:
-        raise RuntimeError(f"{who}: no incoming gradient")
-    B, D, H, W = _volume_dims(who, logp, d_candi, "logp")
-    for nm, g, shp in (("g_logp", g_logp, (B, D, H, W)), ("g_prob", g_prob, (B, D, H, W)), ("g_depth", g_depth, (B, H, W))):
-        if g is not None:
-            _shape(g, shp, nm, who)
-    lib = load()
-    _dev(logp, "logp"), _dev(d_candi, "d_candi")
-    logp, d_candi = logp.contiguous(), d_candi.contiguous()
-    g_logp, g_depth = [None if g is None else g.contiguous().float() for g in (g_logp, g_depth)]
+    (B, D, H, W), logp, d_candi = _reduce_backward_args(who, logp, d_candi, g_logp, g_prob, g_depth)
+    g_logp, g_depth, g_prob = _grad(g_logp, "g_logp"), _grad(g_depth, "g_depth"), _grad(g_prob, "g_prob", keep=dtype)
     prob_lp = g_prob is not None and g_prob.dtype == dtype
-    if g_prob is not None:
-        g_prob = g_prob.contiguous() if prob_lp else g_prob.contiguous().float()
-    for nm, g in (("g_logp", g_logp), ("g_depth", g_depth)):
-        if g is not None:
-            _dev(g, nm)
-    if g_prob is not None:
-        _dev(g_prob, "g_prob", dtype if prob_lp else torch.float32)
     out = torch.empty(logp.shape, dtype=dtype, device=logp.device)
-    ptr = lambda g: None if g is None else g.data_ptr()
-    with _on_device(logp.device):
-        rc = _entry(lib, "pdepth_dpv_reduce_backward_lp")(_LP_DTYPES[dtype], logp.data_ptr(), d_candi.data_ptr(), B, D, H, W, ptr(g_logp),
-                                                          ptr(g_prob), int(prob_lp), ptr(g_depth), out.data_ptr(), _stream(logp.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_reduce_backward_lp", logp.device, _LP_DTYPES[dtype], logp.data_ptr(), d_candi.data_ptr(), B, D, H, W, _ptr(g_logp),
+          _ptr(g_prob), int(prob_lp), _ptr(g_depth), out.data_ptr())
     return out
 
 
@@ -990,15 +931,11 @@ def dpv_expect_backward(dpv, d_candi, bv_log, g_depth):
     who = "dpv_expect_backward"
     B, D, H, W = _volume_dims(who, dpv, d_candi, "dpv")
     _shape(g_depth, (B, H, W), "g_depth", who)
-    lib = load()
     _dev(dpv, "dpv"), _dev(d_candi, "d_candi")
-    dpv, d_candi, g_depth = dpv.contiguous(), d_candi.contiguous(), g_depth.contiguous().float()
-    _dev(g_depth, "g_depth")
+    dpv, d_candi, g_depth = dpv.contiguous(), d_candi.contiguous(), _grad(g_depth, "g_depth")
     out = torch.empty_like(dpv)
-    with _on_device(dpv.device):
-        rc = lib.pdepth_dpv_expect_backward_f32(dpv.data_ptr(), d_candi.data_ptr(), B, D, H, W, int(bool(bv_log)), g_depth.data_ptr(),
-                                                out.data_ptr(), _stream(dpv.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_expect_backward_f32", dpv.device, dpv.data_ptr(), d_candi.data_ptr(), B, D, H, W, int(bool(bv_log)),
+          g_depth.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1015,19 +952,12 @@ def dpv_fuse_backward(logp, dmaps, masks, d_candi, var, eps, g_fused=None, g_log
     for nm, g in (("g_fused", g_fused), ("g_logfused", g_logfused)):
         if g is not None:
             _shape(g, (B, D, H, W), nm, who)
-    lib = load()
     _dev(logp, "logp"), _dev(dmaps, "dmaps"), _dev(masks, "masks"), _dev(d_candi, "d_candi")
     logp, dmaps, masks, d_candi = (t.contiguous() for t in (logp, dmaps, masks, d_candi))
-    gs = [None if g is None else g.contiguous().float() for g in (g_fused, g_logfused)]
-    for nm, g in zip(("g_fused", "g_logfused"), gs):
-        if g is not None:
-            _dev(g, nm)
+    g_fused, g_logfused = _grad(g_fused, "g_fused"), _grad(g_logfused, "g_logfused")
     out = torch.empty_like(logp)
-    with _on_device(logp.device):
-        rc = _entry(lib, "pdepth_dpv_fuse_backward_f32")(logp.data_ptr(), dmaps.data_ptr(), masks.data_ptr(), d_candi.data_ptr(),
-                                                         _ptr(gs[0]), _ptr(gs[1]), B, D, H, W, float(var), float(eps),
-                                                         out.data_ptr(), _stream(logp.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_fuse_backward_f32", logp.device, logp.data_ptr(), dmaps.data_ptr(), masks.data_ptr(), d_candi.data_ptr(),
+          _ptr(g_fused), _ptr(g_logfused), B, D, H, W, float(var), float(eps), out.data_ptr())
     return out
 
 
@@ -1046,38 +976,23 @@ def _soft_ce_args(who, logp, d_candi, label, depth_gt, variance, mask, pow):
     if mask is not None:
         _shape(mask, (B, H, W), "mask", who)
     _dev(logp, "logp"), _dev(d_candi, "d_candi")
-    opt = []
-    for nm, t in (("label", label), ("depth_gt", depth_gt), ("mask", mask)):
-        if t is not None:
-            if not t.is_cuda:
-                raise RuntimeError(f"{nm}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-            t = t.contiguous().float()
-        opt.append(t)
+    label, depth_gt, mask = _optional(label=label, depth_gt=depth_gt, mask=mask)
     var = float(variance) if depth_gt is not None else 0.0
-    return (B, D, H, W), logp.contiguous(), d_candi.contiguous(), opt[0], opt[1], opt[2], var, float(pow)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return (B, D, H, W), logp.contiguous(), d_candi.contiguous(), label, depth_gt, mask, var, float(pow)
 
 
 def dpv_soft_ce(logp, d_candi, label=None, depth_gt=None, variance=None, mask=None, want_depth=False, pow=2.0):
     """logp [B,D,H,W] + (label [B,D,H,W] | depth_gt [B,H,W], variance) [+ mask [B,H,W]] -> (loss [B], count [B], depth [B,H,W] |
     None): pdepth_dpv_soft_ce_f32 on the current stream, no host synchronisation."""
     who = "dpv_soft_ce"
-    lib = load()
     _no_autograd(who, logp)
     (B, D, H, W), logp, d_candi, label, depth_gt, mask, var, pw = _soft_ce_args(who, logp, d_candi, label, depth_gt, variance, mask, pow)
     dev = logp.device
     out = torch.empty((2, B), dtype=torch.float32, device=dev)
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
-    ws_bytes = _entry(lib, "pdepth_dpv_soft_ce_workspace_bytes")(B, H, W)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_dpv_soft_ce_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw, _ptr(mask),
-                                                   B, D, H, W, out[0].data_ptr(), out[1].data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
-                                                   _stream(dev))
-    _check(rc, lib)
+    ws, ws_bytes = _workspace(_ask("pdepth_dpv_soft_ce_workspace_bytes", B, H, W), dev)
+    _call("pdepth_dpv_soft_ce_f32", dev, logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw, _ptr(mask), B, D, H, W,
+          out[0].data_ptr(), out[1].data_ptr(), _ptr(depth), _ptr(ws), ws_bytes)
     return out[0], out[1], depth
 
 
@@ -1091,35 +1006,23 @@ def dpv_soft_ce_backward(logp, d_candi, count, label=None, depth_gt=None, varian
     _shape(count, (B,), "count", who)
     if g_loss is not None:
         _shape(g_loss, (B,), "g_loss", who)
-        g_loss = g_loss.contiguous().float()
-        _dev(g_loss, "g_loss")
+        g_loss = _grad(g_loss, "g_loss")
     if g_depth is not None:
         _shape(g_depth, (B, H, W), "g_depth", who)
-        g_depth = g_depth.contiguous().float()
-        _dev(g_depth, "g_depth")
+        g_depth = _grad(g_depth, "g_depth")
     count = count.contiguous()
-    _dev(count, "count")
-    lib = load()
     out = torch.empty_like(logp)
-    with _on_device(logp.device):
-        rc = _entry(lib, "pdepth_dpv_soft_ce_backward_f32")(logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw,
-                                                            _ptr(mask), count.data_ptr(), B, D, H, W, _ptr(g_loss), _ptr(g_depth),
-                                                            out.data_ptr(), _stream(logp.device))
-    _check(rc, lib)
+    _call("pdepth_dpv_soft_ce_backward_f32", logp.device, logp.data_ptr(), d_candi.data_ptr(), _ptr(label), _ptr(depth_gt), var, pw,
+          _ptr(mask), _dev(count, "count"), B, D, H, W, _ptr(g_loss), _ptr(g_depth), out.data_ptr())
     return out
 
 
 # ---- consistency and smoothness terms of the training loss (ops.depth_stereo_consistency ...) ----------------------------------
-def _maps(who, **named):
-    """Contiguous fp32 device tensors of a loss-term entry, in the order given (shapes are checked by the caller first)."""
-    out = []
-    for name, t in named.items():
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: {name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-        out.append(t.float().contiguous())
-    return out
+def _count_and_gradient(who, B, count, g_value):
+    """(count, g_value) of a loss term's backward, each [B]: the forward's count and the gradient of its value."""
+    _shape(count, (B,), "count", who)
+    _shape(g_value, (B,), "g_value", who)
+    return _tensors(who, count=count, g_value=g_value)
 
 
 def _map_dims(who, t, name, least=2):
@@ -1131,9 +1034,9 @@ def _map_dims(who, t, name, least=2):
     return B, H, W
 
 
-def _terms_out(lib, B, H, W, dev, rows=2):
-    ws_bytes = _entry(lib, "pdepth_loss_terms_workspace_bytes")(B, H, W)
-    return torch.empty((rows, B), dtype=torch.float32, device=dev), torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev), ws_bytes
+def _terms_out(B, H, W, dev, rows=2):
+    """(out [rows,B], workspace | None, its bytes) of a loss-term forward."""
+    return (torch.empty((rows, B), dtype=torch.float32, device=dev), *_workspace(_ask("pdepth_loss_terms_workspace_bytes", B, H, W), dev))
 
 
 def _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
@@ -1146,7 +1049,7 @@ def _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
     if tuple(pose_row.shape) not in ((B, 4), (1, 4)):
         raise RuntimeError(f"{who}: pose_row must be [{B}, 4] or [1, 4], got {list(pose_row.shape)}")
     batched = 1 if (pose_row.shape[0] == B and B > 1) else 0
-    return (B, H, W), batched, _maps(who, src_depth=src_depth, tgt_depth=tgt_depth, src_mask=src_mask, Kinv=Kinv, proj=proj,
+    return (B, H, W), batched, _tensors(who, src_depth=src_depth, tgt_depth=tgt_depth, src_mask=src_mask, Kinv=Kinv, proj=proj,
                                      pose_row=pose_row, intr=intr)
 
 
@@ -1155,13 +1058,10 @@ def loss_dsc(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr):
     who = "loss_dsc"
     _no_autograd(who, src_depth, tgt_depth)
     (B, H, W), batched, t = _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
-    lib = load()
     dev = t[0].device
-    out, ws, ws_bytes = _terms_out(lib, B, H, W, dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_dsc_f32")(*(x.data_ptr() for x in t[:6]), batched, t[6].data_ptr(), B, H, W, out[0].data_ptr(),
-                                                out[1].data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    out, ws, ws_bytes = _terms_out(B, H, W, dev)
+    _call("pdepth_loss_dsc_f32", dev, *(x.data_ptr() for x in t[:6]), batched, t[6].data_ptr(), B, H, W, out[0].data_ptr(),
+          out[1].data_ptr(), _ptr(ws), ws_bytes)
     return out[0], out[1]
 
 
@@ -1171,21 +1071,16 @@ def loss_dsc_backward(src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr
     pdepth_loss_dsc_backward_det_f32 (g_src_depth as an order-independent sum; g_tgt_depth has the same bits either way)."""
     who = "loss_dsc_backward"
     (B, H, W), batched, t = _dsc_args(who, src_depth, tgt_depth, src_mask, Kinv, proj, pose_row, intr)
-    _shape(count, (B,), "count", who)
-    _shape(g_value, (B,), "g_value", who)
-    count, g_value = _maps(who, count=count, g_value=g_value)
-    lib = load()
+    count, g_value = _count_and_gradient(who, B, count, g_value)
     dev = t[0].device
     g_src = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_src else None
     g_tgt = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_tgt else None
     args = (*(x.data_ptr() for x in t[:6]), batched, t[6].data_ptr(), count.data_ptr(), g_value.data_ptr(), B, H, W, _ptr(g_src), _ptr(g_tgt))
-    with _on_device(dev):
-        if deterministic:
-            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_loss_dsc_backward_det_workspace_bytes")(B, H, W) if want_src else 0, dev)
-            rc = _entry(lib, "pdepth_loss_dsc_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
-        else:
-            rc = _entry(lib, "pdepth_loss_dsc_backward_f32")(*args, _stream(dev))
-    _check(rc, lib)
+    if deterministic:
+        ws, ws_bytes = _workspace(_ask("pdepth_loss_dsc_backward_det_workspace_bytes", B, H, W) if want_src else 0, dev)
+        _call("pdepth_loss_dsc_backward_det_f32", dev, *args, _ptr(ws), ws_bytes)
+    else:
+        _call("pdepth_loss_dsc_backward_f32", dev, *args)
     return g_src, g_tgt
 
 
@@ -1195,7 +1090,7 @@ def _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
     _shape(tgt_rgb, (B, 3, H, W), "tgt_rgb", who)
     _shape(Kinv, (B, 3, 3), "Kinv", who)
     _shape(proj, (B, 3, 4), "proj", who)
-    return (B, H, W), _maps(who, src_rgb=src_rgb, tgt_rgb=tgt_rgb, tgt_depth=tgt_depth, Kinv=Kinv, proj=proj)
+    return (B, H, W), _tensors(who, src_rgb=src_rgb, tgt_rgb=tgt_rgb, tgt_depth=tgt_depth, Kinv=Kinv, proj=proj)
 
 
 def loss_rsc(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
@@ -1203,13 +1098,9 @@ def loss_rsc(src_rgb, tgt_rgb, tgt_depth, Kinv, proj):
     who = "loss_rsc"
     _no_autograd(who, tgt_depth)
     (B, H, W), t = _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
-    lib = load()
     dev = t[0].device
-    out, ws, ws_bytes = _terms_out(lib, B, H, W, dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_rsc_f32")(*(x.data_ptr() for x in t), B, H, W, out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(),
-                                                ws_bytes, _stream(dev))
-    _check(rc, lib)
+    out, ws, ws_bytes = _terms_out(B, H, W, dev)
+    _call("pdepth_loss_rsc_f32", dev, *(x.data_ptr() for x in t), B, H, W, out[0].data_ptr(), out[1].data_ptr(), _ptr(ws), ws_bytes)
     return out[0], out[1]
 
 
@@ -1217,16 +1108,10 @@ def loss_rsc_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count, g_value):
     """-> g_tgt_depth [B,H,W]: pdepth_loss_rsc_backward_f32."""
     who = "loss_rsc_backward"
     (B, H, W), t = _rsc_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj)
-    _shape(count, (B,), "count", who)
-    _shape(g_value, (B,), "g_value", who)
-    count, g_value = _maps(who, count=count, g_value=g_value)
-    lib = load()
+    count, g_value = _count_and_gradient(who, B, count, g_value)
     dev = t[0].device
     g = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_rsc_backward_f32")(*(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W,
-                                                         g.data_ptr(), _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_loss_rsc_backward_f32", dev, *(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W, g.data_ptr())
     return g
 
 
@@ -1253,15 +1138,11 @@ def loss_photo(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, ssim_weight, md=1):
     who = "loss_photo"
     _no_autograd(who, tgt_depth)
     (B, H, W), t = _photo_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, md)
-    lib = load()
     dev = t[0].device
-    ws_bytes = _entry(lib, "pdepth_loss_photo_workspace_bytes")(B, H, W)
+    ws, ws_bytes = _workspace(_ask("pdepth_loss_photo_workspace_bytes", B, H, W), dev)
     out = torch.empty((2, B), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_photo_f32")(*(x.data_ptr() for x in t), B, H, W, float(ssim_weight), md, out[0].data_ptr(),
-                                                  out[1].data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_loss_photo_f32", dev, *(x.data_ptr() for x in t), B, H, W, float(ssim_weight), md, out[0].data_ptr(), out[1].data_ptr(),
+          _ptr(ws), ws_bytes)
     return out[0], out[1]
 
 
@@ -1269,23 +1150,18 @@ def loss_photo_backward(src_rgb, tgt_rgb, tgt_depth, Kinv, proj, count, g_value,
     """-> g_tgt_depth [B,H,W]: pdepth_loss_photo_backward_f32."""
     who = "loss_photo_backward"
     (B, H, W), t = _photo_args(who, src_rgb, tgt_rgb, tgt_depth, Kinv, proj, md)
-    _shape(count, (B,), "count", who)
-    _shape(g_value, (B,), "g_value", who)
-    count, g_value = _maps(who, count=count, g_value=g_value)
-    lib = load()
+    count, g_value = _count_and_gradient(who, B, count, g_value)
     dev = t[0].device
     g = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_photo_backward_f32")(*(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W,
-                                                           float(ssim_weight), md, g.data_ptr(), _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_loss_photo_backward_f32", dev, *(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W,
+          float(ssim_weight), md, g.data_ptr())
     return g
 
 
 def _dc_args(who, large, small):
     B, H, W = _map_dims(who, large, "large", least=4)
     _shape(small, (B, H // 4, W // 4), "small", who)
-    return (B, H, W), _maps(who, large=large, small=small)
+    return (B, H, W), _tensors(who, large=large, small=small)
 
 
 def loss_dc(large, small):
@@ -1293,13 +1169,9 @@ def loss_dc(large, small):
     who = "loss_dc"
     _no_autograd(who, large, small)
     (B, H, W), (large, small) = _dc_args(who, large, small)
-    lib = load()
     dev = large.device
-    out, ws, ws_bytes = _terms_out(lib, B, H // 4, W // 4, dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_dc_f32")(large.data_ptr(), small.data_ptr(), B, H, W, out[0].data_ptr(), out[1].data_ptr(),
-                                               ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    out, ws, ws_bytes = _terms_out(B, H // 4, W // 4, dev)
+    _call("pdepth_loss_dc_f32", dev, large.data_ptr(), small.data_ptr(), B, H, W, out[0].data_ptr(), out[1].data_ptr(), _ptr(ws), ws_bytes)
     return out[0], out[1]
 
 
@@ -1307,16 +1179,11 @@ def loss_dc_backward(large, small, count, g_value, want_large=True, want_small=T
     """-> (g_large [B,H,W] | None, g_small [B,H/4,W/4] | None): pdepth_loss_dc_backward_f32."""
     who = "loss_dc_backward"
     (B, H, W), (large, small) = _dc_args(who, large, small)
-    _shape(count, (B,), "count", who)
-    _shape(g_value, (B,), "g_value", who)
-    count, g_value = _maps(who, count=count, g_value=g_value)
-    lib = load()
+    count, g_value = _count_and_gradient(who, B, count, g_value)
     g_large = torch.empty_like(large) if want_large else None
     g_small = torch.empty_like(small) if want_small else None
-    with _on_device(large.device):
-        rc = _entry(lib, "pdepth_loss_dc_backward_f32")(large.data_ptr(), small.data_ptr(), count.data_ptr(), g_value.data_ptr(), B, H, W,
-                                                        _ptr(g_large), _ptr(g_small), _stream(large.device))
-    _check(rc, lib)
+    _call("pdepth_loss_dc_backward_f32", large.device, large.data_ptr(), small.data_ptr(), count.data_ptr(), g_value.data_ptr(), B, H, W,
+          _ptr(g_large), _ptr(g_small))
     return g_large, g_small
 
 
@@ -1325,7 +1192,7 @@ def _smooth_args(who, depth, rgb):
     if tuple(rgb.shape) != (B, 3, H, W):
         raise RuntimeError(f"{who}: rgb must be {[B, 3, H, W]}, the size of the depth map, got {list(rgb.shape)}; the multi-scale form "
                            "is loss_blocks.edge_aware_smoothness_loss")
-    return (B, H, W), _maps(who, depth=depth, rgb=rgb)
+    return (B, H, W), _tensors(who, depth=depth, rgb=rgb)
 
 
 def loss_smooth(depth, rgb):
@@ -1333,13 +1200,9 @@ def loss_smooth(depth, rgb):
     who = "loss_smooth"
     _no_autograd(who, depth)
     (B, H, W), (depth, rgb) = _smooth_args(who, depth, rgb)
-    lib = load()
     dev = depth.device
-    out, ws, ws_bytes = _terms_out(lib, B, H, W, dev, rows=1)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_smooth_f32")(depth.data_ptr(), rgb.data_ptr(), B, H, W, out.data_ptr(), ws.data_ptr(), ws_bytes,
-                                                   _stream(dev))
-    _check(rc, lib)
+    out, ws, ws_bytes = _terms_out(B, H, W, dev, rows=1)
+    _call("pdepth_loss_smooth_f32", dev, depth.data_ptr(), rgb.data_ptr(), B, H, W, out.data_ptr(), _ptr(ws), ws_bytes)
     return out[0]
 
 
@@ -1348,13 +1211,9 @@ def loss_smooth_backward(depth, rgb, g_value):
     who = "loss_smooth_backward"
     (B, H, W), (depth, rgb) = _smooth_args(who, depth, rgb)
     _shape(g_value, (B,), "g_value", who)
-    (g_value,) = _maps(who, g_value=g_value)
-    lib = load()
+    (g_value,) = _tensors(who, g_value=g_value)
     g = torch.empty_like(depth)
-    with _on_device(depth.device):
-        rc = _entry(lib, "pdepth_loss_smooth_backward_f32")(depth.data_ptr(), rgb.data_ptr(), g_value.data_ptr(), B, H, W, g.data_ptr(),
-                                                            _stream(depth.device))
-    _check(rc, lib)
+    _call("pdepth_loss_smooth_backward_f32", depth.device, depth.data_ptr(), rgb.data_ptr(), g_value.data_ptr(), B, H, W, g.data_ptr())
     return g
 
 
@@ -1365,7 +1224,7 @@ SSIM_MD = (1, 2, 3)   # the window half-widths the kernels are built for
 def _ssim_args(who, x, y, md):
     """((B, C, H, W), x, y) of an SSIM call: two [B,C,H,W] device tensors of one shape, as contiguous fp32."""
     _check_md(who, md)
-    x, y = _maps(who, x=x, y=y)
+    x, y = _tensors(who, x=x, y=y)
     if x.dim() != 4 or x.shape != y.shape:
         raise RuntimeError(f"{who}: x and y must be two [B,C,H,W] tensors of one shape, got {list(x.shape)} and {list(y.shape)}")
     B, C, H, W = x.shape
@@ -1380,11 +1239,8 @@ def ssim(x, y, md=1):
     who = "ssim"
     _no_autograd(who, x, y)
     (B, C, H, W), x, y = _ssim_args(who, x, y, md)
-    lib = load()
     out = torch.empty((B, C, H - 2 * md, W - 2 * md), dtype=torch.float32, device=x.device)
-    with _on_device(x.device):
-        rc = _entry(lib, "pdepth_ssim_f32")(x.data_ptr(), y.data_ptr(), B, C, H, W, md, out.data_ptr(), _stream(x.device))
-    _check(rc, lib)
+    _call("pdepth_ssim_f32", x.device, x.data_ptr(), y.data_ptr(), B, C, H, W, md, out.data_ptr())
     return out
 
 
@@ -1393,16 +1249,12 @@ def ssim_backward(x, y, g_out, md=1, want_x=True, want_y=True):
     who = "ssim_backward"
     (B, C, H, W), x, y = _ssim_args(who, x, y, md)
     _shape(g_out, (B, C, H - 2 * md, W - 2 * md), "g_out", who)
-    (g_out,) = _maps(who, g_out=g_out)
+    (g_out,) = _tensors(who, g_out=g_out)
     if not (want_x or want_y):
         raise RuntimeError(f"{who}: no gradient requested")
-    lib = load()
     g_x = torch.empty_like(x) if want_x else None
     g_y = torch.empty_like(y) if want_y else None
-    with _on_device(x.device):
-        rc = _entry(lib, "pdepth_ssim_backward_f32")(x.data_ptr(), y.data_ptr(), g_out.data_ptr(), B, C, H, W, md, _ptr(g_x), _ptr(g_y),
-                                                     _stream(x.device))
-    _check(rc, lib)
+    _call("pdepth_ssim_backward_f32", x.device, x.data_ptr(), y.data_ptr(), g_out.data_ptr(), B, C, H, W, md, _ptr(g_x), _ptr(g_y))
     return g_x, g_y
 
 
@@ -1416,14 +1268,14 @@ def _ternary_args(who, x, y, md):
     _check_md(who, md)
     for name, t in (("x", x), ("y", y)):
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+            _refuse(t, f"{who}: {name}")
     if x.dim() != 4 or x.shape != y.shape:
         raise RuntimeError(f"{who}: x and y must be two [B,3,H,W] tensors of one shape, got {list(x.shape)} and {list(y.shape)}")
     B, C, H, W = x.shape
     if B < 1 or C != 3:
         raise RuntimeError(f"{who}: x and y must be [B,3,H,W] RGB images with B >= 1, got {list(x.shape)} and {list(y.shape)}")
     _check_md(who, md, "patch", H, W)
-    x, y = _maps(who, x=x, y=y)
+    x, y = _tensors(who, x=x, y=y)
     return (B, H, W), x, y
 
 
@@ -1432,11 +1284,8 @@ def ternary(x, y, md=1):
     who = "ternary"
     _no_autograd(who, x, y)
     (B, H, W), x, y = _ternary_args(who, x, y, md)
-    lib = load()
     out = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
-    with _on_device(x.device):
-        rc = _entry(lib, "pdepth_ternary_f32")(x.data_ptr(), y.data_ptr(), B, H, W, md, out.data_ptr(), _stream(x.device))
-    _check(rc, lib)
+    _call("pdepth_ternary_f32", x.device, x.data_ptr(), y.data_ptr(), B, H, W, md, out.data_ptr())
     return out
 
 
@@ -1445,16 +1294,12 @@ def ternary_backward(x, y, g_out, md=1, want_x=True, want_y=True):
     who = "ternary_backward"
     (B, H, W), x, y = _ternary_args(who, x, y, md)
     _shape(g_out, (B, 1, H, W), "g_out", who)
-    (g_out,) = _maps(who, g_out=g_out)
+    (g_out,) = _tensors(who, g_out=g_out)
     if not (want_x or want_y):
         raise RuntimeError(f"{who}: no gradient requested")
-    lib = load()
     g_x = torch.empty_like(x) if want_x else None
     g_y = torch.empty_like(y) if want_y else None
-    with _on_device(x.device):
-        rc = _entry(lib, "pdepth_ternary_backward_f32")(x.data_ptr(), y.data_ptr(), g_out.data_ptr(), B, H, W, md, _ptr(g_x), _ptr(g_y),
-                                                        _stream(x.device))
-    _check(rc, lib)
+    _call("pdepth_ternary_backward_f32", x.device, x.data_ptr(), y.data_ptr(), g_out.data_ptr(), B, H, W, md, _ptr(g_x), _ptr(g_y))
     return g_x, g_y
 
 
@@ -1466,32 +1311,13 @@ def _range_call(who, entry, head, B, H, W, th, want_range, want_visible, dev):
         raise RuntimeError(f"{who}: th is NaN")
     if not (want_range or want_visible):
         raise RuntimeError(f"{who}: no output requested")
-    lib = load()
     rng = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if want_range else None
     vis = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if want_visible else None
-    ws_bytes = _entry(lib, "pdepth_range_map_workspace_bytes")(B, H, W)
-    if ws_bytes == 0:
+    ws, ws_bytes = _workspace(_ask("pdepth_range_map_workspace_bytes", B, H, W), dev)
+    if ws is None:
         raise RuntimeError(f"{who}: B={B}, H={H}, W={W}: H*W must be at most 2^24 and B at most 65535")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, entry)(*head, B, H, W, th, _ptr(rng), _ptr(vis), ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    _call(entry, dev, *head, B, H, W, th, _ptr(rng), _ptr(vis), _ptr(ws), ws_bytes)
     return rng, vis
-
-
-def _fp32_maps(who, **named):
-    """Contiguous device tensors of a range-map entry, which must be fp32 already (a position in half precision is another position)."""
-    out = []
-    for name, t in named.items():
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{who}: {name}: expected float32, got {t.dtype}")
-    for name, t in named.items():
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: {name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-        out.append(t.contiguous())
-    return out
 
 
 def range_map(coords, th=0.2, want_range=True, want_visible=False):
@@ -1500,11 +1326,11 @@ def range_map(coords, th=0.2, want_range=True, want_visible=False):
     who = "range_map"
     _no_autograd(who, coords)
     if not isinstance(coords, torch.Tensor):
-        raise TypeError(f"{who}: coords: expected a torch.Tensor")
+        _refuse(coords, f"{who}: coords")
     if coords.dim() != 4 or coords.shape[1] != 2 or min(coords.shape) < 1:
         raise RuntimeError(f"{who}: coords must be [B,2,H,W] with B, H, W >= 1, got {list(coords.shape)}")
     B, _, H, W = coords.shape
-    (coords,) = _fp32_maps(who, coords=coords)
+    (coords,) = _tensors(who, "insist", coords=coords)
     return _range_call(who, "pdepth_range_map_f32", (coords.data_ptr(),), B, H, W, th, want_range, want_visible, coords.device)
 
 
@@ -1514,7 +1340,7 @@ def depth_range_map(depth, Kinv, proj, src_mask=None, th=0.2, want_range=True, w
     who = "depth_range_map"
     _no_autograd(who, depth, src_mask, Kinv, proj)
     if not isinstance(depth, torch.Tensor):
-        raise TypeError(f"{who}: depth: expected a torch.Tensor")
+        _refuse(depth, f"{who}: depth")
     B, H, W = _map_dims(who, depth, "depth")
     _shape(Kinv, (B, 3, 3), "Kinv", who)
     _shape(proj, (B, 3, 4), "proj", who)
@@ -1522,7 +1348,7 @@ def depth_range_map(depth, Kinv, proj, src_mask=None, th=0.2, want_range=True, w
     if src_mask is not None:
         _shape(src_mask, (B, H, W), "src_mask", who)
         named["src_mask"] = src_mask
-    t = _fp32_maps(who, **named)
+    t = _tensors(who, "insist", **named)
     head = (t[0].data_ptr(), _ptr(t[3] if src_mask is not None else None), t[1].data_ptr(), t[2].data_ptr())
     return _range_call(who, "pdepth_depth_range_map_f32", head, B, H, W, th, want_range, want_visible, t[0].device)
 
@@ -1538,14 +1364,14 @@ def _flow_args(who, x, flow, pad, xname="x", fname="flow"):
         raise RuntimeError(f"{who}: pad must be 'border' or 'zeros', got {pad!r}")
     for name, t in ((xname, x), (fname, flow)):
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+            _refuse(t, f"{who}: {name}")
     if x.dim() != 4 or min(x.shape) < 1:
         raise RuntimeError(f"{who}: {xname} must be [B,C,H,W] with B, C >= 1, got {list(x.shape)}")
     B, C, H, W = x.shape
     if H < 2 or W < 2:
         raise RuntimeError(f"{who}: H={H}, W={W}: the grid is normalised by H - 1 and W - 1, both must be at least 2")
     _shape(flow, (B, 2, H, W), fname, who)
-    x, flow = _fp32_maps(who, **{xname: x, fname: flow})
+    x, flow = _tensors(who, "insist", **{xname: x, fname: flow})
     return (B, C, H, W), x, flow, FLOW_PADS[pad]
 
 
@@ -1554,11 +1380,8 @@ def flow_warp(x, flow, pad="border"):
     who = "flow_warp"
     _no_autograd(who, x, flow)
     (B, C, H, W), x, flow, code = _flow_args(who, x, flow, pad)
-    lib = load()
     out = torch.empty_like(x)
-    with _on_device(x.device):
-        rc = _entry(lib, "pdepth_flow_warp_f32")(x.data_ptr(), flow.data_ptr(), B, C, H, W, code, out.data_ptr(), _stream(x.device))
-    _check(rc, lib)
+    _call("pdepth_flow_warp_f32", x.device, x.data_ptr(), flow.data_ptr(), B, C, H, W, code, out.data_ptr())
     return out
 
 
@@ -1568,21 +1391,18 @@ def flow_warp_backward(x, flow, grad_out, pad="border", want_x=True, want_flow=T
     who = "flow_warp_backward"
     (B, C, H, W), x, flow, code = _flow_args(who, x, flow, pad)
     _shape(grad_out, (B, C, H, W), "grad_out", who)
-    (grad_out,) = _fp32_maps(who, grad_out=grad_out)
+    (grad_out,) = _tensors(who, "insist", grad_out=grad_out)
     if not (want_x or want_flow):
         raise RuntimeError(f"{who}: no gradient requested")
-    lib = load()
     dev = x.device
     g_x = torch.empty_like(x) if want_x else None
     g_f = torch.empty_like(flow) if want_flow else None
     args = (x.data_ptr(), flow.data_ptr(), grad_out.data_ptr(), B, C, H, W, code, _ptr(g_x), _ptr(g_f))
-    with _on_device(dev):
-        if deterministic:
-            ws, ws_bytes = _det_workspace(_entry(lib, "pdepth_flow_warp_backward_det_workspace_bytes")(B, C, H, W) if want_x else 0, dev)
-            rc = _entry(lib, "pdepth_flow_warp_backward_det_f32")(*args, _ptr(ws), ws_bytes, _stream(dev))
-        else:
-            rc = _entry(lib, "pdepth_flow_warp_backward_f32")(*args, _stream(dev))
-    _check(rc, lib)
+    if deterministic:
+        ws, ws_bytes = _workspace(_ask("pdepth_flow_warp_backward_det_workspace_bytes", B, C, H, W) if want_x else 0, dev)
+        _call("pdepth_flow_warp_backward_det_f32", dev, *args, _ptr(ws), ws_bytes)
+    else:
+        _call("pdepth_flow_warp_backward_f32", dev, *args)
     return g_x, g_f
 
 
@@ -1593,12 +1413,9 @@ def flow_fb_check(flow12, flow21, scale=0.01, bias=0.5):
     if isinstance(flow12, torch.Tensor) and (flow12.dim() != 4 or flow12.shape[1] != 2):
         raise RuntimeError(f"{who}: flow12 must be [B,2,H,W], got {list(flow12.shape)}")
     (B, _, H, W), flow12, flow21, _ = _flow_args(who, flow12, flow21, "zeros", xname="flow12", fname="flow21")
-    lib = load()
     occ = torch.empty((B, 1, H, W), dtype=torch.float32, device=flow12.device)
-    with _on_device(flow12.device):
-        rc = _entry(lib, "pdepth_flow_fb_check_f32")(flow12.data_ptr(), flow21.data_ptr(), B, H, W, float(scale), float(bias),
-                                                     occ.data_ptr(), _stream(flow12.device))
-    _check(rc, lib)
+    _call("pdepth_flow_fb_check_f32", flow12.device, flow12.data_ptr(), flow21.data_ptr(), B, H, W, float(scale), float(bias),
+          occ.data_ptr())
     return occ
 
 
@@ -1615,7 +1432,7 @@ def _cost_volume_args(who, x1, x2, flow, max_displacement, negative_slope, pad):
     named = {"x1": x1, "x2": x2} if flow is None else {"x1": x1, "x2": x2, "flow": flow}
     for name, t in named.items():
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+            _refuse(t, f"{who}: {name}")
     if x1.dim() != 4 or min(x1.shape) < 1:
         raise RuntimeError(f"{who}: x1 must be [B,C,H,W] with every size >= 1, got {list(x1.shape)}")
     B, C, H, W = x1.shape
@@ -1624,7 +1441,7 @@ def _cost_volume_args(who, x1, x2, flow, max_displacement, negative_slope, pad):
         if H < 2 or W < 2:
             raise RuntimeError(f"{who}: H={H}, W={W}: the grid is normalised by H - 1 and W - 1, both must be at least 2 with a flow")
         _shape(flow, (B, 2, H, W), "flow", who)
-    t = _fp32_maps(who, **named)
+    t = _tensors(who, "insist", **named)
     return (B, C, H, W), t[0], t[1], (t[2] if flow is not None else None), md, slope, FLOW_PADS[pad]
 
 
@@ -1634,12 +1451,8 @@ def flow_cost_volume(x1, x2, flow=None, max_displacement=4, negative_slope=0.1, 
     who = "flow_cost_volume"
     _no_autograd(who, x1, x2, flow)
     (B, C, H, W), x1, x2, flow, md, slope, code = _cost_volume_args(who, x1, x2, flow, max_displacement, negative_slope, pad)
-    lib = load()
     out = torch.empty((B, (2 * md + 1) ** 2, H, W), dtype=torch.float32, device=x1.device)
-    with _on_device(x1.device):
-        rc = _entry(lib, "pdepth_flow_cost_volume_f32")(x1.data_ptr(), x2.data_ptr(), _ptr(flow), B, C, H, W, md, slope, code,
-                                                        out.data_ptr(), _stream(x1.device))
-    _check(rc, lib)
+    _call("pdepth_flow_cost_volume_f32", x1.device, x1.data_ptr(), x2.data_ptr(), _ptr(flow), B, C, H, W, md, slope, code, out.data_ptr())
     return out
 
 
@@ -1653,22 +1466,19 @@ def flow_cost_volume_backward(x1, x2, flow, out, grad_out, max_displacement=4, n
     nd2 = (2 * md + 1) ** 2
     _shape(out, (B, nd2, H, W), "out", who)
     _shape(grad_out, (B, nd2, H, W), "grad_out", who)
-    out, grad_out = _fp32_maps(who, out=out, grad_out=grad_out)
+    out, grad_out = _tensors(who, "insist", out=out, grad_out=grad_out)
     want_flow = bool(want_flow) and flow is not None
     if not (want_x1 or want_x2 or want_flow):
         raise RuntimeError(f"{who}: no gradient requested")
-    lib = load()
     dev = x1.device
     g1 = torch.empty_like(x1) if want_x1 else None
     g2 = torch.empty_like(x2) if want_x2 else None
     gf = torch.empty_like(flow) if want_flow else None
     name = "pdepth_flow_cost_volume_backward_det" if deterministic else "pdepth_flow_cost_volume_backward"
-    with _on_device(dev):
-        need = flow is not None and (want_x2 or want_flow)
-        ws, ws_bytes = _det_workspace(_entry(lib, name + "_workspace_bytes")(B, C, H, W, 1) if need else 0, dev)
-        rc = _entry(lib, name + "_f32")(x1.data_ptr(), x2.data_ptr(), _ptr(flow), out.data_ptr(), grad_out.data_ptr(), B, C, H, W, md, slope,
-                                        code, _ptr(g1), _ptr(g2), _ptr(gf), _ptr(ws), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    need = flow is not None and (want_x2 or want_flow)
+    ws, ws_bytes = _workspace(_ask(name + "_workspace_bytes", B, C, H, W, 1) if need else 0, dev)
+    _call(name + "_f32", dev, x1.data_ptr(), x2.data_ptr(), _ptr(flow), out.data_ptr(), grad_out.data_ptr(), B, C, H, W, md, slope, code,
+          _ptr(g1), _ptr(g2), _ptr(gf), _ptr(ws), ws_bytes)
     return g1, g2, gf
 
 
@@ -1680,7 +1490,7 @@ def _flow_photo_args(who, im, other, flow, mask, w_l1, w_ssim, w_ternary, pad):
     named = {"im": im, "other": other, "flow": flow, "mask": mask}
     for name, t in named.items():
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+            _refuse(t, f"{who}: {name}")
     if im.dim() != 4 or im.shape[0] < 1 or im.shape[1] != 3:
         raise RuntimeError(f"{who}: im must be [B,3,H,W] with B >= 1, got {list(im.shape)}")
     B, _, H, W = im.shape
@@ -1692,7 +1502,7 @@ def _flow_photo_args(who, im, other, flow, mask, w_l1, w_ssim, w_ternary, pad):
     _shape(other, (B, 3, H, W), "other", who)
     _shape(flow, (B, 2, H, W), "flow", who)
     _shape(mask, (B, 1, H, W), "mask", who)
-    return (B, H, W), tuple(_fp32_maps(who, **named)), weights, FLOW_PADS[pad]
+    return (B, H, W), tuple(_tensors(who, "insist", **named)), weights, FLOW_PADS[pad]
 
 
 def flow_photo(im, other, flow, mask, w_l1, w_ssim, w_ternary, pad="border"):
@@ -1701,15 +1511,11 @@ def flow_photo(im, other, flow, mask, w_l1, w_ssim, w_ternary, pad="border"):
     who = "flow_photo"
     _no_autograd(who, im, other, flow, mask)
     (B, H, W), t, weights, code = _flow_photo_args(who, im, other, flow, mask, w_l1, w_ssim, w_ternary, pad)
-    lib = load()
     dev = t[0].device
-    ws_bytes = _entry(lib, "pdepth_flow_photo_workspace_bytes")(B, H, W)
+    ws, ws_bytes = _workspace(_ask("pdepth_flow_photo_workspace_bytes", B, H, W), dev)
     out = torch.empty((2,), dtype=torch.float32, device=dev)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_flow_photo_f32")(*(x.data_ptr() for x in t), B, H, W, code, *weights, out[0].data_ptr(), out[1].data_ptr(),
-                                                  ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_flow_photo_f32", dev, *(x.data_ptr() for x in t), B, H, W, code, *weights, out[0].data_ptr(), out[1].data_ptr(),
+          _ptr(ws), ws_bytes)
     return out[0], out[1]
 
 
@@ -1720,28 +1526,25 @@ def flow_photo_backward(im, other, flow, mask, count, g_value, w_l1, w_ssim, w_t
     for name, v in (("count", count), ("g_value", g_value)):
         if v.numel() != 1:
             raise RuntimeError(f"{who}: {name} must have one element, got {list(v.shape)}")
-    count, g_value = _maps(who, count=count.reshape(1), g_value=g_value.reshape(1))
-    lib = load()
+    count, g_value = _tensors(who, count=count.reshape(1), g_value=g_value.reshape(1))
     dev = t[0].device
     g = torch.empty_like(t[2])
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_flow_photo_backward_f32")(*(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W, code,
-                                                           *weights, g.data_ptr(), _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_flow_photo_backward_f32", dev, *(x.data_ptr() for x in t), count.data_ptr(), g_value.data_ptr(), B, H, W, code, *weights,
+          g.data_ptr())
     return g
 
 
 def _smooth1_args(who, flo, image):
     for name, t in (("flo", flo), ("image", image)):
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: {name}: expected a torch.Tensor")
+            _refuse(t, f"{who}: {name}")
     if flo.dim() != 4 or image.dim() != 4 or min(flo.shape) < 1 or min(image.shape) < 1 or \
             (flo.shape[0],) + tuple(flo.shape[2:]) != (image.shape[0],) + tuple(image.shape[2:]):
         raise RuntimeError(f"{who}: flo [B,Cf,H,W] and image [B,Ci,H,W] must share B, H and W, got {list(flo.shape)} and {list(image.shape)}")
     B, Cf, H, W = flo.shape
     if H < 2 or W < 2:
         raise RuntimeError(f"{who}: H={H}, W={W}: both must be at least 2")
-    flo, image = _fp32_maps(who, flo=flo, image=image)
+    flo, image = _tensors(who, "insist", flo=flo, image=image)
     return (B, Cf, image.shape[1], H, W), flo, image
 
 
@@ -1750,15 +1553,10 @@ def loss_smooth1(flo, image, alpha):
     who = "loss_smooth1"
     _no_autograd(who, flo)
     (B, Cf, Ci, H, W), flo, image = _smooth1_args(who, flo, image)
-    lib = load()
     dev = flo.device
-    ws_bytes = _entry(lib, "pdepth_loss_terms_workspace_bytes")(B, H, W)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(_ask("pdepth_loss_terms_workspace_bytes", B, H, W), dev)
     out = torch.empty((1,), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_loss_smooth1_f32")(flo.data_ptr(), image.data_ptr(), B, Cf, Ci, H, W, float(alpha), out.data_ptr(),
-                                                    ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_loss_smooth1_f32", dev, flo.data_ptr(), image.data_ptr(), B, Cf, Ci, H, W, float(alpha), out.data_ptr(), _ptr(ws), ws_bytes)
     return out[0]
 
 
@@ -1768,13 +1566,10 @@ def loss_smooth1_backward(flo, image, alpha, g_value):
     (B, Cf, Ci, H, W), flo, image = _smooth1_args(who, flo, image)
     if g_value.numel() != 1:
         raise RuntimeError(f"{who}: g_value must have one element, got {list(g_value.shape)}")
-    (g_value,) = _maps(who, g_value=g_value.reshape(1))
-    lib = load()
+    (g_value,) = _tensors(who, g_value=g_value.reshape(1))
     g = torch.empty_like(flo)
-    with _on_device(flo.device):
-        rc = _entry(lib, "pdepth_loss_smooth1_backward_f32")(flo.data_ptr(), image.data_ptr(), g_value.data_ptr(), B, Cf, Ci, H, W,
-                                                             float(alpha), g.data_ptr(), _stream(flo.device))
-    _check(rc, lib)
+    _call("pdepth_loss_smooth1_backward_f32", flo.device, flo.data_ptr(), image.data_ptr(), g_value.data_ptr(), B, Cf, Ci, H, W,
+          float(alpha), g.data_ptr())
     return g
 
 
@@ -1783,7 +1578,6 @@ def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_ma
     """truth [B,H,W] + (pred [B,H,W] | logp [B,D,H,W], d_candi [D]) [+ mask [B,H,W]] -> (metrics [B,9], count [B], depth [B,H,W] |
     None): pdepth_depth_metrics_f32 on the current stream, no host synchronisation.  clamp_max None or <= 0: no clamp."""
     who = "depth_metrics"
-    lib = load()
     _no_autograd(who, truth, pred, logp, mask)
     if (pred is None) == (logp is None):
         raise RuntimeError(f"{who}: give exactly one prediction, pred [B,H,W] or logp [B,D,H,W]")
@@ -1804,41 +1598,22 @@ def depth_metrics(truth, pred=None, logp=None, d_candi=None, mask=None, clamp_ma
             raise RuntimeError(f"{who}: want_depth belongs to the volume form (the depth map form is given its map)")
     if mask is not None:
         _shape(mask, (B, H, W), "mask", who)
-    tensors = []
-    for nm, t in (("truth", truth), ("pred", pred), ("logp", logp), ("d_candi", d_candi if logp is not None else None), ("mask", mask)):
-        if t is not None:
-            if not t.is_cuda:
-                raise RuntimeError(f"{nm}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-            t = t.contiguous().float()
-        tensors.append(t)
-    truth, pred, logp, d_candi, mask = tensors
+    truth, pred, logp, d_candi, mask = _optional(truth=truth, pred=pred, logp=logp, d_candi=d_candi if logp is not None else None, mask=mask)
     dev = truth.device
     out = torch.empty(B * 10, dtype=torch.float32, device=dev)
     metrics, count = out[:B * 9].view(B, 9), out[B * 9:]
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_depth else None
-    ws_bytes = _entry(lib, "pdepth_depth_metrics_workspace_bytes")(B, H, W)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_depth_metrics_f32")(_ptr(logp), _ptr(pred), _ptr(d_candi), truth.data_ptr(), _ptr(mask),
-                                                     float(clamp_max) if clamp_max is not None else 0.0, B, D, H, W,
-                                                     metrics.data_ptr(), count.data_ptr(), _ptr(depth), ws.data_ptr(), ws_bytes,
-                                                     _stream(dev))
-    _check(rc, lib)
+    ws, ws_bytes = _workspace(_ask("pdepth_depth_metrics_workspace_bytes", B, H, W), dev)
+    _call("pdepth_depth_metrics_f32", dev, _ptr(logp), _ptr(pred), _ptr(d_candi), truth.data_ptr(), _ptr(mask),
+          float(clamp_max) if clamp_max is not None else 0.0, B, D, H, W, metrics.data_ptr(), count.data_ptr(), _ptr(depth), _ptr(ws), ws_bytes)
     return metrics, count, depth
 
 
 # ---- flow evaluation (ops.flow_metrics, ops.flow_resize) ------------------------------------------------------------------------
-def _flow_tensor(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-    return t.contiguous().float()
-
-
 def flow_metrics(gt, pred, move_mask=None, want_flow=False):
     """gt [B,2|4,H,W], pred [B,2,h,w] [, move_mask [B,H,W]] -> (errors [B,8], counts [B,5], flow_up [B,2,H,W] | None):
     pdepth_flow_metrics_f32 on the current stream, no host synchronisation."""
     who = "flow_metrics"
-    lib = load()
     _no_autograd(who, gt, pred, move_mask)
     if gt.dim() != 4 or gt.shape[1] not in (2, 4):
         raise RuntimeError(f"{who}: gt must be [B,2,H,W] or [B,4,H,W], got {list(gt.shape)}")
@@ -1850,38 +1625,30 @@ def flow_metrics(gt, pred, move_mask=None, want_flow=False):
         if C != 4:
             raise RuntimeError(f"{who}: a move mask needs a truth of 4 channels (it multiplies valid)")
         _shape(move_mask, (B, H, W), "move_mask", who)
-    gt, pred = _flow_tensor(gt, "gt"), _flow_tensor(pred, "pred")
-    move_mask = None if move_mask is None else _flow_tensor(move_mask, "move_mask")
+    gt, pred, move_mask = _optional(gt=gt, pred=pred, move_mask=move_mask)
     dev = gt.device
     if pred.device != dev or (move_mask is not None and move_mask.device != dev):
         raise RuntimeError(f"{who}: gt, pred and move_mask must be on one device")
     out = torch.empty(B * 13, dtype=torch.float32, device=dev)
     errors, counts = out[:B * 8].view(B, 8), out[B * 8:].view(B, 5)
     flow_up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if want_flow else None
-    ws_bytes = _entry(lib, "pdepth_flow_metrics_workspace_bytes")(B, H, W)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_flow_metrics_f32")(gt.data_ptr(), C, pred.data_ptr(), h, w, _ptr(move_mask), B, H, W, errors.data_ptr(),
-                                                    counts.data_ptr(), _ptr(flow_up), ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, lib)
+    ws, ws_bytes = _workspace(_ask("pdepth_flow_metrics_workspace_bytes", B, H, W), dev)
+    _call("pdepth_flow_metrics_f32", dev, gt.data_ptr(), C, pred.data_ptr(), h, w, _ptr(move_mask), B, H, W, errors.data_ptr(),
+          counts.data_ptr(), _ptr(flow_up), _ptr(ws), ws_bytes)
     return errors, counts, flow_up
 
 
 def flow_resize(flow, size, align_corners=False):
     """flow [B,2,h,w] -> [B,2,H,W], rescaled by W / w and H / h and resized: pdepth_flow_resize_f32 on the current stream."""
     who = "flow_resize"
-    lib = load()
     _no_autograd(who, flow)
     if flow.dim() != 4 or flow.shape[1] != 2:
         raise RuntimeError(f"{who}: flow must be [B,2,h,w], got {list(flow.shape)}")
     B, _, h, w = flow.shape
     H, W = (int(s) for s in size)
-    flow = _flow_tensor(flow, "flow")
+    (flow,) = _tensors(None, flow=flow)
     out = torch.empty((B, 2, H, W), dtype=torch.float32, device=flow.device)
-    with _on_device(flow.device):
-        rc = _entry(lib, "pdepth_flow_resize_f32")(flow.data_ptr(), B, h, w, H, W, 1 if align_corners else 0, out.data_ptr(),
-                                                   _stream(flow.device))
-    _check(rc, lib)
+    _call("pdepth_flow_resize_f32", flow.device, flow.data_ptr(), B, h, w, H, W, 1 if align_corners else 0, out.data_ptr())
     return out
 
 
@@ -1891,7 +1658,6 @@ def lidar_depth(points, counts, M_velo2cam, intr, height, width, filtering=2, fi
     dmap_quarter [B,H//4,W//4], mask_quarter [B,H//4,W//4]): pdepth_lidar_depth_f32 on the current stream, no host
     synchronisation."""
     who = "lidar_depth"
-    lib = load()
     _no_autograd(who, points, M_velo2cam, intr)
     if points.dim() != 3 or points.shape[2] not in (3, 4):
         raise RuntimeError(f"{who}: points must be [B,Nmax,4] or [B,Nmax,3], got {tuple(points.shape)}")
@@ -1902,26 +1668,17 @@ def lidar_depth(points, counts, M_velo2cam, intr, height, width, filtering=2, fi
     _shape(M_velo2cam, (4, 4) if M_velo2cam.dim() == 2 else (B, 4, 4), "M_velo2cam", who)
     _shape(intr, (3, 4) if intr.dim() == 2 else (B, 3, 4), "intr", who)
     H, W = int(height), int(width)
-    for nm, t in (("points", points), ("counts", counts), ("M_velo2cam", M_velo2cam), ("intr", intr)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{nm}: the HIP path needs a device tensor (got {t.device}); there is no CPU fallback")
-    if counts.dtype != torch.int32:
-        raise RuntimeError(f"counts: expected int32, got {counts.dtype}")
-    for nm, t in (("points", points), ("M_velo2cam", M_velo2cam), ("intr", intr)):
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{nm}: expected float32, got {t.dtype}")
-    points, counts, M_velo2cam, intr = (t.contiguous() for t in (points, counts, M_velo2cam, intr))
+    points, counts, M_velo2cam, intr = _tensors(None, None, points=points, counts=counts, M_velo2cam=M_velo2cam, intr=intr)
+    for nm, t, dtype in (("counts", counts, torch.int32), ("points", points, torch.float32), ("M_velo2cam", M_velo2cam, torch.float32),
+                         ("intr", intr, torch.float32)):   # (every device before any dtype, the counts' before the floats')
+        if t.dtype != dtype:
+            _refuse(t, nm, dtype)
     dev = points.device
-    ws_bytes = _entry(lib, "pdepth_lidar_depth_workspace_bytes")(B, H, W)
+    ws, ws_bytes = _workspace(_ask("pdepth_lidar_depth_workspace_bytes", B, H, W), dev)
     large = torch.empty((2, B, max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
     small = torch.empty((2, B, max(H, 0) // 4, max(W, 0) // 4), dtype=torch.float32, device=dev)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = _entry(lib, "pdepth_lidar_depth_f32")(_ptr(points) or None, counts.data_ptr(), M_velo2cam.data_ptr(), intr.data_ptr(),
-                                                   B, Nmax, dim, int(M_velo2cam.dim() == 3), int(intr.dim() == 3), H, W,
-                                                   int(filtering), float(filterdiff), float(pool_default),
-                                                   large[0].data_ptr() or None, large[1].data_ptr() or None,
-                                                   small[0].data_ptr() or None, small[1].data_ptr() or None,
-                                                   ws.data_ptr() or None, ws_bytes, _stream(dev))
-    _check(rc, lib)
+    _call("pdepth_lidar_depth_f32", dev, _ptr(points) or None, counts.data_ptr(), M_velo2cam.data_ptr(), intr.data_ptr(), B, Nmax, dim,
+          int(M_velo2cam.dim() == 3), int(intr.dim() == 3), H, W, int(filtering), float(filterdiff), float(pool_default),
+          large[0].data_ptr() or None, large[1].data_ptr() or None, small[0].data_ptr() or None, small[1].data_ptr() or None,
+          _ptr(ws), ws_bytes)
     return large[0], large[1], small[0], small[1]

@@ -282,6 +282,18 @@ def test_refusals_by_name(dev):
         g.sum().backward()
 
 
+def test_a_map_beyond_the_size_limit_is_refused_for_its_size(dev):
+    """Beyond H W = 2^24 the workspace query answers 0 and the binding passes no workspace at all: the entry refuses the size, which
+    it judges before it looks at its workspace.  Nothing is launched and nothing of the (uninitialised) maps is read."""
+    H, W = 4097, 4096
+    for call in (lambda: _native.loss_smooth(torch.empty((1, H, W), device=dev), torch.empty((1, 3, H, W), device=dev)),
+                 lambda: _native.flow_photo(torch.empty((1, 3, H, W), device=dev), torch.empty((1, 3, H, W), device=dev),
+                                            torch.empty((1, 2, H, W), device=dev), torch.empty((1, 1, H, W), device=dev), 0.15, 0.85, 1.0)):
+        with pytest.raises(RuntimeError) as refused:
+            call()
+        assert "2^24" in str(refused.value) and "workspace" not in str(refused.value)
+
+
 # ---- BaseLoss ---------------------------------------------------------------------------------------------------------------------
 def _base_run(dev, fused):
     inp = U.make_inputs()
